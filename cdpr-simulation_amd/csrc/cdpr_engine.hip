@@ -920,6 +920,10 @@ int fetch_slots(cdpr_engine* h, const float4* dsrc, int nslots, std::vector<floa
 // into the read-out scratch, then one contiguous copy.  fields = (slot, component) per output column.
 int fetch_fields(cdpr_engine* h, const float4* rows, const std::vector<std::pair<int, int>>& fields, void* host_out, uint32_t as_int = 0) {
   if (!host_out) return CDPR_OK;
+  if (fields.size() > kUnpackMaxWidth) {  // (the kernel argument holds kUnpackMaxWidth (slot, component) pairs)
+    h->err = "fetch_fields: more columns than the gather's field table holds";
+    return CDPR_ERR_INVALID;
+  }
   const size_t count = (size_t)h->batch * fields.size();
   if (h->unpack_cap < count) {
     HIP_TRY(h, wait_stream(h));
@@ -1746,6 +1750,10 @@ int cdpr_get_observables(cdpr_handle_t h, float* position, float* velocity, floa
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
   if (h->fp64) return checked(h, fetch_observables64(h, position, velocity, effort, pose7, twist6, true));
   const uint32_t n = h->n, width = 3u * n + 13u;
+  if (width > kPublishMaxWidth) {  // (the kernel argument holds kPublishMaxWidth (slot, component) pairs)
+    h->err = "cdpr_get_observables: more columns than the publish kernel's field table holds";
+    return CDPR_ERR_INVALID;
+  }
   const size_t count = (size_t)h->batch * width;
   // lazy set-up, every allocation guarded on its own pointer (a failure half way leaves nothing to leak or to skip next
   // time).  Coherent host memory: the host spins on the completion word while the kernel is still running.

@@ -408,9 +408,11 @@ int rollout_enqueue_f64(cdpr_engine* h, int samples, int horizon, const float* d
   a.nsteps = 1;
   a.publish_mask = 0;
   a.obs_step_stride = 0;
-  LaunchShape shape = launch_shape(h, 2);  // the handle's one-wave kernel, rings in memory
-  shape.f64_split = 0, shape.f64_ring_lds = 0, shape.f64_jcache = 0;
-  F64Kernel kern = f64_kernel_for(h, planned_kernel(h->plan, shape));
+  LaunchShape shape = launch_shape(h, horizon);  // the handle's one-wave kernel, rings in memory (planned_kernel's rollout rule)
+  shape.rollout = true;
+  const PlannedKernel pk = planned_kernel(h->plan, shape);
+  F64Kernel kern = f64_kernel_for(h, pk);
+  h->last_kernel = pk;
   a.travel_stop = h->tstop64 ? (int)h->cfg.travel_stop : 0;
   int calls = reset ? 0 : h->pid_calls;  // (uniform handles; per-robot handles count in the meta bytes)
   for (int k = 0; k < horizon; ++k) {

@@ -52,6 +52,9 @@ static int rollout_enqueue(cdpr_engine* h, int samples, int horizon, const float
     GenKernel kern = pick_gen_kernel(h->n, h->fk, h->td, true, h->glay.nb > 11, false);
     hipLaunchKernelGGL(kern, dim3((uint32_t)((traj + 63u) / 64u)), dim3(64), 0, h->stream, a, g);
     HIP_TRY(h, hipGetLastError());
+    LaunchShape rs = launch_shape(h, horizon);
+    rs.rollout = true;
+    h->last_kernel = planned_kernel(h->plan, rs);
     ++h->launches;
     return CDPR_OK;
   }
@@ -84,9 +87,11 @@ static int rollout_enqueue(cdpr_engine* h, int samples, int horizon, const float
   const uint64_t traj = (uint64_t)h->batch * (uint64_t)samples;
   LaunchShape rs = launch_shape(h, horizon);
   rs.rollout = true;
-  StepKernel kern = step_kernel_of(h, planned_kernel(h->plan, rs));
+  const PlannedKernel pk = planned_kernel(h->plan, rs);
+  StepKernel kern = step_kernel_of(h, pk);
   hipLaunchKernelGGL(kern, dim3((uint32_t)((traj + 63u) / 64u)), dim3(64), 0, h->stream, a);
   HIP_TRY(h, hipGetLastError());
+  h->last_kernel = pk;
   ++h->launches;
   return CDPR_OK;
 }

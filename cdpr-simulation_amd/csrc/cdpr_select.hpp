@@ -338,10 +338,12 @@ inline PlannedKernel planned_kernel(const KernelPlan& p, const LaunchShape& s) {
   PlannedKernel k;
   const int steps = s.scheduled ? std::max(s.steps, 2) : s.steps;  // a launch over a schedule runs on the several-steps kernel even for one step
   if (p.fp64) {
-    const bool ring_lds = p.n <= 8u && (s.f64_ring_lds >= 0 ? s.f64_ring_lds != 0 : p.batch <= 32768u);  // (nine to twelve cables: the plain one-wave kernel, rings in memory)
+    // a rollout steps batch x samples trajectories, one step per launch, on the handle's one-wave kernel with the rings in memory
+    // (rollout_enqueue_f64, cdpr_engine_f64.hip)
+    const bool ring_lds = !s.rollout && p.n <= 8u && (s.f64_ring_lds >= 0 ? s.f64_ring_lds != 0 : p.batch <= 32768u);  // (nine to twelve cables: the plain one-wave kernel, rings in memory)
     const bool jcache = ring_lds && (s.f64_jcache >= 0 ? s.f64_jcache != 0 : p.batch <= 16384u);
-    const bool lean = s.f64_split >= 0 ? s.f64_split == 2 : p.batch > 16384u;
-    const bool can_split = p.fk && p.td && p.n <= 8u && s.f64_split != 0 && !p.per_robot && !p.tstop64 && !p.long64 && !p.hold_long;
+    const bool lean = !s.rollout && (s.f64_split >= 0 ? s.f64_split == 2 : p.batch > 16384u);
+    const bool can_split = !s.rollout && p.fk && p.td && p.n <= 8u && s.f64_split != 0 && !p.per_robot && !p.tstop64 && !p.long64 && !p.hold_long;
     k.f64_ring_lds = ring_lds, k.f64_jcache = jcache, k.f64_lean = lean;
     // up to one workgroup per CU the role-split kernel's one-step launches beat the one-wave kernel's several-steps ones (14.4
     // against 20.8 us per step at one robot x 8, same bits): the engine then runs a fused update as one-step launches

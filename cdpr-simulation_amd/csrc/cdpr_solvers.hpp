@@ -3,6 +3,7 @@
 // Lane-per-robot like the step kernel and built from the same device functions, but with the
 // caller's robot-major arrays (float[B][n], float[B][7] ...) read and written directly.
 #pragma once
+#include "../../include/cdpr.h"
 #include "cdpr_step_kernel.hpp"
 
 namespace cdpr {
@@ -143,13 +144,16 @@ __global__ __launch_bounds__(64) void cdpr_solver_kernel(const SolveArgs a) {
 // Observable read-out: slot rows (float4 per robot per slot) -> robot-major float arrays as the C-ABI hands them out
 // ([B][W]), on the device, so the host gets one contiguous copy instead of transposing B x W values in a scalar loop
 // (at 524 288 robots: 50 MB of joint states).  Thread (r, j) picks component comp[j] of slot slot[j] of robot r.
+constexpr uint32_t kUnpackMaxWidth = 24;  // the widest field list of one gather: a joint block (n columns), a pose, a twist
 struct UnpackArgs {
   const float4* rows;
   float* out;
   uint32_t stride, batch, width;
-  uint8_t slot[24], comp[24];
+  uint8_t slot[kUnpackMaxWidth], comp[kUnpackMaxWidth];
   uint32_t as_int;  // bit j set: the value is converted to int32 (iteration counts, flags) before it is stored
 };
+static_assert(kUnpackMaxWidth >= CDPR_MAX_CABLES, "UnpackArgs: a joint block of CDPR_MAX_CABLES columns must fit the field table");
+static_assert(kUnpackMaxWidth <= 32, "UnpackArgs: as_int has one bit per column");
 
 static __global__ __launch_bounds__(256) void cdpr_unpack_kernel(const UnpackArgs a) {
   const uint32_t t = blockIdx.x * 256u + threadIdx.x;
@@ -163,6 +167,7 @@ static __global__ __launch_bounds__(256) void cdpr_unpack_kernel(const UnpackArg
 // robot-major blocks [position | velocity | effort | pose7 | twist6] gathered from the observable rows by one launch,
 // then a completion word written by the last workgroup after a system-scope fence.  The host spins on that word: no
 // copy engine, no runtime call in the wait (cdpr_get_observables).
+constexpr uint32_t kPublishMaxWidth = 3u * CDPR_MAX_CABLES + 13u;  // three joint blocks of n columns, pose7, twist6
 struct PublishArgs {
   const float4* rows;
   float* out;               // host-mapped
@@ -170,8 +175,10 @@ struct PublishArgs {
   uint32_t* arrivals;       // device counter, zero between launches
   uint64_t epoch;
   uint32_t stride, batch, n, width;  // width = 3 n + 13
-  uint8_t slot[40], comp[40];
+  uint8_t slot[kPublishMaxWidth], comp[kPublishMaxWidth];
 };
+static_assert(sizeof(PublishArgs::slot) == 3u * CDPR_MAX_CABLES + 13u, "PublishArgs: one field per output column at CDPR_MAX_CABLES cables");
+static_assert(CDPR_MAX_CABLES + 1u <= 24u, "pack_flags: the TD flag and one travel-limit bit per cable must stay exact in a float");
 
 static __global__ __launch_bounds__(256) void cdpr_publish_kernel(const PublishArgs a) {
   // one thread per OUTPUT element, so that a wave writes 256 contiguous bytes (the destination may be host memory behind

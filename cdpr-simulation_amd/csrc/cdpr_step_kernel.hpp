@@ -568,7 +568,8 @@ CDPR_DEV uint32_t travel_mask(const StepArgs& a, const v2f (&q)[cable_pairs(N)])
   }
   return m;
 }
-// observable slot 3, component w: tension-distribution flag in bit 0, travel-limit mask above it (<= 511: exact in a float)
+// observable slot 3, component w: tension-distribution flag in bit 0, travel-limit mask above it (13 bits at
+// CDPR_MAX_CABLES = 12, < 2^24: exact in a float)
 CDPR_DEV float pack_flags(int td_flag, uint32_t limit_mask) { return (float)((uint32_t)td_flag | (limit_mask << 1)); }
 
 // The joint stop itself ([EXT] Gazebo/ODE -> reduced; cdpr_config_t.travel_stop), between the velocity and the pose half

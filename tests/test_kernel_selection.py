@@ -1,8 +1,8 @@
 """What CDPR_MAP_AUTO picks, as a table: the routing rules of cdpr-simulation_amd/csrc/cdpr_select.hpp are
 pure functions of the configuration, exposed without a GPU through cdpr_plan_kernel (include/cdpr.h), and every cell of
-  cables {4, 6, 7, 8} x stages {none, FK, TD, FK + TD} x batch {1, 4 096, 32 768, 65 536, 131 072, 524 288}
-  x handle {uniform, per-robot, general (hold branch live), precision = 64} x steps per launch {1, 10}
-is pinned to the kernel name in tests/golden/kernel_selection.json (regenerate: python tests/test_kernel_selection.py --write,
+  cables {1 .. 12} x stages {none, FK, TD, FK + TD} x batch {1, 4 096, 32 768, 65 536, 131 072, 524 288}
+  x handle {uniform, per-robot, general (hold branch live), precision = 64} x launch {1 step, 10 steps, MPC rollout}
+(FK / TD from six cables on; a refused combination is pinned as its return code and reason) is pinned to the kernel name in tests/golden/kernel_selection.json (regenerate: python tests/test_kernel_selection.py --write,
 and review the diff: a changed cell is a changed routing decision).  The engine takes its kernels from the same function
 (cdpr_engine.hip, cdpr_engine_f64.hip: planned_kernel -> step_kernel_of), and tests/test_gpu_full_size.py checks on the GPU that the kernel a
 handle really launched (cdpr_kernel_name) is the planned one."""
@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "kernel_selection.json")
 OVERRIDES = ("CDPR_MAPPING", "CDPR_LOWREG", "CDPR_CHUNK", "CDPR_PERSIST", "CDPR_ONESTEP", "CDPR_SPLIT", "CDPR_PAIR_STREAM", "CDPR_GEN_SPLIT", "CDPR_GEN_LEAN",
              "CDPR_GEN_HOT")
-CABLES, BATCHES = (4, 6, 7, 8), (1, 4096, 32768, 65536, 131072, 524288)
+CABLES, BATCHES = tuple(range(1, 13)), (1, 4096, 32768, 65536, 131072, 524288)
 STAGES = {"none": 0, "fk": 1, "td": 2, "fk+td": 3}
 HANDLES = ("uniform", "per_robot", "general", "fp64")
 FIRST, SCHEDULED, ROLLOUT, NOT_STEADY = 1, 2, 4, 8
@@ -27,7 +27,7 @@ FIRST, SCHEDULED, ROLLOUT, NOT_STEADY = 1, 2, 4, 8
 def model_of(pkg, n):
     if n == 4:
         return pkg.cube_model()
-    full = pkg.eight_cable_model()
+    full = pkg.eight_cable_model() if n <= 8 else pkg.twelve_cable_model()
     return replace(full, frame_anchors=full.frame_anchors[:n], platform_anchors=full.platform_anchors[:n])
 
 
@@ -55,9 +55,9 @@ def table(pkg):
                         kw["velocityEpsilon"] = 0.001
                     elif handle == "fp64":
                         kw["precision"] = 64
-                    for steps in (1, 10):
-                        rc, name = plan(pkg, pkg.Config(**kw), steps)
-                        out[f"n{n} {sname} b{batch} {handle} k{steps}"] = name if rc == 0 else f"rc {rc}: {name}"
+                    for steps, flags, cell in ((1, 0, "k1"), (10, 0, "k10"), (10, ROLLOUT, "rollout")):
+                        rc, name = plan(pkg, pkg.Config(**kw), steps, flags)
+                        out[f"n{n} {sname} b{batch} {handle} {cell}"] = name if rc == 0 else f"rc {rc}: {name}"
     return out
 
 
@@ -80,6 +80,12 @@ def test_auto_routing_table_is_pinned(pkg, clean_env):
     assert got["n8 fk+td b524288 uniform k1"] == "cdpr_step_kernel<8, true, true, SINGLE, LOWREG>"  # config 4 on one GPU
     assert got["n8 fk+td b65536 general k1"].startswith("cdpr_gen_lean_kernel<8>")
     assert got["n8 fk+td b65536 fp64 k1"] == "cdpr_split_kernel_f64<8, LEAN>"
+    # a precision = 64 rollout runs on the handle's one-wave kernel with the rings in memory (rollout_enqueue_f64), whatever
+    # the step launches of the same handle run on
+    assert got["n8 fk+td b1 fp64 k1"] == "cdpr_split_kernel_f64<8>" and got["n8 fk+td b1 fp64 rollout"] == "cdpr_step_kernel_f64<8>"
+    assert got["n8 none b1 fp64 k10"] == "cdpr_step_kernel_f64<8, RING_LDS, JCACHE>" and got["n8 none b1 fp64 rollout"] == "cdpr_step_kernel_f64<8>"
+    assert got["n8 fk+td b4096 uniform rollout"] == "cdpr_step_kernel<8, true, true, ROLLOUT>"  # config 5
+    assert got["n12 none b1 general k1"].startswith("rc -3: more than 8 cables")  # (refused by name, not served by another path)
 
 
 def test_launch_flags_and_overrides(pkg, clean_env, monkeypatch):
