@@ -8,6 +8,9 @@
   geometry.json      gen_cdpr.py's geometry formulas (lines 101-125) re-evaluated with the
                      reference's own transformations.py imported from /root/reference
                      (gen_cdpr.py itself is Python 2 and imports a missing module).
+  geometry_workspace.json  the same formulas (gen_cdpr.py:101-125 and :181) at 64 seeded poses across the workspace and the 13
+                     special poses of tests/workspace_poses.py, rotation matrix and quaternion from the reference's
+                     transformations.py (euler_matrix, quaternion_from_matrix): pins IK away from R = I.
   biquad.json        outputs of the reference's own Filter.h BiQuad<double>, via
                      oracle/_ref/libref_filter.so (built by oracle/Makefile from the header
                      where it lies).
@@ -97,6 +100,51 @@ def geometry(model):
     out["rank_J_home"] = int(np.linalg.matrix_rank(J))
     # static tension balancing gravity 9.8 on the 1 kg platform (vertical force balance, 4 equal cables)
     out["static_tension_g9.8"] = float(model["sdf_platform_inertia"]["mass"] * 9.8 / (-J[:, 2].sum()))
+    return out
+
+
+def geometry_workspace(model):
+    """gen_cdpr.py:101-125 and :181 at poses across the workspace, on the 4-cable `points` of cube.yaml: xyz in box E of
+    tests/workspace_poses.py, rpy through the reference's euler_matrix (roll, pitch +-0.4, yaw +-pi), then the special poses
+    (yaw pi and +-pi / 2, the largest tilt about x and about y alone, the corners of W's position box).  Data only."""
+    sys.path.insert(0, os.path.join(REF, "sdf"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import transformations as tr  # the reference's own module, imported where it lies
+    import workspace_poses as wp
+
+    class Home:
+        home_position = model["sdf_platform_pose"][:3]
+
+    e = wp.BOXES["E"]
+    rng = np.random.default_rng(20261017)
+    poses = []
+    for _ in range(64):
+        xyz = [float(rng.uniform(-e["dxy"], e["dxy"])), float(rng.uniform(-e["dxy"], e["dxy"])), float(rng.uniform(e["zlo"], e["zhi"]))]
+        rpy = [float(rng.uniform(-e["dr"], e["dr"])), float(rng.uniform(-e["dr"], e["dr"])), float(rng.uniform(-np.pi, np.pi))]
+        poses.append((xyz, rpy, False))
+    poses += [([float(v) for v in xyz], [float(v) for v in rpy], True) for rpy, xyz in wp.special_rpy_xyz(Home, tilt=e["dr"])]
+    z = [0, 0, 1]
+    out = {"source": "gen_cdpr.py:101-125 and :181 formulas evaluated with the reference's transformations.py (euler_matrix, "
+                     "quaternion_from_matrix reordered from w x y z to x y z w, sign as returned) on the points of sdf/cube.yaml",
+           "points": model["yaml"]["points"], "poses": []}
+    for xyz, rpy, special in poses:
+        pf_t = np.array(xyz).reshape(3, 1)
+        m4 = tr.euler_matrix(rpy[0], rpy[1], rpy[2])
+        pf_R = m4[:3, :3]  # gen:102
+        qw = tr.quaternion_from_matrix(m4)
+        cables = []
+        for cbl in model["yaml"]["points"]:
+            fp = np.array(cbl["frame"], dtype=float).reshape(3, 1)
+            pp = pf_t + np.dot(pf_R, np.array(cbl["platform"], dtype=float).reshape(3, 1))  # gen:115
+            u = (pp - fp).reshape(3)
+            L = float(np.linalg.norm(u))
+            u = u / L  # gen:117-118
+            R = tr.rotation_matrix(np.arctan2(np.linalg.norm(np.cross(z, u)), np.dot(u, z)), np.cross(z, u))  # gen:119
+            rb = (pp - pf_t).reshape(3)
+            cables.append({"L": L, "u": u.tolist(), "Rb": rb.tolist(), "jacobian_row": u.tolist() + np.cross(rb, u).tolist(),
+                           "axis": (-R[:3, 2]).tolist()})  # gen:181 prismatic axis = -R[:,2]
+        out["poses"].append({"xyz": xyz, "rpy": rpy, "special": special, "R": pf_R.tolist(),
+                             "quaternion_xyzw": [float(qw[1]), float(qw[2]), float(qw[3]), float(qw[0])], "cables": cables})
     return out
 
 
@@ -248,6 +296,7 @@ if __name__ == "__main__":
     m = cube_model()
     json.dump(m, open(os.path.join(HERE, "cube_model.json"), "w"), indent=1)
     json.dump(geometry(m), open(os.path.join(HERE, "geometry.json"), "w"), indent=1)
+    json.dump(geometry_workspace(m), open(os.path.join(HERE, "geometry_workspace.json"), "w"), indent=0)
     json.dump(biquad(), open(os.path.join(HERE, "biquad.json"), "w"), indent=1)
     json.dump(biquad_live(), open(os.path.join(HERE, "biquad_live.json"), "w"), indent=1)
     json.dump(sdf_loader_values(), open(os.path.join(HERE, "sdf_loader_values.json"), "w"), indent=1)

@@ -85,3 +85,61 @@ def test_survey_home_geometry_values(pkg, oracle):
     sv = np.linalg.svd(j8, compute_uv=False)
     assert np.allclose(sv, kat["eight_cable_singular_values"], rtol=2e-3)
     assert np.linalg.matrix_rank(j8) == 6
+
+
+def test_ik_matches_generator_geometry_across_the_workspace(pkg, oracle):
+    """oracle IK (lengths, Jacobian, q = L0 - L) at the 77 poses of geometry_workspace.json - box E, yaw to +-pi, the special poses -
+    == gen_cdpr.py:101-125 evaluated with the reference's euler_matrix; the pose goes in as the quaternion the reference's
+    quaternion_from_matrix returned, and once more negated.  The prismatic axis (gen:181) is -u."""
+    from cdpr_simulation_amd.config import quat_to_matrix
+
+    geo = load("geometry_workspace.json")
+    cfg = pkg.Config()
+    s = cfg.to_struct()
+    l0 = cfg.model.reference_lengths()
+    assert len(geo["poses"]) >= 64 + 13 and geo["points"] == load("cube_model.json")["yaml"]["points"]
+    rot_span = 0.0
+    for p in geo["poses"]:
+        quat = np.array(p["quaternion_xyzw"])
+        assert np.abs(quat_to_matrix(quat) - np.array(p["R"])).max() < 1e-12
+        rot_span = max(rot_span, float(np.abs(np.array(p["R"]) - np.eye(3)).max()))
+        for sign in (1.0, -1.0):
+            q, _, ln, jac = oracle.ik(s, np.concatenate([p["xyz"], sign * quat]))
+            for i, c in enumerate(p["cables"]):
+                assert abs(ln[i] - c["L"]) < 1e-12 and abs(q[i] - (l0[i] - c["L"])) < 1e-12
+                assert np.abs(jac[i] - c["jacobian_row"]).max() < 1e-12
+                assert np.abs(jac[i, :3] + c["axis"]).max() < 1e-12
+    assert rot_span > 1.9  # (the fixture leaves R = I far behind: a diagonal entry near -1)
+
+
+def test_second_derivation_ik_matches_generator_geometry_across_the_workspace(pkg):
+    """tests/second_derivation.py's IK (scipy's Rotation) against the same fixture: lengths, unit vectors, lever arms R b."""
+    import second_derivation as sd
+    from scipy.spatial.transform import Rotation
+
+    geo = load("geometry_workspace.json")
+    m = pkg.cube_model()
+    l0 = m.reference_lengths()
+    for p in geo["poses"]:
+        rot = Rotation.from_quat(p["quaternion_xyzw"])
+        q, _, u, rb = sd.ik(np.asarray(m.frame_anchors, float), np.asarray(m.platform_anchors, float), l0, np.array(p["xyz"]), rot, np.zeros(3), np.zeros(3))
+        for i, c in enumerate(p["cables"]):
+            assert abs(q[i] - (l0[i] - c["L"])) < 1e-12
+            assert np.abs(u[i] - c["u"]).max() < 1e-12 and np.abs(rb[i] - c["Rb"]).max() < 1e-12
+            assert np.abs(np.concatenate([u[i], np.cross(rb[i], u[i])]) - c["jacobian_row"]).max() < 1e-12
+
+
+def test_special_poses_are_the_fixtures(pkg):
+    """tests/workspace_poses.special_poses (closed-form quaternions, yaw pi with w = 0 exactly) are the rotations and positions the
+    fixture stores for its special poses (there at box E's tilt), twins included."""
+    import workspace_poses as wp
+    from cdpr_simulation_amd.config import quat_to_matrix
+
+    fixture = [p for p in load("geometry_workspace.json")["poses"] if p["special"]]
+    mine = wp.special_poses(pkg.cube_model(), tilt=wp.BOXES["E"]["dr"])
+    assert len(fixture) == wp.N_SPECIAL and mine.shape == (2 * wp.N_SPECIAL, 7)
+    assert list(mine[0, 3:]) == [0.0, 0.0, 1.0, 0.0]
+    for k, p in enumerate(fixture):
+        for row in (mine[k], mine[k + wp.N_SPECIAL]):
+            assert np.abs(row[:3] - p["xyz"]).max() < 1e-15 and np.abs(quat_to_matrix(row[3:]) - np.array(p["R"])).max() < 1e-15 + 3e-16
+    assert np.array_equal(mine[: wp.N_SPECIAL, 3:], -mine[wp.N_SPECIAL:, 3:])
