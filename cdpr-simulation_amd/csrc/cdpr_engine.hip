@@ -204,6 +204,20 @@ double sim_time(uint64_t step, double dt) {
   return (double)(now_ns / 1000000000LL) + (double)(now_ns % 1000000000LL) * 1e-9;
 }
 
+// Which of the next k world steps publish (bit j: world step h->step + j), PLG.cpp:236-242: strict '>' against the last
+// published stamp, which moves on with every step that does.
+uint64_t publish_mask(cdpr_engine* h, int k) {
+  uint64_t mask = 0;
+  for (int j = 0; j < k; ++j) {
+    const double now = sim_time(h->step + (uint64_t)j, h->cfg.dt);
+    if ((now - h->prev_publish) > h->cfg.publish_period) {
+      h->prev_publish = now;
+      mask |= (1ull << j);
+    }
+  }
+  return mask;
+}
+
 int set_device(cdpr_engine* h) {
   HIP_TRY(h, hipSetDevice(h->device));
   return CDPR_OK;
@@ -235,11 +249,8 @@ int upload_home(cdpr_engine* h) {
   }
   HIP_TRY(h, hipMemcpyAsync(h->d_obs, o.data(), o.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream));
   if (h->d_dbg) HIP_TRY(h, hipMemsetAsync(h->d_dbg, 0, (size_t)h->batch * CDPR_PID_DEBUG_AXES * sizeof(float), h->stream));
-  for (int i = 0; i < 2; ++i) {  // latched and pending Joy buffers: target 0 after Load / reset
-    HIP_TRY(h, hipMemsetAsync(h->d_vel[i], 0, (size_t)h->stride * h->n * sizeof(float), h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_pos[i], 0, (size_t)h->stride * h->n * sizeof(float), h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_frc[i], 0, (size_t)h->stride * h->n * sizeof(float), h->stream));
-  }
+  for (int i = 0; i < 2; ++i)  // latched and pending Joy buffers: target 0 after Load / reset
+    for (CmdChannel& c : h->cmd) HIP_TRY(h, hipMemsetAsync(c.d[i], 0, (size_t)h->stride * h->n * sizeof(float), h->stream));
   if (h->d_rec) HIP_TRY(h, hipMemsetAsync(h->d_rec, 0, h->glay.bytes(h->stride), h->stream));
   if (h->d_mode) HIP_TRY(h, hipMemsetAsync(h->d_mode, kModePosition, h->batch, h->stream));  // PLG.cpp:153-157 (call count 0)
   if (h->d_target) HIP_TRY(h, hipMemsetAsync(h->d_target, 0, (size_t)h->stride * h->n * sizeof(float), h->stream));  // target 0 after Load
@@ -263,8 +274,6 @@ void free_all(cdpr_engine* h) {
     if (p64) (void)hipFree(p64);
   if (h->d_mode) (void)hipFree(h->d_mode);
   if (h->d_target) (void)hipFree(h->d_target);
-  for (int i = 0; i < 3; ++i)
-    if (h->d_mask[i]) (void)hipFree(h->d_mask[i]);
   if (h->d_unpack) (void)hipFree(h->d_unpack);
   for (void* p64 : {(void*)h->d_state64, (void*)h->d_obs64, (void*)h->d_geom64, (void*)h->d_wtab64, (void*)h->d_dbg64, h->d_unpack64})
     if (p64) (void)hipFree(p64);
@@ -275,22 +284,19 @@ void free_all(cdpr_engine* h) {
   if (h->d_pub_arrivals) (void)hipFree(h->d_pub_arrivals);
   if (h->d_roll_ref) (void)hipFree(h->d_roll_ref);
   if (h->d_roll_cost) (void)hipFree(h->d_roll_cost);
-  for (int i = 0; i < 2; ++i) {
-    if (h->d_vel[i]) (void)hipFree(h->d_vel[i]);
-    if (h->d_pos[i]) (void)hipFree(h->d_pos[i]);
-    if (h->d_frc[i]) (void)hipFree(h->d_frc[i]);
-  }
   for (auto& g : h->graphs) {
     (void)hipGraphExecDestroy(g.exec);
     (void)hipGraphDestroy(g.graph);
   }
   if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
-  for (int k = 0; k < 3; ++k) {
+  for (CmdChannel& c : h->cmd) {
     for (int i = 0; i < 2; ++i) {
-      if (h->h_stage[k][i]) (void)hipHostFree(h->h_stage[k][i]);
-      if (h->stage_ev[k][i]) (void)hipEventDestroy(h->stage_ev[k][i]);
+      if (c.d[i]) (void)hipFree(c.d[i]);
+      if (c.h_stage[i]) (void)hipHostFree(c.h_stage[i]);
+      if (c.stage_ev[i]) (void)hipEventDestroy(c.stage_ev[i]);
     }
-    if (h->free_ev[k]) (void)hipEventDestroy(h->free_ev[k]);
+    if (c.d_mask) (void)hipFree(c.d_mask);
+    if (c.free_ev) (void)hipEventDestroy(c.free_ev);
   }
   if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -300,12 +306,12 @@ void free_all(cdpr_engine* h) {
 }
 
 void engine_reset_host(cdpr_engine* h) {
-  h->vel_pending = h->pos_pending = h->frc_pending = false;
-  h->vel_masked = h->pos_masked = h->frc_masked = false;
-  for (int k = 0; k < 3; ++k) h->sched_rows[k] = nullptr, h->sched_mask[k] = nullptr;
+  for (CmdChannel& c : h->cmd) {
+    c.pending = c.masked = c.have = false;
+    c.ext[0] = c.ext[1] = nullptr;
+    c.sched_rows = nullptr, c.sched_mask = nullptr;
+  }
   if (h->h_fault) *h->h_fault = 0u;
-  h->ext_vel[0] = h->ext_vel[1] = h->ext_pos[0] = h->ext_pos[1] = h->ext_frc[0] = h->ext_frc[1] = nullptr;
-  h->have_vel = h->have_pos = h->have_frc = false;
   h->mode = kModePosition;  // PLG.cpp:153-157: Position mode, target 0 after operator= -> reset()
   h->step = 0;
   h->pid_calls = 0;
@@ -316,12 +322,15 @@ void engine_reset_host(cdpr_engine* h) {
 // in any other way than latching it (device-side staging, masked merges, resets).
 static int drain_copy_stream(cdpr_engine* h) {
   if (h->copy_stream) HIP_TRY(h, hipStreamSynchronize(h->copy_stream));
-  h->ready_wait[0] = h->ready_wait[1] = h->ready_wait[2] = nullptr;
+  for (CmdChannel& c : h->cmd) c.ready_wait = nullptr;
   return CDPR_OK;
 }
 
-int stage_command(cdpr_engine* h, float* dst, const float* src, size_t count, bool from_device) {
+// The rows of a command of `kind` into that kind's pending device buffer (every setter but the masked and the bound forms).
+int stage_command(cdpr_engine* h, int kind, const float* src, size_t count, bool from_device) {
   const size_t n = h->n, B = h->batch;
+  CmdChannel& c = h->cmd[kind];
+  float* const dst = c.d[1];
   if (!src) {
     h->err = "null command buffer";
     return CDPR_ERR_INVALID;
@@ -343,26 +352,25 @@ int stage_command(cdpr_engine* h, float* dst, const float* src, size_t count, bo
     return CDPR_OK;
   }
   // host source: rows -> pinned staging -> pending device buffer on the copy stream, no wait for the launches in flight
-  const int kind = (dst == h->d_vel[1]) ? 0 : (dst == h->d_pos[1]) ? 1 : 2;
   if (!h->copy_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-  const int idx = (h->stage_idx[kind] ^= 1);
-  if (!h->h_stage[kind][idx]) {
-    HIP_TRY(h, hipHostMalloc((void**)&h->h_stage[kind][idx], bytes, hipHostMallocDefault));
-    HIP_TRY(h, hipEventCreateWithFlags(&h->stage_ev[kind][idx], hipEventDisableTiming));
+  const int idx = (c.stage_idx ^= 1);
+  if (!c.h_stage[idx]) {
+    HIP_TRY(h, hipHostMalloc((void**)&c.h_stage[idx], bytes, hipHostMallocDefault));
+    HIP_TRY(h, hipEventCreateWithFlags(&c.stage_ev[idx], hipEventDisableTiming));
   }
-  if (!h->free_ev[kind]) HIP_TRY(h, hipEventCreateWithFlags(&h->free_ev[kind], hipEventDisableTiming));
-  if (h->stage_ev_set[kind][idx]) HIP_TRY(h, hipEventSynchronize(h->stage_ev[kind][idx]));  // two commands back: long done
-  float* stage = h->h_stage[kind][idx];
+  if (!c.free_ev) HIP_TRY(h, hipEventCreateWithFlags(&c.free_ev, hipEventDisableTiming));
+  if (c.stage_ev_set[idx]) HIP_TRY(h, hipEventSynchronize(c.stage_ev[idx]));  // two commands back: long done
+  float* stage = c.h_stage[idx];
   if (count == n * B) {
     memcpy(stage, src, bytes);  // the caller may reuse its buffer on return
   } else {
     for (size_t b = 0; b < B; ++b) memcpy(stage + b * n, src, n * sizeof(float));
   }
-  if (h->free_ev_set[kind]) HIP_TRY(h, hipStreamWaitEvent(h->copy_stream, h->free_ev[kind], 0));
+  if (c.free_ev_set) HIP_TRY(h, hipStreamWaitEvent(h->copy_stream, c.free_ev, 0));
   HIP_TRY(h, hipMemcpyAsync(dst, stage, bytes, hipMemcpyHostToDevice, h->copy_stream));
-  HIP_TRY(h, hipEventRecord(h->stage_ev[kind][idx], h->copy_stream));
-  h->stage_ev_set[kind][idx] = true;
-  h->ready_wait[kind] = h->stage_ev[kind][idx];
+  HIP_TRY(h, hipEventRecord(c.stage_ev[idx], h->copy_stream));
+  c.stage_ev_set[idx] = true;
+  c.ready_wait = c.stage_ev[idx];
   return CDPR_OK;
 }
 
@@ -427,9 +435,9 @@ GenCtl general_ctl(const cdpr_engine* h) {
   g.rec = h->d_rec;
   g.rstride = h->stride;
   g.rec_bytes = (uint32_t)h->glay.bytes(h->stride);
-  g.vel_cmd = h->have_vel ? (h->ext_vel[0] ? h->ext_vel[0] : h->d_vel[0]) : nullptr;
-  g.pos_cmd = h->have_pos ? (h->ext_pos[0] ? h->ext_pos[0] : h->d_pos[0]) : nullptr;
-  g.frc_cmd = h->have_frc ? (h->ext_frc[0] ? h->ext_frc[0] : h->d_frc[0]) : nullptr;
+  const float* latched[kCmdKinds];
+  for (int k = 0; k < kCmdKinds; ++k) latched[k] = h->cmd[k].have ? h->cmd[k].latched() : nullptr;
+  g.vel_cmd = latched[CDPR_COMMAND_VELOCITY], g.pos_cmd = latched[CDPR_COMMAND_POSITION], g.frc_cmd = latched[CDPR_COMMAND_FORCE];
   g.mode_arr = h->per_robot ? h->d_mode : nullptr;
   g.wtab = h->d_gwtab;
   g.mode = h->mode;
@@ -487,14 +495,7 @@ int run_steps_general(cdpr_engine* h, int nsteps, int per_launch, float4* record
     a.flags = (h->step == 0) ? kFlagFirstWorldStep : 0u;
     g.now_step = (int)h->step;
     if (record) a.obs = record + (size_t)done * image;
-    a.publish_mask = 0;
-    for (int j = 0; j < k; ++j) {  // PLG.cpp:236-242: strict '>' against the last published stamp
-      const double now = sim_time(h->step + (uint64_t)j, h->cfg.dt);
-      if ((now - h->prev_publish) > h->cfg.publish_period) {
-        h->prev_publish = now;
-        a.publish_mask |= (1ull << j);
-      }
-    }
+    a.publish_mask = publish_mask(h, k);
     hipLaunchKernelGGL(kern, dim3((h->batch + 63u) / 64u), dim3((gsplit || glean) ? 128 : 64), 0, h->stream, a, g);
     HIP_TRY(h, hipGetLastError());
     ++h->launches;
@@ -577,6 +578,141 @@ void launch_step(cdpr_engine* h, StepKernel kern, uint32_t robots_per_block, dim
   }
 }
 
+// the general path's hot rows back into the H slots (cdpr_gen_flush_hot_kernel) before a Pid's records are reset or latched over
+static void flush_hot(cdpr_engine* h) {
+  if (!h->d_rec || !h->gen_hot) return;
+  GenFlushArgs fa{};
+  fa.rec = h->d_rec, fa.rstride = h->stride, fa.batch = h->batch, fa.lay = h->glay, fa.nbuf = std::max(h->gpid[0].nbuf, 1);
+  hipLaunchKernelGGL(cdpr_gen_flush_hot_kernel, dim3((h->batch + 255u) / 256u), dim3(256), 0, h->stream, fa);
+}
+
+// Pid::reset of one Pid of every cable (general path): its slots, its rows
+static hipError_t reset_block(cdpr_engine* h, int which) {
+  const GenLayout& L = h->glay;
+  flush_hot(h);
+  hipError_t e1 = hipMemsetAsync(h->d_rec + (size_t)L.block_a(which, 0) * h->stride * 4, 0, (size_t)L.pid_slots() * h->stride * 16, h->stream);
+  if (e1 != hipSuccess || L.pid_rows() == 0) return e1;
+  return hipMemsetAsync(h->d_rec + ((size_t)L.slots() * 4 + (size_t)L.block_b(which, 0)) * h->stride, 0, (size_t)L.pid_rows() * h->stride * 4, h->stream);
+}
+
+// precision = 64 with the hold branch: Pid::reset of one Pid of every cable (its rows behind the state)
+static hipError_t reset_block64(cdpr_engine* h, int which) {
+  for (uint32_t i = 0; i < h->n; ++i) {
+    hipError_t e1 = hipMemsetAsync(h->d_state64 + (size_t)f64_hold_row((int)h->n, (int)i, which, h->hold_win) * h->stride, 0, (size_t)hold_pid_rows(h->hold_win) * h->stride * sizeof(double),
+                                   h->stream);
+    if (e1 != hipSuccess) return e1;
+  }
+  return hipSuccess;
+}
+
+// Per-robot handles: every robot has its own mode, so a command of `kind` (masked or not) is latched on the device, robot by
+// robot, by the latch kernel of the handle's path: precision = 64, register-resident, general.
+static int latch_per_robot(cdpr_engine* h, int kind, const float* pending, const uint8_t* mask) {
+  const CmdKind& K = kCmdKind[kind];
+  const dim3 grid((h->batch + 255u) / 256u), block(256);
+  if (h->fp64) {  // the same on the double state (integral rows 20 + 11 i + 10)
+    LatchF64Args lf{};
+    lf.mask = mask;
+    lf.meta = h->d_mode;
+    lf.pending = pending;
+    lf.target = h->d_target;
+    lf.state = h->d_state64;
+    lf.stride = h->stride;
+    lf.batch = h->batch;
+    lf.n = h->n;
+    lf.new_mode = K.meta;
+    lf.hold = h->hold64 ? 1u : 0u;
+    lf.win = (uint32_t)h->win64;
+    lf.hold_win = (uint32_t)h->hold_win;
+    hipLaunchKernelGGL(cdpr_latch_f64_kernel, grid, block, 0, h->stream, lf);
+  } else if (!h->general) {  // one active target row and one Pid record per robot
+    LatchFastArgs lf{};
+    lf.mask = mask;
+    lf.meta = h->d_mode;
+    lf.pending = pending;
+    lf.target = h->d_target;
+    lf.hot = h->d_state + (size_t)(plat_slots(h->fk) + 5 * cable_pairs((int)h->n)) * h->stride;
+    lf.stride = h->stride;
+    lf.batch = h->batch;
+    lf.n = h->n;
+    lf.hot_rows = (uint32_t)((cable_pairs((int)h->n) + 1) / 2);
+    lf.new_mode = K.meta;
+    hipLaunchKernelGGL(cdpr_latch_fast_kernel, grid, block, 0, h->stream, lf);
+  } else {
+    flush_hot(h);
+    GenLatchArgs la{};
+    la.mask = mask;
+    la.mode = h->d_mode;
+    la.pending = pending;
+    la.latched = h->cmd[kind].d[0];
+    la.rec = h->d_rec;
+    la.rstride = h->stride;
+    la.batch = h->batch;
+    la.n = h->n;
+    la.reset_pid = K.reset_pid;  // (-1: setForce resets no Pid)
+    la.lay = h->glay;
+    la.new_mode = K.mode;
+    hipLaunchKernelGGL(cdpr_gen_latch_kernel, grid, block, 0, h->stream, la);
+  }
+  HIP_TRY(h, hipGetLastError());
+  return CDPR_OK;
+}
+
+// PLG.cpp:206-219: an update starts by latching the pending commands, velocity first, then position; force after the two
+// Joy topics ([NEW] ordering: the reference has no force callback).  `reset_pid`: the mode change of a uniform handle asks
+// the launches that follow to zero their single Pid record (register-resident path, precision = 64 without the hold branch).
+static int latch_pending(cdpr_engine* h, bool& reset_pid) {
+  for (CmdChannel& c : h->cmd) {
+    if (c.pending && c.ready_wait) {  // a host Joy batch is (or was) on its way on the copy stream
+      HIP_TRY(h, hipStreamWaitEvent(h->stream, c.ready_wait, 0));
+      c.ready_wait = nullptr;
+    }
+  }
+  bool touched[kCmdKinds] = {false, false, false};  // the engine's own pending buffer was read (latch kernel) or swapped
+  for (int k = 0; k < kCmdKinds; ++k) {
+    CmdChannel& c = h->cmd[k];
+    if (!c.pending) continue;
+    const CmdKind& K = kCmdKind[k];
+    if (h->per_robot) {
+      // (a batch of a device-resident schedule, cdpr_update_scheduled_kind, is latched from the caller's buffers in place)
+      const bool in_place = c.sched_rows != nullptr;
+      if (int rc = latch_per_robot(h, k, in_place ? c.sched_rows : c.d[1], in_place ? c.sched_mask : (c.masked ? c.d_mask : nullptr))) return rc;
+      touched[k] = !in_place;
+    } else {
+      if (c.ext[1]) {  // bound caller buffer: latched by pointer, nothing copied
+        c.ext[0] = c.ext[1];
+        c.ext[1] = nullptr;
+      } else {
+        std::swap(c.d[0], c.d[1]);
+        c.ext[0] = nullptr;
+        touched[k] = true;  // what is pending now was the latched buffer of the launches queued so far
+      }
+      if (K.reset_pid >= 0) {  // entering a mode resets its Pid (fast path: the single record now belongs to that Pid)
+        reset_pid = (h->mode != K.mode);
+        if (h->general && reset_pid) HIP_TRY(h, reset_block(h, K.reset_pid));
+        if (h->hold64 && reset_pid) HIP_TRY(h, reset_block64(h, K.reset_pid));
+      }
+      h->mode = K.mode;
+    }
+    c.pending = c.masked = false;
+    c.have = true;
+  }
+  for (CmdChannel& c : h->cmd) c.sched_rows = nullptr;
+  // What is now the PENDING buffer of a touched kind was last used by the work queued on the compute stream so far: the next
+  // host batch of that kind, which travels on the copy stream, may overwrite it only once that work is through.  The event is
+  // recorded on EVERY such latch once a copy stream exists, however the latched command itself arrived (host, _device or
+  // masked): a stale event from an earlier host batch would let the copy run into launches that still read the buffer.  Bound
+  // commands swap nothing and handles that never saw a host batch have no copy stream: no event, no device time.
+  for (int k = 0; k < kCmdKinds; ++k) {
+    CmdChannel& c = h->cmd[k];
+    if (!touched[k] || !h->copy_stream) continue;
+    if (!c.free_ev) HIP_TRY(h, hipEventCreateWithFlags(&c.free_ev, hipEventDisableTiming));
+    HIP_TRY(h, hipEventRecord(c.free_ev, h->stream));
+    c.free_ev_set = true;
+  }
+  return CDPR_OK;
+}
+
 int run_steps(cdpr_engine* h, int nsteps, int per_launch, float4* record = nullptr) {
   if (!h) return CDPR_ERR_INVALID;
   if (nsteps < 0 || per_launch < 1 || (per_launch > 64 && !h->sched_refresh)) {
@@ -586,179 +722,8 @@ int run_steps(cdpr_engine* h, int nsteps, int per_launch, float4* record = nullp
   if (nsteps == 0) return CDPR_OK;
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
 
-  // --- PLG.cpp:206-219: latch pending commands, velocity first, then position
-  const bool latch_kind[3] = {h->vel_pending, h->pos_pending, h->frc_pending};
-  for (int k = 0; k < 3; ++k) {
-    if (latch_kind[k] && h->ready_wait[k]) {  // a host Joy batch is (or was) on its way on the copy stream
-      HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ready_wait[k], 0));
-      h->ready_wait[k] = nullptr;
-    }
-  }
-  // After the latch below, what is then the PENDING buffer of a kind whose buffers were swapped (or, on per-robot handles,
-  // read by the latch kernel) was last touched by the work queued on the compute stream so far: the next host batch of
-  // that kind, which travels on the copy stream, may overwrite it only once that work is through.  The event is recorded
-  // on EVERY such latch once a copy stream exists, however the latched command itself arrived (host, _device or masked):
-  // a stale event from an earlier host batch would let the copy run into launches that still read the buffer.  Bound
-  // commands swap nothing and handles that never saw a host batch have no copy stream: no event, no device time.
-  bool touched[3] = {false, false, false};
-  auto mark_free = [&]() -> int {
-    for (int k = 0; k < 3; ++k) {
-      if (!touched[k] || !h->copy_stream) continue;
-      if (!h->free_ev[k]) HIP_TRY(h, hipEventCreateWithFlags(&h->free_ev[k], hipEventDisableTiming));
-      HIP_TRY(h, hipEventRecord(h->free_ev[k], h->stream));
-      h->free_ev_set[k] = true;
-    }
-    return CDPR_OK;
-  };
   bool reset_pid = false;
-  auto flush_hot = [&]() {  // the general path's hot rows back into the H slots (cdpr_gen_flush_hot_kernel) before a Pid's records are reset
-    if (!h->d_rec || !h->gen_hot) return;
-    GenFlushArgs fa{};
-    fa.rec = h->d_rec, fa.rstride = h->stride, fa.batch = h->batch, fa.lay = h->glay, fa.nbuf = std::max(h->gpid[0].nbuf, 1);
-    hipLaunchKernelGGL(cdpr_gen_flush_hot_kernel, dim3((h->batch + 255u) / 256u), dim3(256), 0, h->stream, fa);
-  };
-  auto reset_block = [&](int which) -> hipError_t {  // Pid::reset of one Pid of every cable (general path): its slots, its rows
-    const GenLayout& L = h->glay;
-    flush_hot();
-    hipError_t e1 = hipMemsetAsync(h->d_rec + (size_t)L.block_a(which, 0) * h->stride * 4, 0, (size_t)L.pid_slots() * h->stride * 16, h->stream);
-    if (e1 != hipSuccess || L.pid_rows() == 0) return e1;
-    return hipMemsetAsync(h->d_rec + ((size_t)L.slots() * 4 + (size_t)L.block_b(which, 0)) * h->stride, 0, (size_t)L.pid_rows() * h->stride * 4, h->stream);
-  };
-  auto reset_block64 = [&](int which) -> hipError_t {  // precision = 64 with the hold branch: Pid::reset of one Pid of every cable (its rows behind the state)
-    for (uint32_t i = 0; i < h->n; ++i) {
-      hipError_t e1 = hipMemsetAsync(h->d_state64 + (size_t)f64_hold_row((int)h->n, (int)i, which, h->hold_win) * h->stride, 0, (size_t)hold_pid_rows(h->hold_win) * h->stride * sizeof(double),
-                                     h->stream);
-      if (e1 != hipSuccess) return e1;
-    }
-    return hipSuccess;
-  };
-  if (h->per_robot) {
-    // every robot has its own mode: commands (masked or not) are latched on the device, robot by robot
-    auto latch = [&](float* pending, float* latched, const uint8_t* mask, int which, int new_mode) -> int {
-      if (h->fp64) {  // precision = 64: the same on the double state (integral rows 20 + 11 i + 10)
-        LatchF64Args lf{};
-        lf.mask = mask;
-        lf.meta = h->d_mode;
-        lf.pending = pending;
-        lf.target = h->d_target;
-        lf.state = h->d_state64;
-        lf.stride = h->stride;
-        lf.batch = h->batch;
-        lf.n = h->n;
-        lf.new_mode = (new_mode == kModeVelocity) ? kMetaVelocity : (new_mode == kModePosition) ? kMetaPosition : kMetaForce;
-        lf.hold = h->hold64 ? 1u : 0u;
-        lf.win = (uint32_t)h->win64;
-        lf.hold_win = (uint32_t)h->hold_win;
-        hipLaunchKernelGGL(cdpr_latch_f64_kernel, dim3((h->batch + 255u) / 256u), dim3(256), 0, h->stream, lf);
-        HIP_TRY(h, hipGetLastError());
-        return CDPR_OK;
-      }
-      if (!h->general) {  // register-resident path: one active target row and one Pid record per robot
-        LatchFastArgs lf{};
-        lf.mask = mask;
-        lf.meta = h->d_mode;
-        lf.pending = pending;
-        lf.target = h->d_target;
-        lf.hot = h->d_state + (size_t)(plat_slots(h->fk) + 5 * cable_pairs((int)h->n)) * h->stride;
-        lf.stride = h->stride;
-        lf.batch = h->batch;
-        lf.n = h->n;
-        lf.hot_rows = (uint32_t)((cable_pairs((int)h->n) + 1) / 2);
-        lf.new_mode = (new_mode == kModeVelocity) ? kMetaVelocity : (new_mode == kModePosition) ? kMetaPosition : kMetaForce;
-        hipLaunchKernelGGL(cdpr_latch_fast_kernel, dim3((h->batch + 255u) / 256u), dim3(256), 0, h->stream, lf);
-        HIP_TRY(h, hipGetLastError());
-        return CDPR_OK;
-      }
-      flush_hot();
-      GenLatchArgs la{};
-      la.mask = mask;
-      la.mode = h->d_mode;
-      la.pending = pending;
-      la.latched = latched;
-      la.rec = h->d_rec;
-      la.rstride = h->stride;
-      la.batch = h->batch;
-      la.n = h->n;
-      la.reset_pid = which;  // (-1: setForce resets no Pid)
-      la.lay = h->glay;
-      la.new_mode = new_mode;
-      hipLaunchKernelGGL(cdpr_gen_latch_kernel, dim3((h->batch + 255u) / 256u), dim3(256), 0, h->stream, la);
-      HIP_TRY(h, hipGetLastError());
-      return CDPR_OK;
-    };
-    // (a batch of a device-resident schedule, cdpr_update_scheduled_kind, is latched from the caller's buffers in place)
-    auto rows_of = [&](int kind, float* pending) -> float* { return h->sched_rows[kind] ? const_cast<float*>(h->sched_rows[kind]) : pending; };
-    auto mask_of = [&](int kind, bool masked) -> const uint8_t* { return h->sched_rows[kind] ? h->sched_mask[kind] : (masked ? h->d_mask[kind] : nullptr); };
-    if (h->vel_pending) {
-      if (int rc = latch(rows_of(0, h->d_vel[1]), h->d_vel[0], mask_of(0, h->vel_masked), 1, kModeVelocity)) return rc;
-      h->vel_pending = h->vel_masked = false;
-      h->have_vel = true;
-      touched[0] = !h->sched_rows[0];  // the latch kernel reads the pending buffer
-    }
-    if (h->pos_pending) {
-      if (int rc = latch(rows_of(1, h->d_pos[1]), h->d_pos[0], mask_of(1, h->pos_masked), 0, kModePosition)) return rc;
-      h->pos_pending = h->pos_masked = false;
-      h->have_pos = true;
-      touched[1] = !h->sched_rows[1];
-    }
-    if (h->frc_pending) {  // [NEW] ordering: after the two Joy topics (the reference has no force callback)
-      if (int rc = latch(rows_of(2, h->d_frc[1]), h->d_frc[0], mask_of(2, h->frc_masked), -1, kModeForce)) return rc;
-      h->frc_pending = h->frc_masked = false;
-      h->have_frc = true;
-      touched[2] = !h->sched_rows[2];
-    }
-    h->sched_rows[0] = h->sched_rows[1] = h->sched_rows[2] = nullptr;
-    if (int rc = mark_free()) return rc;
-    touched[0] = touched[1] = touched[2] = false;  // recorded; nothing below latches on a per-robot handle
-    if (h->general) return run_steps_general(h, nsteps, per_launch, record);
-    if (h->fp64) return run_steps_f64(h, nsteps, per_launch, false, reinterpret_cast<double*>(record));
-  }
-  if (h->vel_pending) {
-    if (h->ext_vel[1]) {  // bound caller buffer: latched by pointer, nothing copied
-      h->ext_vel[0] = h->ext_vel[1];
-      h->ext_vel[1] = nullptr;
-    } else {
-      std::swap(h->d_vel[0], h->d_vel[1]);
-      h->ext_vel[0] = nullptr;
-      touched[0] = true;  // what is pending now was the latched buffer of the launches queued so far
-    }
-    h->vel_pending = false;
-    h->have_vel = true;
-    reset_pid = (h->mode != kModeVelocity);  // JFC.cpp:113-115
-    if (h->general && reset_pid) HIP_TRY(h, reset_block(1));
-    if (h->hold64 && reset_pid) HIP_TRY(h, reset_block64(1));
-    h->mode = kModeVelocity;
-  }
-  if (h->pos_pending) {
-    if (h->ext_pos[1]) {
-      h->ext_pos[0] = h->ext_pos[1];
-      h->ext_pos[1] = nullptr;
-    } else {
-      std::swap(h->d_pos[0], h->d_pos[1]);
-      h->ext_pos[0] = nullptr;
-      touched[1] = true;
-    }
-    h->pos_pending = false;
-    h->have_pos = true;
-    reset_pid = (h->mode != kModePosition);  // JFC.cpp:101-103 (fast path: the single record now belongs to the position Pid)
-    if (h->general && reset_pid) HIP_TRY(h, reset_block(0));
-    if (h->hold64 && reset_pid) HIP_TRY(h, reset_block64(0));
-    h->mode = kModePosition;
-  }
-  if (h->frc_pending) {  // setForce (JFC.h:92-95): mode Force, no Pid is reset.  [NEW] ordering: after the two Joy topics
-    if (h->ext_frc[1]) {
-      h->ext_frc[0] = h->ext_frc[1];
-      h->ext_frc[1] = nullptr;
-    } else {
-      std::swap(h->d_frc[0], h->d_frc[1]);
-      h->ext_frc[0] = nullptr;
-      touched[2] = true;
-    }
-    h->frc_pending = false;
-    h->have_frc = true;
-    h->mode = kModeForce;
-  }
-  if (int rc = mark_free()) return rc;
+  if (int rc = latch_pending(h, reset_pid)) return rc;
   if (h->general) return run_steps_general(h, nsteps, per_launch, record);
   if (h->fp64) return run_steps_f64(h, nsteps, per_launch, reset_pid, reinterpret_cast<double*>(record));
 
@@ -782,15 +747,9 @@ int run_steps(cdpr_engine* h, int nsteps, int per_launch, float4* record = nullp
     copy_pid_alt(h->pid_pos, a.alt);
     a.cmd = h->d_target;
     a.meta = h->d_mode;
-  } else if (h->mode == kModeVelocity) {
-    copy_pid(h->pid_vel, a);
-    a.cmd = h->ext_vel[0] ? h->ext_vel[0] : h->d_vel[0];
-  } else if (h->mode == kModeForce) {
-    copy_pid(h->pid_pos, a);  // unused: no Pid runs in Force mode
-    a.cmd = h->ext_frc[0] ? h->ext_frc[0] : h->d_frc[0];
   } else {
-    copy_pid(h->pid_pos, a);
-    a.cmd = h->ext_pos[0] ? h->ext_pos[0] : h->d_pos[0];  // all zeros until the first jointPositions message: target 0 (PLG.cpp:153-157)
+    copy_pid(h->mode == kModeVelocity ? h->pid_vel : h->pid_pos, a);  // (Force mode: unused, no Pid runs)
+    a.cmd = h->cmd[cmd_kind_of_mode(h->mode)].latched();  // position: all zeros until the first jointPositions message: target 0 (PLG.cpp:153-157)
   }
   const uint32_t robots_per_block = h->lane_cable ? (h->n <= 4 ? 16u : 8u) : h->lane_pair ? 32u : 64u;
   const dim3 grid((h->batch + robots_per_block - 1u) / robots_per_block);
@@ -890,13 +849,7 @@ int run_steps(cdpr_engine* h, int nsteps, int per_launch, float4* record = nullp
       a.fault = h->d_fault;
       h->prev_publish = sim_time(h->step + (uint64_t)k - 1, h->cfg.dt);
     } else {
-      for (int j = 0; j < k; ++j) {  // PLG.cpp:236-242: strict '>' against the last published stamp
-        const double now = sim_time(h->step + (uint64_t)j, h->cfg.dt);
-        if ((now - h->prev_publish) > h->cfg.publish_period) {
-          h->prev_publish = now;
-          a.publish_mask |= (1ull << j);
-        }
-      }
+      a.publish_mask = publish_mask(h, k);
     }
     launch_step(h, kern, robots_per_block, block, a, (h->persist && k == 1 && !h->per_robot) ? h->persist_grid : 0u);
     HIP_TRY(h, hipGetLastError());
@@ -1189,14 +1142,11 @@ int cdpr_create(const cdpr_config_t* cfg, int device, cdpr_handle_t* out) {
     if ((e = hipMalloc(&h->d_obs, slot_bytes * h->n_obs)) != hipSuccess) return fail("hipMalloc(obs)", e);
   }
   const size_t cmd_bytes = (size_t)h->stride * h->n * sizeof(float);
-  for (int i = 0; i < 2; ++i) {
-    if ((e = hipMalloc(&h->d_vel[i], cmd_bytes)) != hipSuccess) return fail("hipMalloc(cmd)", e);
-    if ((e = hipMalloc(&h->d_pos[i], cmd_bytes)) != hipSuccess) return fail("hipMalloc(cmd)", e);
-    if ((e = hipMalloc(&h->d_frc[i], cmd_bytes)) != hipSuccess) return fail("hipMalloc(cmd)", e);
-    (void)hipMemset(h->d_vel[i], 0, cmd_bytes);
-    (void)hipMemset(h->d_pos[i], 0, cmd_bytes);
-    (void)hipMemset(h->d_frc[i], 0, cmd_bytes);
-  }
+  for (int i = 0; i < 2; ++i)
+    for (CmdChannel& c : h->cmd) {
+      if ((e = hipMalloc(&c.d[i], cmd_bytes)) != hipSuccess) return fail("hipMalloc(cmd)", e);
+      (void)hipMemset(c.d[i], 0, cmd_bytes);
+    }
   if ((e = hipMalloc(&h->d_wtab, sizeof wtab_host)) != hipSuccess) return fail("hipMalloc(wtab)", e);
   if ((e = hipMemcpy(h->d_wtab, wtab_host, sizeof wtab_host, hipMemcpyHostToDevice)) != hipSuccess) return fail("hipMemcpy(wtab)", e);
   h->pid_vel.wtab = h->d_wtab;
@@ -1248,8 +1198,8 @@ int cdpr_create(const cdpr_config_t* cfg, int device, cdpr_handle_t* out) {
   if (h->per_robot) {
     if (!h->general && (e = hipMalloc(&h->d_target, cmd_bytes)) != hipSuccess) return fail("hipMalloc(target)", e);
     if ((e = hipMalloc(&h->d_mode, h->batch)) != hipSuccess) return fail("hipMalloc(mode)", e);
-    for (int i = 0; i < 3; ++i)
-      if ((e = hipMalloc(&h->d_mask[i], h->batch)) != hipSuccess) return fail("hipMalloc(mask)", e);
+    for (CmdChannel& c : h->cmd)
+      if ((e = hipMalloc(&c.d_mask, h->batch)) != hipSuccess) return fail("hipMalloc(mask)", e);
   }
   if (h->dbg && !h->fp64)
     if ((e = hipMalloc(&h->d_dbg, (size_t)h->batch * CDPR_PID_DEBUG_AXES * sizeof(float))) != hipSuccess)
@@ -1275,7 +1225,7 @@ int cdpr_reset(cdpr_handle_t h) {
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
   if (int rc = drain_copy_stream(h)) return rc;
   HIP_TRY(h, wait_stream(h));
-  h->free_ev_set[0] = h->free_ev_set[1] = h->free_ev_set[2] = false;
+  for (CmdChannel& c : h->cmd) c.free_ev_set = false;
   engine_reset_host(h);
   return upload_home(h);
 }
@@ -1316,7 +1266,12 @@ int cdpr_set_platform_state(cdpr_handle_t h, const float* pose7, const float* tw
 // A pending command replaces the one before it (PLG.cpp:69,78: the callback overwrites the stored message); on a
 // per-robot handle an UNMASKED command after a masked one would have to merge with it, which the callbacks of
 // independent plugins never need: the later call wins for the robots it addresses, the earlier one keeps the rest.
-static int stage_masked(cdpr_engine* h, int which, const float* axes, size_t count, const uint8_t* robot_mask) {
+static int stage_masked(cdpr_engine* h, int kind, const float* axes, size_t count, const uint8_t* robot_mask) {
+  if (!h) return CDPR_ERR_INVALID;
+  if (!axes) {
+    h->err = "null command buffer";
+    return CDPR_ERR_INVALID;
+  }
   if (!h->per_robot) {
     h->err = "masked commands need a handle created with per_robot_commands = 1";
     return CDPR_ERR_UNSUPPORTED;
@@ -1329,16 +1284,14 @@ static int stage_masked(cdpr_engine* h, int which, const float* axes, size_t cou
   if (count != n * B && count != n) return CDPR_IGNORED;  // PLG.cpp:68-73,77-82
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
   if (int rc = drain_copy_stream(h)) return rc;
-  float* pending = which == 0 ? h->d_vel[1] : which == 1 ? h->d_pos[1] : h->d_frc[1];
-  bool& is_pending = which == 0 ? h->vel_pending : which == 1 ? h->pos_pending : h->frc_pending;
-  bool& masked = which == 0 ? h->vel_masked : which == 1 ? h->pos_masked : h->frc_masked;
+  CmdChannel& c = h->cmd[kind];
   // merge with a command of the same kind that is already pending: rows and mask bits of the robots addressed now
   std::vector<float> rows(n * B);
   std::vector<uint8_t> mask(B, 0);
-  if (is_pending) {
-    HIP_TRY(h, hipMemcpyAsync(rows.data(), pending, n * B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (masked)
-      HIP_TRY(h, hipMemcpyAsync(mask.data(), h->d_mask[which], B, hipMemcpyDeviceToHost, h->stream));
+  if (c.pending) {
+    HIP_TRY(h, hipMemcpyAsync(rows.data(), c.d[1], n * B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (c.masked)
+      HIP_TRY(h, hipMemcpyAsync(mask.data(), c.d_mask, B, hipMemcpyDeviceToHost, h->stream));
     else
       std::fill(mask.begin(), mask.end(), (uint8_t)1);
     HIP_TRY(h, wait_stream(h));
@@ -1348,110 +1301,31 @@ static int stage_masked(cdpr_engine* h, int which, const float* axes, size_t cou
     mask[b] = 1;
     memcpy(&rows[b * n], count == n ? axes : axes + b * n, n * sizeof(float));
   }
-  HIP_TRY(h, hipMemcpyAsync(pending, rows.data(), n * B * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(h->d_mask[which], mask.data(), B, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(c.d[1], rows.data(), n * B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(c.d_mask, mask.data(), B, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, wait_stream(h));
-  is_pending = true;
-  masked = true;
+  c.pending = true;
+  c.masked = true;
   return CDPR_OK;
 }
 
-int cdpr_set_velocity_command(cdpr_handle_t h, const float* axes, size_t count) {
+// The unmasked setters, host or device source: the rows replace whatever of that kind was pending, a bound buffer included.
+static int set_command(cdpr_engine* h, int kind, const float* axes, size_t count, bool from_device) {
   if (!h) return CDPR_ERR_INVALID;
-  int rc = stage_command(h, h->d_vel[1], axes, count, false);
+  const int rc = stage_command(h, kind, axes, count, from_device);
   if (rc == CDPR_OK) {
-    h->vel_pending = true;
-    h->vel_masked = false;
-    h->ext_vel[1] = nullptr;
-  }
-  return rc;
-}
-
-int cdpr_set_position_command(cdpr_handle_t h, const float* axes, size_t count) {
-  if (!h) return CDPR_ERR_INVALID;
-  int rc = stage_command(h, h->d_pos[1], axes, count, false);
-  if (rc == CDPR_OK) {
-    h->pos_pending = true;
-    h->pos_masked = false;
-    h->ext_pos[1] = nullptr;
-  }
-  return rc;
-}
-
-int cdpr_set_force_command(cdpr_handle_t h, const float* axes, size_t count) {
-  if (!h) return CDPR_ERR_INVALID;
-  int rc = stage_command(h, h->d_frc[1], axes, count, false);
-  if (rc == CDPR_OK) {
-    h->frc_pending = true;
-    h->frc_masked = false;
-    h->ext_frc[1] = nullptr;
-  }
-  return rc;
-}
-
-int cdpr_set_force_command_device(cdpr_handle_t h, const float* d_axes, size_t count) {
-  if (!h) return CDPR_ERR_INVALID;
-  int rc = stage_command(h, h->d_frc[1], d_axes, count, true);
-  if (rc == CDPR_OK) {
-    h->frc_pending = true;
-    h->frc_masked = false;
-    h->ext_frc[1] = nullptr;
-  }
-  return rc;
-}
-
-int cdpr_set_force_command_masked(cdpr_handle_t h, const float* axes, size_t count, const uint8_t* robot_mask) {
-  if (!h) return CDPR_ERR_INVALID;
-  if (!axes) {
-    h->err = "null command buffer";
-    return CDPR_ERR_INVALID;
-  }
-  return stage_masked(h, 2, axes, count, robot_mask);
-}
-
-int cdpr_set_velocity_command_masked(cdpr_handle_t h, const float* axes, size_t count, const uint8_t* robot_mask) {
-  if (!h) return CDPR_ERR_INVALID;
-  if (!axes) {
-    h->err = "null command buffer";
-    return CDPR_ERR_INVALID;
-  }
-  return stage_masked(h, 0, axes, count, robot_mask);
-}
-
-int cdpr_set_position_command_masked(cdpr_handle_t h, const float* axes, size_t count, const uint8_t* robot_mask) {
-  if (!h) return CDPR_ERR_INVALID;
-  if (!axes) {
-    h->err = "null command buffer";
-    return CDPR_ERR_INVALID;
-  }
-  return stage_masked(h, 1, axes, count, robot_mask);
-}
-
-int cdpr_set_velocity_command_device(cdpr_handle_t h, const float* d_axes, size_t count) {
-  if (!h) return CDPR_ERR_INVALID;
-  int rc = stage_command(h, h->d_vel[1], d_axes, count, true);
-  if (rc == CDPR_OK) {
-    h->vel_pending = true;
-    h->vel_masked = false;
-    h->ext_vel[1] = nullptr;
-  }
-  return rc;
-}
-
-int cdpr_set_position_command_device(cdpr_handle_t h, const float* d_axes, size_t count) {
-  if (!h) return CDPR_ERR_INVALID;
-  int rc = stage_command(h, h->d_pos[1], d_axes, count, true);
-  if (rc == CDPR_OK) {
-    h->pos_pending = true;
-    h->pos_masked = false;
-    h->ext_pos[1] = nullptr;
+    CmdChannel& c = h->cmd[kind];
+    c.pending = true;
+    c.masked = false;
+    c.ext[1] = nullptr;
   }
   return rc;
 }
 
 // Zero-copy form: the caller's device buffer float[B][n] IS the latched Joy batch from the next update on (no copy, no
 // synchronisation); it must stay valid and unchanged until another command of the same kind has been latched.
-static int bind_command(cdpr_engine* h, int which, const float* d_axes, size_t count) {
+static int bind_command(cdpr_engine* h, int kind, const float* d_axes, size_t count) {
+  if (!h) return CDPR_ERR_INVALID;
   if (!d_axes) {
     h->err = "null command buffer";
     return CDPR_ERR_INVALID;
@@ -1461,30 +1335,32 @@ static int bind_command(cdpr_engine* h, int which, const float* d_axes, size_t c
     h->err = "cdpr_bind_*_command_device: not available on a per_robot_commands handle (commands are latched robot by robot)";
     return CDPR_ERR_UNSUPPORTED;
   }
-  if (which == 0) {
-    h->ext_vel[1] = d_axes;
-    h->vel_pending = true;
-  } else if (which == 1) {
-    h->ext_pos[1] = d_axes;
-    h->pos_pending = true;
-  } else {
-    h->ext_frc[1] = d_axes;
-    h->frc_pending = true;
-  }
+  h->cmd[kind].ext[1] = d_axes;
+  h->cmd[kind].pending = true;
   return CDPR_OK;
 }
 
-int cdpr_bind_force_command_device(cdpr_handle_t h, const float* d_axes, size_t count) {
-  return h ? bind_command(h, 2, d_axes, count) : CDPR_ERR_INVALID;
+int cdpr_set_velocity_command(cdpr_handle_t h, const float* axes, size_t count) { return set_command(h, CDPR_COMMAND_VELOCITY, axes, count, false); }
+int cdpr_set_position_command(cdpr_handle_t h, const float* axes, size_t count) { return set_command(h, CDPR_COMMAND_POSITION, axes, count, false); }
+int cdpr_set_force_command(cdpr_handle_t h, const float* axes, size_t count) { return set_command(h, CDPR_COMMAND_FORCE, axes, count, false); }
+
+int cdpr_set_velocity_command_device(cdpr_handle_t h, const float* d_axes, size_t count) { return set_command(h, CDPR_COMMAND_VELOCITY, d_axes, count, true); }
+int cdpr_set_position_command_device(cdpr_handle_t h, const float* d_axes, size_t count) { return set_command(h, CDPR_COMMAND_POSITION, d_axes, count, true); }
+int cdpr_set_force_command_device(cdpr_handle_t h, const float* d_axes, size_t count) { return set_command(h, CDPR_COMMAND_FORCE, d_axes, count, true); }
+
+int cdpr_set_velocity_command_masked(cdpr_handle_t h, const float* axes, size_t count, const uint8_t* robot_mask) {
+  return stage_masked(h, CDPR_COMMAND_VELOCITY, axes, count, robot_mask);
+}
+int cdpr_set_position_command_masked(cdpr_handle_t h, const float* axes, size_t count, const uint8_t* robot_mask) {
+  return stage_masked(h, CDPR_COMMAND_POSITION, axes, count, robot_mask);
+}
+int cdpr_set_force_command_masked(cdpr_handle_t h, const float* axes, size_t count, const uint8_t* robot_mask) {
+  return stage_masked(h, CDPR_COMMAND_FORCE, axes, count, robot_mask);
 }
 
-int cdpr_bind_velocity_command_device(cdpr_handle_t h, const float* d_axes, size_t count) {
-  return h ? bind_command(h, 0, d_axes, count) : CDPR_ERR_INVALID;
-}
-
-int cdpr_bind_position_command_device(cdpr_handle_t h, const float* d_axes, size_t count) {
-  return h ? bind_command(h, 1, d_axes, count) : CDPR_ERR_INVALID;
-}
+int cdpr_bind_velocity_command_device(cdpr_handle_t h, const float* d_axes, size_t count) { return bind_command(h, CDPR_COMMAND_VELOCITY, d_axes, count); }
+int cdpr_bind_position_command_device(cdpr_handle_t h, const float* d_axes, size_t count) { return bind_command(h, CDPR_COMMAND_POSITION, d_axes, count); }
+int cdpr_bind_force_command_device(cdpr_handle_t h, const float* d_axes, size_t count) { return bind_command(h, CDPR_COMMAND_FORCE, d_axes, count); }
 
 int cdpr_update(cdpr_handle_t h, int nsteps) { return run_steps(h, nsteps, 1); }
 
@@ -1558,48 +1434,46 @@ static int scheduled_update(cdpr_engine* h, uint32_t kind, int nsteps, int refre
   }
   float4* const record = static_cast<float4*>(d_record);
   const size_t batch_floats = (size_t)h->batch * h->n;
-  bool* pending[3] = {&h->vel_pending, &h->pos_pending, &h->frc_pending};
-  bool* masked[3] = {&h->vel_masked, &h->pos_masked, &h->frc_masked};
-  const float** ext[3] = {h->ext_vel, h->ext_pos, h->ext_frc};
+  CmdChannel& c = h->cmd[kind];
   const int nbatches = (nsteps + refresh_steps - 1) / refresh_steps;
   // batch j becomes the pending command of `kind`, in place
   auto stage_batch = [&](int j) {
     const float* rows = d_commands + (size_t)j * batch_floats;
     if (h->per_robot) {
-      h->sched_rows[kind] = rows;
-      h->sched_mask[kind] = d_masks ? d_masks + (size_t)j * h->batch : nullptr;
+      c.sched_rows = rows;
+      c.sched_mask = d_masks ? d_masks + (size_t)j * h->batch : nullptr;
     } else {
-      ext[kind][1] = rows;
+      c.ext[1] = rows;
     }
-    *pending[kind] = true;
-    *masked[kind] = false;
+    c.pending = true;
+    c.masked = false;
   };
   // Per-robot handles: a command of the SAME kind still pending at the call (cdpr_set_*_command[_masked] without an update since)
   // would have to reach its robots before batch 0 reaches batch 0's - B independent plugins each keep the last message that
   // reached THEM.  Staging batch 0 would overwrite it silently: refused, the caller latches it with cdpr_update first
   // or leaves it out.  (Uniform handles: the later message of a kind replaces the earlier one, as in the plugin, PLG.cpp:67-83.)
-  if (h->per_robot && *pending[kind]) {
+  if (h->per_robot && c.pending) {
     h->err = "cdpr_update_scheduled_kind: a command of the same kind is still pending on this per-robot handle; step it in with cdpr_update first";
     return CDPR_ERR_INVALID;
   }
   // whatever way this function is left, nothing of the caller's schedule stays staged in the handle: an error return must not
   // leave `pending` set on pointers the caller may free, nor the schedule fields set for the next plain cdpr_update
   struct Unstage {
-    cdpr_engine* h; uint32_t kind; bool* pend; const float** ext; bool ok = false;
+    cdpr_engine* h; CmdChannel& c; bool ok = false;
     ~Unstage() {
-      h->sched_rows[kind] = nullptr;
-      h->sched_mask[kind] = nullptr;
+      c.sched_rows = nullptr;
+      c.sched_mask = nullptr;
       h->sched_refresh = 0;
       h->sched_ready = nullptr;
       if (!ok) {  // an error in between: drop the batch that was staged but not latched
-        if (*pend && (h->per_robot || ext[1])) *pend = false;
-        ext[1] = nullptr;
+        if (c.pending && (h->per_robot || c.ext[1])) c.pending = false;
+        c.ext[1] = nullptr;
       }
     }
-  } unstage{h, kind, pending[kind], ext[kind]};
+  } unstage{h, c};
   const bool in_launch = !(h->general || h->fp64 || h->per_robot || h->lane_cable) && h->cfg.publish_period == 0.0;
   bool others = false;
-  for (uint32_t k = 0; k < 3; ++k) others = others || (k != kind && *pending[k]);
+  for (uint32_t k = 0; k < (uint32_t)kCmdKinds; ++k) others = others || (k != kind && h->cmd[k].pending);
   int j = 0, done = 0;
   // ---- the chain: every batch of a handle the launch form does not serve; batch 0 where another command is pending
   const int chain_spl = ((size_t)h->batch * h->n <= 131072u) ? std::min(refresh_steps, 64) : 1;  // small batches: the hold in one launch
@@ -1637,7 +1511,7 @@ static int scheduled_update(cdpr_engine* h, uint32_t kind, int nsteps, int refre
     if (rc != CDPR_OK) return rc;
     done += rest;
     j += (rest + refresh_steps - 1) / refresh_steps;
-    if (j >= nbatches) ext[kind][0] = d_commands + (size_t)(nbatches - 1) * batch_floats;  // the batch that stays latched
+    if (j >= nbatches) c.ext[0] = d_commands + (size_t)(nbatches - 1) * batch_floats;  // the batch that stays latched
   }
   unstage.ok = true;
   return CDPR_OK;

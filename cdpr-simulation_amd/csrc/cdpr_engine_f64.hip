@@ -22,11 +22,8 @@ int upload_home64(cdpr_engine* h) {
   if (h->d_dbg64) HIP_TRY(h, hipMemsetAsync(h->d_dbg64, 0, (size_t)h->batch * CDPR_PID_DEBUG_AXES * sizeof(double), h->stream));
   if (h->d_mode) HIP_TRY(h, hipMemsetAsync(h->d_mode, kModePosition, h->batch, h->stream));  // PLG.cpp:153-157 (call count 0)
   if (h->d_target) HIP_TRY(h, hipMemsetAsync(h->d_target, 0, (size_t)h->stride * h->n * sizeof(float), h->stream));
-  for (int i = 0; i < 2; ++i) {
-    HIP_TRY(h, hipMemsetAsync(h->d_vel[i], 0, (size_t)h->stride * h->n * sizeof(float), h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_pos[i], 0, (size_t)h->stride * h->n * sizeof(float), h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_frc[i], 0, (size_t)h->stride * h->n * sizeof(float), h->stream));
-  }
+  for (int i = 0; i < 2; ++i)
+    for (CmdChannel& c : h->cmd) HIP_TRY(h, hipMemsetAsync(c.d[i], 0, (size_t)h->stride * h->n * sizeof(float), h->stream));
   HIP_TRY(h, wait_stream(h));
   return CDPR_OK;
 }
@@ -45,9 +42,7 @@ void fill_pid64(const cdpr_pid_params_t& p, double dt, F64Args& k) {
 static void f64_mode_args(const cdpr_engine* h, bool vel, bool frc, F64Args& a) {
   const bool pr = h->per_robot;
   fill_pid64(vel ? h->cfg.velocity_pid : h->cfg.position_pid, h->cfg.dt, a);
-  a.cmd = pr ? h->d_target
-             : frc ? (h->ext_frc[0] ? h->ext_frc[0] : h->d_frc[0])
-                   : vel ? (h->ext_vel[0] ? h->ext_vel[0] : h->d_vel[0]) : (h->ext_pos[0] ? h->ext_pos[0] : h->d_pos[0]);
+  a.cmd = pr ? h->d_target : h->cmd[frc ? CDPR_COMMAND_FORCE : vel ? CDPR_COMMAND_VELOCITY : CDPR_COMMAND_POSITION].latched();
   a.wtab = h->d_wtab64 + (vel ? 0 : h->win64 * (h->win64 + 2));
   if (pr) {  // mode, Pid call count and so the Pid per lane: the velocity Pid in the primary fields, the position Pid in alt_*
     F64Args p = h->base64;
@@ -157,14 +152,7 @@ int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, do
     a.pid_calls = sat_pid_calls(h->pid_calls);
     a.ring_slot = ring_slot_of(h->step, h->win64);
     a.step0 = (int)h->step;
-    a.publish_mask = 0;
-    for (int j = 0; j < k; ++j) {  // PLG.cpp:236-242: strict '>' against the last published stamp
-      const double now = sim_time(h->step + (uint64_t)j, h->cfg.dt);
-      if ((now - h->prev_publish) > h->cfg.publish_period) {
-        h->prev_publish = now;
-        a.publish_mask |= (1ull << j);
-      }
-    }
+    a.publish_mask = publish_mask(h, k);
     if (k == 1 && split_kern) {
       hipLaunchKernelGGL(split_kern, dim3((h->batch + 63u) / 64u), dim3(128), 0, h->stream, a);
       h->last_kernel = pk1;

@@ -37,6 +37,48 @@ enum Mode { kModeForce = 0, kModePosition = 1, kModeVelocity = 2 };  // JFC.h:35
     }                                                                                            \
   } while (0)
 
+// Everything one command kind owns.  The handle keeps one record per kind, cdpr_engine::cmd[], indexed by the ABI's
+// CDPR_COMMAND_VELOCITY / _POSITION / _FORCE (0, 1, 2); what differs between the kinds is kCmdKind below.
+struct CmdChannel {
+  float* d[2] = {nullptr, nullptr};          // the engine's own device buffers: [0] latched, [1] pending
+  // zero-copy commands (cdpr_bind_*_command_device): a caller-owned device buffer takes the place of d[0] / d[1]
+  const float* ext[2] = {nullptr, nullptr};
+  uint8_t* d_mask = nullptr;                 // per-robot handles: the pending command's mask, uint8[B]
+  bool pending = false;
+  bool masked = false;                       // the pending command came with a mask
+  bool have = false;                         // a command of this kind has been latched since Load
+  // Host-side Joy batches travel on their own stream (cdpr_set_*_command with a host pointer): the caller's rows go into
+  // one of two pinned staging buffers and from there to the PENDING device buffer while earlier launches still
+  // run; the call returns without waiting.
+  float* h_stage[2] = {nullptr, nullptr};
+  hipEvent_t stage_ev[2] = {nullptr, nullptr};  // the copy out of that staging buffer has completed
+  bool stage_ev_set[2] = {false, false};
+  int stage_idx = 0;
+  hipEvent_t ready_wait = nullptr;  // event the compute stream has to pass before it touches the pending buffer
+  hipEvent_t free_ev = nullptr;     // every launch that read what is now the pending buffer has completed
+  bool free_ev_set = false;
+  // cdpr_update_scheduled_kind on a per-robot handle: batch j of the schedule is latched straight from the caller's device
+  // buffers (rows d_commands + j * B * n, mask d_robot_masks + j * B or nullptr = every robot), nothing staged
+  const float* sched_rows = nullptr;
+  const uint8_t* sched_mask = nullptr;
+
+  const float* latched() const { return ext[0] ? ext[0] : d[0]; }  // what the launches read: the bound buffer where one is latched
+};
+
+constexpr int kCmdKinds = 3;
+struct CmdKind {
+  int mode;        // the mode a latched command of this kind enters
+  int reset_pid;   // the Pid a CHANGE of mode resets (general path / hold rows: 0 = position, 1 = velocity), -1: none
+  uint32_t meta;   // the mode as the per-robot latch kernels take it (StepArgs::meta)
+};
+// in latch order: velocity, position (PLG.cpp:206-219), then force ([NEW]: the reference has no force callback)
+constexpr CmdKind kCmdKind[kCmdKinds] = {
+    {kModeVelocity, 1, kMetaVelocity},   // CDPR_COMMAND_VELOCITY: setVelocityTarget, JFC.cpp:113-115
+    {kModePosition, 0, kMetaPosition},   // CDPR_COMMAND_POSITION: setPositionTarget, JFC.cpp:101-103
+    {kModeForce, -1, kMetaForce},        // CDPR_COMMAND_FORCE: setForce, JFC.h:92-95 (no Pid is reset)
+};
+static_assert(CDPR_COMMAND_VELOCITY == 0 && CDPR_COMMAND_POSITION == 1 && CDPR_COMMAND_FORCE == 2, "kCmdKind is indexed by the ABI's command kinds");
+
 }  // namespace cdpr_host
 using namespace cdpr_host;
 
@@ -66,10 +108,6 @@ struct cdpr_engine {
   bool split = false;       // FK + TD one-step launches use cdpr_split_kernel (estimator wave + controller wave per 64 robots)
   int sched_refresh = 0;            // cdpr_update_scheduled in progress: Joy batches per launch (StepArgs::sched_*)
   const uint32_t* sched_ready = nullptr;
-  // cdpr_update_scheduled_kind on a per-robot handle: batch j of the schedule is latched straight from the caller's device
-  // buffers (rows d_commands + j * B * n, mask d_robot_masks + j * B or nullptr = every robot), nothing staged
-  const float* sched_rows[3] = {nullptr, nullptr, nullptr};
-  const uint8_t* sched_mask[3] = {nullptr, nullptr, nullptr};
   uint32_t* h_fault = nullptr;      // pinned, device-mapped status word: a schedule mailbox that never delivered (kernels OR bits into it)
   uint32_t* d_fault = nullptr;      // its device address
   uint32_t chunk = 0;       // > 0: a step over the batch is issued as back-to-back launches over contiguous blocks of at most
@@ -106,33 +144,13 @@ struct cdpr_engine {
   int cus = 256;
   bool use_graphs = true;
   bool pair_stream = true;  // cdpr_pair_stream_kernel serves the steady several-steps launches of lane-pair handles (CDPR_PAIR_STREAM=0: never; A/B and tests)
-  float* d_vel[2] = {nullptr, nullptr};  // [0] latched, [1] pending
-  float* d_pos[2] = {nullptr, nullptr};
-  float* d_frc[2] = {nullptr, nullptr};  // force commands (cdpr_set_force_command; JFC.h:92-95)
-  // zero-copy commands (cdpr_bind_*_command_device): a caller-owned device buffer takes the place of d_*[0] / d_*[1]
-  const float* ext_vel[2] = {nullptr, nullptr};
-  const float* ext_pos[2] = {nullptr, nullptr};
-  const float* ext_frc[2] = {nullptr, nullptr};
+  CmdChannel cmd[kCmdKinds];  // command state, one record per kind
   // per-robot command arrival (cfg.per_robot_commands): every robot has its own mode; general controller path only
   bool per_robot = false;
   uint8_t* d_mode = nullptr;        // uint8[B]: 1 = Position, 2 = Velocity; on the register-resident path also the robot's
                                     // Pid call count in bits 2-7 (StepArgs::meta)
   float* d_target = nullptr;        // per-robot handles on the register-resident path: float[B][n], every robot's ACTIVE target row
-  uint8_t* d_mask[3] = {nullptr, nullptr, nullptr};  // pending masks of the velocity / position / force command, uint8[B]
-  bool vel_masked = false, pos_masked = false, frc_masked = false;  // the pending command came with a mask
-  // Host-side Joy batches travel on their own stream (cdpr_set_*_command with a host pointer): the caller's rows go into
-  // one of two pinned staging buffers per kind and from there to the PENDING device buffer while earlier launches still
-  // run; the call returns without waiting.  kind 0 = velocity, 1 = position, 2 = force.
-  hipStream_t copy_stream = nullptr;
-  float* h_stage[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
-  hipEvent_t stage_ev[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};  // the copy out of that staging buffer has completed
-  bool stage_ev_set[3][2] = {{false, false}, {false, false}, {false, false}};
-  int stage_idx[3] = {0, 0, 0};
-  hipEvent_t ready_wait[3] = {nullptr, nullptr, nullptr};  // event the compute stream has to pass before it touches the pending buffer
-  hipEvent_t free_ev[3] = {nullptr, nullptr, nullptr};     // every launch that read what is now the pending buffer has completed
-  bool free_ev_set[3] = {false, false, false};
-  bool vel_pending = false, pos_pending = false, frc_pending = false;
-  bool have_vel = false, have_pos = false, have_frc = false;  // a command of that kind has been latched since Load
+  hipStream_t copy_stream = nullptr;  // host-side Joy batches travel on their own stream (CmdChannel::h_stage)
   int mode = kModePosition;
   uint64_t step = 0;
   double prev_publish = 0.0;
@@ -180,6 +198,9 @@ struct DevBuf {
   template <typename T> T* as() { return static_cast<T*>(p); }
 };
 
+// the kind whose latched command a uniform handle in `mode` reads
+inline int cmd_kind_of_mode(int mode) { return mode == kModeVelocity ? (int)CDPR_COMMAND_VELOCITY : mode == kModeForce ? (int)CDPR_COMMAND_FORCE : (int)CDPR_COMMAND_POSITION; }
+
 constexpr int kCallSat = 64;  // Pid call counts saturate here on the host (the kernels ask "0?", ">= nbuf?")
 inline int sat_pid_calls(int calls) { return calls < kCallSat ? calls : kCallSat; }
 // ring slot the error of world step `step` is written to (fp32 kernels: a ring of kWin; fp64: of w = win64)
@@ -193,6 +214,7 @@ int check_fault(cdpr_engine* h);
 int checked(cdpr_engine* h, int rc);
 int derivative_weights(uint32_t n, uint32_t degree, double* w);
 double sim_time(uint64_t step, double dt);
+uint64_t publish_mask(cdpr_engine* h, int k);  // which of the next k world steps publish; advances prev_publish
 LaunchShape launch_shape(const cdpr_engine* h, int k, bool steady = false);
 StepKernel step_kernel_of(const cdpr_engine* h, const PlannedKernel& pk);
 StepKernel select_step_kernel(const cdpr_engine* h, int k, bool steady = false);

@@ -1,0 +1,245 @@
+"""The engine's host-side command state, one channel per kind (velocity, position, force): what a single update does with the
+commands that are pending when it starts, whatever route they came by.  Against the fp64 oracle at the tolerances of
+tests/test_gpu_parity.py.
+
+  1  all three kinds (and every pair) pending before one update, in every arrival order: the latch order is fixed - velocity,
+     position, force (PLG.cpp:206-219 plus the [NEW] force ordering) - so Force mode wins, and on the way the Pid of every mode
+     entered is reset (JFC.cpp:101-103,113-115).  With velocity and position both pending the position latch sees the mode the
+     velocity latch has just set.  A velocity Joy with joints at or below velocityEpsilon follows: on the handles with the hold
+     branch those joints run the POSITION Pid, whose records tell whether the right Pid was reset.
+  2  two commands of one kind by different routes (host rows, a bound device buffer, a device buffer copied) before one update:
+     the later call wins and stays latched; a host command after a bound one swaps the engine's own buffers again.
+  3  per-robot handles: an unmasked command and a masked one of the same kind before one update merge robot by robot.
+  4  reset() drops every pending command, a bound pointer among them: the handle runs as from Load, bit for bit.
+
+Batches of 130 (two wavefronts and a partly filled one), 50 world steps per sequence.  The inputs are those of the existing
+tests (poses within 2 cm / 0.05 rad of home, velocities +-0.03, position targets +-0.004, forces around static equilibrium and
+inside [f_min, f_max]); every sequence below, run on the oracle alone from two start poses one float32 rounding apart, stays
+finite, keeps every effort >= 0, raises no travel-limit flag and moves effort by <= 3.1e-4 N and twist by <= 3.1e-7: sixty
+times and more below the tolerances (the check tests/test_workspace_inputs.py makes for its inputs)."""
+import itertools
+
+import numpy as np
+import pytest
+
+from test_gpu_force_mode import static_forces
+from test_gpu_parity import TOL, compare, pair, perturbed_poses
+
+pytestmark = pytest.mark.gpu
+
+B = 130
+KINDS = ("velocity", "position", "force")
+EPS = 0.002
+
+HANDLES = {  # uniform handles of test 1: (cables, Config arguments, CDPR_MAPPING)
+    "role_split_n8": (8, dict(stages=3), None),
+    "lane_pair_n4": (4, dict(stages=0), "2"),
+    "general_n8": (8, dict(stages=3, velocityEpsilon=EPS), None),
+    "fp64_hold_n8": (8, dict(stages=3, precision=64, velocityEpsilon=EPS), None),
+}
+
+
+def model_of(pkg, cables):
+    return pkg.cube_model() if cables == 4 else pkg.eight_cable_model()
+
+
+def rows_of(kind, cfg, rng):
+    if kind == "velocity":
+        return rng.uniform(-0.03, 0.03, (B, cfg.n_cables)).astype(np.float32)
+    if kind == "position":
+        return rng.uniform(-0.004, 0.004, (B, cfg.n_cables)).astype(np.float32)
+    return static_forces(cfg, B, rng)
+
+
+def hold_velocities(cfg, rng):
+    """a velocity Joy whose even joints sit below velocityEpsilon (they hold their position where the hold branch is live)"""
+    v = rows_of("velocity", cfg, rng)
+    v[np.abs(v) <= 2 * EPS] = np.float32(3 * EPS)
+    v[:, ::2] = np.float32(0.5 * EPS)
+    return v
+
+
+class Routes:
+    """The engine's three ways to hand a command over; the device buffers live until close()."""
+
+    def __init__(self, eng):
+        self.eng, self.bufs = eng, []
+
+    def send(self, kind, rows, route="host", mask=None):
+        if route == "host":
+            return getattr(self.eng, f"set_{kind}_command")(rows, mask=mask)
+        d = self.eng.device_upload(rows)
+        self.bufs.append(d)
+        name = f"bind_{kind}_command_device" if route == "bound" else f"set_{kind}_command_device"
+        return getattr(self.eng, name)(d, rows.size)
+
+    def update(self, k):
+        self.eng.update(k)
+
+    def close(self):
+        for d in self.bufs:
+            self.eng.device_free(d)
+        self.eng.close()
+
+
+class Plain:
+    """The oracle behind the same two calls: it has one route."""
+
+    def __init__(self, ora):
+        self.ora = ora
+
+    def send(self, kind, rows, route="host", mask=None):
+        return getattr(self.ora, f"set_{kind}_command")(rows, mask=mask)
+
+    def update(self, k):
+        self.ora.update(k)
+
+
+# ---- the sequences: `gpu` and `ora` have send(kind, rows, route, mask) and update(k); `check(where)` compares the two
+
+
+def seq_arrival_order(gpu, ora, check, cfg, rng, order, start):
+    """test 1: `order` = the kinds pending before one update, in arrival order; start = the mode with a Pid history before it"""
+    cmd = {k: rows_of(k, cfg, rng) for k in KINDS}
+    if start == "velocity":
+        v0 = rows_of("velocity", cfg, rng)
+        gpu.send("velocity", v0), ora.send("velocity", v0)
+    gpu.update(13), ora.update(13)
+    for k in order:
+        assert gpu.send(k, cmd[k]) == 0 and ora.send(k, cmd[k]) == 0
+    gpu.update(1), ora.update(1)
+    check(f"{order} from {start}: first step")
+    gpu.update(16), ora.update(16)
+    check(f"{order} from {start}: 17 steps")
+    v = hold_velocities(cfg, rng)
+    gpu.send("velocity", v), ora.send("velocity", v)
+    gpu.update(20), ora.update(20)
+    check(f"{order} from {start}: the velocity Joy behind it")
+
+
+ROUTE_PAIRS = (("host", "bound"), ("bound", "host"), ("copied", "bound"), ("bound", "copied"))
+
+
+def seq_mixed_routes(gpu, ora, check, cfg, rng, kind, routes):
+    """test 2: two commands of `kind` by two routes before one update; the oracle hears the later one only"""
+    a, b, c = (rows_of(kind, cfg, rng) for _ in range(3))
+    gpu.update(10), ora.update(10)
+    assert gpu.send(kind, a, routes[0]) == 0 and gpu.send(kind, b, routes[1]) == 0
+    ora.send(kind, b)
+    gpu.update(15), ora.update(15)
+    check(f"{kind} {routes}: the later call wins")
+    gpu.update(10), ora.update(10)
+    check(f"{kind} {routes}: it stays latched")
+    assert gpu.send(kind, c, "host") == 0
+    ora.send(kind, c)
+    gpu.update(15), ora.update(15)
+    check(f"{kind} {routes}: a host command behind it")
+
+
+def seq_masked_merge(gpu, ora, check, cfg, rng, kind, masked_first):
+    """test 3: an unmasked and a masked command of `kind` before one update on a per-robot handle, robots in three modes before it"""
+    a, b = rows_of(kind, cfg, rng), rows_of(kind, cfg, rng)
+    m = rng.random(B) < 0.4
+    grp = np.arange(B) % 3
+    v0, f0 = rows_of("velocity", cfg, rng), rows_of("force", cfg, rng)
+    for s in (gpu, ora):
+        s.send("velocity", v0, mask=grp == 1)
+        s.send("force", f0, mask=grp == 2)
+        s.update(15)
+        for rows, mask in ([(b, m), (a, None)] if masked_first else [(a, None), (b, m)]):
+            assert s.send(kind, rows, mask=mask) == 0
+        s.update(1)
+    check(f"{kind}, masked {'first' if masked_first else 'second'}: first step")
+    gpu.update(34), ora.update(34)
+    check(f"{kind}, masked {'first' if masked_first else 'second'}: 35 steps")
+
+
+# ---- on the GPU
+
+
+def run_on_gpu(pkg, oracle, cfg, seed, seq, *args):
+    rng = np.random.default_rng(seed)
+    eng, ora = pair(pkg, oracle, cfg, perturbed_poses(cfg.model, B, rng, 0.02, 0.05))
+    gpu = Routes(eng)
+    seq(gpu, Plain(ora), lambda where: compare(eng, ora, where=where), cfg, rng, *args)
+    gpu.close()
+    ora.close()
+
+
+def arrival_orders():
+    return list(itertools.permutations(KINDS)) + [p for s in itertools.combinations(KINDS, 2) for p in itertools.permutations(s)]
+
+
+@pytest.mark.parametrize("start", ["position", "velocity"])
+@pytest.mark.parametrize("handle", list(HANDLES))
+def test_pending_kinds_are_latched_in_the_fixed_order_whatever_their_arrival_order(pkg, oracle, monkeypatch, handle, start):
+    cables, kw, mapping = HANDLES[handle]
+    if mapping:
+        monkeypatch.setenv("CDPR_MAPPING", mapping)
+    cfg = pkg.Config(model=model_of(pkg, cables), batch=B, **kw)
+    for j, order in enumerate(arrival_orders()):
+        run_on_gpu(pkg, oracle, cfg, 100 + j, seq_arrival_order, order, start)
+
+
+def test_the_handles_of_the_arrival_order_test_are_what_they_are_named(pkg, monkeypatch):
+    from cdpr_simulation_amd.engine import plan_kernel
+
+    want = {"role_split_n8": "cdpr_split_kernel<8", "lane_pair_n4": "cdpr_step_kernel_pair<4", "general_n8": "cdpr_gen_", "fp64_hold_n8": "HOLD"}
+    for handle, (cables, kw, mapping) in HANDLES.items():
+        monkeypatch.delenv("CDPR_MAPPING", raising=False)
+        if mapping:
+            monkeypatch.setenv("CDPR_MAPPING", mapping)
+        name = plan_kernel(pkg.Config(model=model_of(pkg, cables), batch=B, **kw), 1)
+        assert want[handle] in name, (handle, name)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_the_later_of_two_routes_wins_and_stays_latched(pkg, oracle, kind):
+    cfg = pkg.Config(model=pkg.eight_cable_model(), batch=B, stages=3)
+    for j, routes in enumerate(ROUTE_PAIRS):
+        run_on_gpu(pkg, oracle, cfg, 200 + j, seq_mixed_routes, kind, routes)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("path", ["register_resident", "general"])
+def test_unmasked_and_masked_commands_of_one_kind_merge_per_robot(pkg, oracle, path, kind):
+    cfg = pkg.Config(model=pkg.eight_cable_model(), batch=B, stages=3, perRobotCommands=True, velocityEpsilon=EPS if path == "general" else -0.001)
+    for masked_first in (False, True):
+        run_on_gpu(pkg, oracle, cfg, 300 + int(masked_first), seq_masked_merge, kind, masked_first)
+
+
+@pytest.mark.parametrize("handle", ["role_split_n8", "general_n8", "fp64_hold_n8"])
+def test_reset_drops_every_pending_command_and_never_reads_a_bound_buffer_again(pkg, oracle, handle):
+    """Commands of all three kinds pending (the position one bound), reset(), the bound buffer overwritten with NaN and freed:
+    the next update runs as from Load - Position mode, target 0 - bit-identical to a fresh handle, and on the oracle."""
+    cables, kw, _ = HANDLES[handle]
+    cfg = pkg.Config(model=model_of(pkg, cables), batch=B, **kw)
+    rng = np.random.default_rng(400)
+    pose = perturbed_poses(cfg.model, B, rng, 0.02, 0.05).astype(np.float32)
+    eng, ora = pair(pkg, oracle, cfg, pose)
+    fresh = pkg.Engine(cfg, 0)
+    fresh.set_platform_state(pose7=pose)
+    v, p, f = (rows_of(k, cfg, rng) for k in KINDS)
+    eng.set_velocity_command(v), ora.set_velocity_command(v)
+    eng.update(20), ora.update(20)  # a mode and a Pid history to forget
+    d_p = eng.device_upload(p)
+    assert eng.set_velocity_command(-v) == 0 and eng.bind_position_command_device(d_p, p.size) == 0 and eng.set_force_command(f) == 0
+    ora.set_velocity_command(-v), ora.set_position_command(p), ora.set_force_command(f)
+    eng.reset(), ora.reset()
+    eng.device_upload_into(d_p, np.full_like(p, np.nan))
+    eng.device_free(d_p)
+    eng.set_platform_state(pose7=pose), ora.set_platform_state(pose7=pose.astype(np.float64))
+    for k in (1, 29):
+        eng.update(k), fresh.update(k), ora.update(k)
+        for x, y in zip(eng.platform_state() + eng.joint_states(), fresh.platform_state() + fresh.joint_states()):
+            assert np.array_equal(x, y), f"{handle}: differs from a fresh handle after reset"
+        compare(eng, ora, where=f"{handle}: after reset")
+    # ... and the channels work as before: a bound command, then a host one
+    d_v = eng.device_upload(v)
+    eng.bind_velocity_command_device(d_v, v.size), ora.set_velocity_command(v)
+    eng.update(10), ora.update(10)
+    eng.set_velocity_command(-v), ora.set_velocity_command(-v)
+    eng.update(10), ora.update(10)
+    compare(eng, ora, where=f"{handle}: commands after reset")
+    eng.device_free(d_v)
+    eng.close(), fresh.close(), ora.close()
