@@ -441,7 +441,11 @@ GenCtl general_ctl(const cdpr_engine* h) {
   g.mode_arr = h->per_robot ? h->d_mode : nullptr;
   g.wtab = h->d_gwtab;
   g.mode = h->mode;
+  // JFC.cpp:72 compares the Joy axis (a float32) promoted to double with the double epsilon.  The kernels compare in float32: with the
+  // largest float32 that is not above epsilon, t > g.eps holds for a float32 t exactly when (double)t > epsilon.  (float)epsilon
+  // alone may round UP (0.001, 0.004): a target equal to it would then hold position where the reference runs the velocity Pid.
   g.eps = (float)h->cfg.velocity_epsilon;
+  if ((double)g.eps > h->cfg.velocity_epsilon) g.eps = nextafterf(g.eps, -INFINITY);
   g.dt = (float)h->cfg.dt;
   g.lay = h->glay;
   g.ptab = h->d_gptab;

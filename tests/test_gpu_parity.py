@@ -193,7 +193,10 @@ def test_mode_switching_resets_the_right_pid(pkg, oracle):
 
 
 def test_saturation_and_anti_windup(pkg, oracle):
-    """A 2 m/s velocity demand saturates the command clamp (Pid.cpp:175-186) and the SetForce effort clamp."""
+    """A 2 m/s velocity demand saturates the command clamp (Pid.cpp:175-186) and the SetForce effort clamp.  cmdLimit equals the
+    effort limit here (both 100), so what the anti-windup leaves one increment BEYOND the command clamp is cut off by SetForce and
+    never reaches an observable: tests/test_gpu_pid_limits.py runs the clamps apart (cmdLimit 12 under an effort limit of 20 and
+    above one of 9) in every kernel family."""
     cfg = pkg.Config(batch=3)
     eng, ora = pair(pkg, oracle, cfg)
     cmd = np.array([[2.0] * 4, [-2.0] * 4, [0.5, -0.5, 0.5, -0.5]], dtype=np.float32)
