@@ -76,23 +76,7 @@ void fill_pid(const cdpr_pid_params_t& p, double dt, StepArgs& k, float* wtab_ho
   k.inv_dt = (float)(1.0 / dt);
   k.nbuf = (int)p.d_buffer_length;
   k.clamp_cmd = k.cmax > k.cmin;
-  // end-point LS derivative weights, oldest..newest, zero padded at the old end to kWin + 1 entries
-  double w[CDPR_MAX_D_BUFFER];
-  float wpad[kWin + 1];
-  for (int j = 0; j <= kWin; ++j) wpad[j] = 0.f;
-  if (derivative_weights(p.d_buffer_length, p.d_degree, w) == CDPR_OK && p.d_buffer_length <= (uint32_t)kWin + 1)
-    for (uint32_t j = 0; j < p.d_buffer_length; ++j) wpad[kWin + 1 - p.d_buffer_length + j] = (float)w[j];
-  // ring: when the new error goes to slot ws, slot (ws - j) mod 10 holds the error of j steps ago (j = 1..10;
-  // j = 10 is slot ws itself, the sample about to be overwritten), whose weight is wpad[10 - j]
-  for (int ws = 0; ws < kWin; ++ws) {
-    for (int s = 0; s < kWin; ++s) {
-      int j = ((ws - s) % kWin + kWin) % kWin;
-      if (j == 0) j = kWin;
-      wtab_host[ws * (kWin + 2) + s] = wpad[kWin - j];
-    }
-    wtab_host[ws * (kWin + 2) + kWin] = wpad[kWin];
-    wtab_host[ws * (kWin + 2) + kWin + 1] = 0.f;
-  }
+  rotated_weights(p, kWin, wtab_host);
 }
 
 void copy_pid(const StepArgs& src, StepArgs& dst) {
@@ -110,46 +94,20 @@ void copy_pid_alt(const StepArgs& src, PidSet& dst) {
 }
 
 void fill_consts(const cdpr_config_t& c, StepArgs& k) {
-  k.dt = (float)c.dt;
-  k.half_dt = (float)(0.5 * c.dt);
+  fill_physics<float>(c, k);
   k.dt_inv_mass = (float)(c.dt / c.mass);
-  k.fgx = (float)(c.mass * c.gravity[0]);
-  k.fgy = (float)(c.mass * c.gravity[1]);
-  k.fgz = (float)(c.mass * c.gravity[2]);
-  double inv[6];
-  mat3_inverse_sym(c.inertia, inv);
-  for (int i = 0; i < 6; ++i) {
-    k.ib[i] = (float)c.inertia[i];
-    k.ibinv[i] = (float)inv[i];
-  }
-  k.damping = (float)c.joint_damping;
-  k.effort = (float)c.effort_limit;
-  k.vel_limit = (float)c.velocity_limit;
-  k.unilateral = c.unilateral_cables ? 1 : 0;
-  k.travel_lo = (float)c.travel_lower;
-  k.travel_hi = (float)c.travel_upper;
-  k.travel_on = (c.travel_lower != 0.0 || c.travel_upper != 0.0) ? 1 : 0;
   k.travel_stop = k.travel_on ? (int)c.travel_stop : 0;
-  k.inv_mass = (float)(1.0 / c.mass);
-  k.ph_lumped = (c.passive_damping != 0.0 || c.leg_inertia != 0.0 || c.cable_axial_mass != 0.0 || c.anchor_point_mass != 0.0 || c.anchor_inertia != 0.0) ? 1 : 0;
-  k.ph_c = (float)c.passive_damping;
-  k.ph_jleg = (float)c.leg_inertia;
-  k.ph_max = (float)c.cable_axial_mass;
-  k.ph_mpt = (float)c.anchor_point_mass;
-  k.ph_iadd_total = (float)(c.anchor_inertia * (double)c.n_cables);
-  k.ph_mass = (float)c.mass;
-  k.gx = (float)c.gravity[0];
-  k.gy = (float)c.gravity[1];
-  k.gz = (float)c.gravity[2];
   k.split_swap = 0x9;  // measured on MI355X (65 536 x 8): masks 0 .. 0xf8 give 10.8-11.3 us/step, 0x9 the best; bits 8-9 (the
                        // workgroups that share a CU) make it 12.8: the dispatcher already alternates the SIMD pairs there
   if (const char* sw = std::getenv("CDPR_SPLIT_SWAP")) k.split_swap = (uint32_t)strtoul(sw, nullptr, 0);
-  k.fk_lambda = (float)c.fk_lambda;
-  k.fk_tol = (float)c.fk_tolerance;
-  k.fk_iters = (int)c.fk_max_iterations;
-  k.td_min = (float)c.td_f_min;
-  k.td_max = (float)c.td_f_max;
-  k.td_mid = (float)(0.5 * (c.td_f_min + c.td_f_max));
+}
+
+// BiQuad::SetFc(fc, fs = 1.0, q), Filter.h:130-140, in double: a0 a1 a2 b1 b2
+void biquad_coefficients(const cdpr_filter_params_t& f, double co[5]) {
+  const double k = std::tan(M_PI * f.rel_cutoff / 1.0);
+  const double den = k * k + k / f.quality + 1.0;
+  co[0] = k * k / den, co[1] = 2.0 * co[0], co[2] = co[0];
+  co[3] = 2.0 * (k * k - 1.0) / den, co[4] = (k * k - k / f.quality + 1.0) / den;
 }
 
 void fill_gen_pid(const cdpr_pid_params_t& p, GenPid& g) {
@@ -160,11 +118,9 @@ void fill_gen_pid(const cdpr_pid_params_t& p, GenPid& g) {
   g.pcas = (int)p.p_filter.cascade; g.dcas = (int)p.d_filter.cascade;
   g.clamp = g.cmax > g.cmin ? 1 : 0;
   auto biquad = [](const cdpr_filter_params_t& f, float& a0, float& a1, float& a2, float& b1, float& b2) {
-    // BiQuad::SetFc(fc, fs = 1.0, q), Filter.h:130-140
-    const double k = std::tan(M_PI * f.rel_cutoff / 1.0);
-    const double den = k * k + k / f.quality + 1.0;
-    a0 = (float)(k * k / den); a1 = (float)(2.0 * (k * k / den)); a2 = a0;
-    b1 = (float)(2.0 * (k * k - 1.0) / den); b2 = (float)((k * k - k / f.quality + 1.0) / den);
+    double co[5];
+    biquad_coefficients(f, co);
+    a0 = (float)co[0], a1 = (float)co[1], a2 = (float)co[2], b1 = (float)co[3], b2 = (float)co[4];
   };
   g.pa0 = g.pa1 = g.pa2 = g.pb1 = g.pb2 = g.da0 = g.da1 = g.da2 = g.db1 = g.db2 = 0.f;
   if (g.pcas) biquad(p.p_filter, g.pa0, g.pa1, g.pa2, g.pb1, g.pb2);
@@ -223,23 +179,23 @@ int set_device(cdpr_engine* h) {
   return CDPR_OK;
 }
 
-// Host image of the state a fresh Load leaves: platform at home, zero twist, FK seed at
+// Host image of the state a fresh Load leaves, `rows` columns of it: platform at home, zero twist, FK seed at
 // home, every controller record zero (count 0 => the first Pid call returns 0).
-std::vector<float4> home_state(const cdpr_engine* h) {
-  std::vector<float4> s((size_t)h->n_state * h->stride, make_float4(0.f, 0.f, 0.f, 0.f));
+std::vector<float4> home_state(const cdpr_engine* h, uint32_t rows) {
+  std::vector<float4> s((size_t)h->n_state * rows, make_float4(0.f, 0.f, 0.f, 0.f));
   const double* hp = h->cfg.home_pose;
-  for (uint32_t r = 0; r < h->stride; ++r) {
-    s[0 * (size_t)h->stride + r] = make_float4((float)hp[0], (float)hp[1], (float)hp[2], (float)hp[3]);
-    s[1 * (size_t)h->stride + r] = make_float4((float)hp[4], (float)hp[5], (float)hp[6], 0.f);
-    s[3 * (size_t)h->stride + r] = make_float4(0.f, (float)hp[0], (float)hp[1], (float)hp[2]);
-    if (h->fk) s[4 * (size_t)h->stride + r] = make_float4((float)hp[3], (float)hp[4], (float)hp[5], (float)hp[6]);
+  for (uint32_t r = 0; r < rows; ++r) {
+    s[0 * (size_t)rows + r] = make_float4((float)hp[0], (float)hp[1], (float)hp[2], (float)hp[3]);
+    s[1 * (size_t)rows + r] = make_float4((float)hp[4], (float)hp[5], (float)hp[6], 0.f);
+    s[3 * (size_t)rows + r] = make_float4(0.f, (float)hp[0], (float)hp[1], (float)hp[2]);
+    if (h->plan.fk) s[4 * (size_t)rows + r] = make_float4((float)hp[3], (float)hp[4], (float)hp[5], (float)hp[6]);
   }
   return s;
 }
 
 int upload_home(cdpr_engine* h) {
-  if (h->fp64) return upload_home64(h);
-  std::vector<float4> s = home_state(h);
+  if (h->plan.fp64) return upload_home64(h);
+  std::vector<float4> s = home_state(h, h->stride);
   HIP_TRY(h, hipMemcpyAsync(h->d_state, s.data(), s.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream));
   // observables before the first publish: the home pose, zeros elsewhere
   std::vector<float4> o((size_t)h->n_obs * h->stride, make_float4(0.f, 0.f, 0.f, 0.f));
@@ -258,50 +214,23 @@ int upload_home(cdpr_engine* h) {
   return CDPR_OK;
 }
 
+// Only what has an order is spelled out: both streams have drained (cdpr_destroy waits for the compute stream first), the graph
+// cache goes, then the events before their streams; every buffer is an owner member and goes with the handle.
 void free_all(cdpr_engine* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  if (h->d_state) (void)hipFree(h->d_state);
-  if (h->d_obs) (void)hipFree(h->d_obs);
-  if (h->d_dbg) (void)hipFree(h->d_dbg);
-  if (h->d_geom) (void)hipFree(h->d_geom);
-  if (h->d_wtab) (void)hipFree(h->d_wtab);
-  if (h->d_rec) (void)hipFree(h->d_rec);
-  if (h->d_gwtab) (void)hipFree(h->d_gwtab);
-  if (h->d_gptab) (void)hipFree(h->d_gptab);
-  if (h->d_roll_rec) (void)hipFree(h->d_roll_rec);
-  for (void* p64 : {(void*)h->d_roll64, (void*)h->d_roll64_acc, (void*)h->d_roll64_cmd, (void*)h->d_roll64_meta})
-    if (p64) (void)hipFree(p64);
-  if (h->d_mode) (void)hipFree(h->d_mode);
-  if (h->d_target) (void)hipFree(h->d_target);
-  if (h->d_unpack) (void)hipFree(h->d_unpack);
-  for (void* p64 : {(void*)h->d_state64, (void*)h->d_obs64, (void*)h->d_geom64, (void*)h->d_wtab64, (void*)h->d_dbg64, h->d_unpack64})
-    if (p64) (void)hipFree(p64);
-  if (h->h_fault) (void)hipHostFree(h->h_fault);
-  if (h->h_pub) (void)hipHostFree(h->h_pub);
-  if (h->h_pub64) (void)hipHostFree(h->h_pub64);
-  if (h->h_pub_done) (void)hipHostFree(h->h_pub_done);
-  if (h->d_pub_arrivals) (void)hipFree(h->d_pub_arrivals);
-  if (h->d_roll_ref) (void)hipFree(h->d_roll_ref);
-  if (h->d_roll_cost) (void)hipFree(h->d_roll_cost);
+  if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
   for (auto& g : h->graphs) {
     (void)hipGraphExecDestroy(g.exec);
     (void)hipGraphDestroy(g.graph);
   }
-  if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
-  for (CmdChannel& c : h->cmd) {
-    for (int i = 0; i < 2; ++i) {
-      if (c.d[i]) (void)hipFree(c.d[i]);
-      if (c.h_stage[i]) (void)hipHostFree(c.h_stage[i]);
-      if (c.stage_ev[i]) (void)hipEventDestroy(c.stage_ev[i]);
-    }
-    if (c.d_mask) (void)hipFree(c.d_mask);
-    if (c.free_ev) (void)hipEventDestroy(c.free_ev);
-  }
-  if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  for (CmdChannel& c : h->cmd)
+    for (hipEvent_t ev : {c.stage_ev[0], c.stage_ev[1], c.free_ev})
+      if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : {h->ev0, h->ev1})
+    if (ev) (void)hipEventDestroy(ev);
+  for (hipStream_t st : {h->copy_stream, h->stream})
+    if (st) (void)hipStreamDestroy(st);
   delete h;
 }
 
@@ -355,7 +284,7 @@ int stage_command(cdpr_engine* h, int kind, const float* src, size_t count, bool
   if (!h->copy_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
   const int idx = (c.stage_idx ^= 1);
   if (!c.h_stage[idx]) {
-    HIP_TRY(h, hipHostMalloc((void**)&c.h_stage[idx], bytes, hipHostMallocDefault));
+    HIP_TRY(h, c.h_stage[idx].alloc(bytes, hipHostMallocDefault));
     HIP_TRY(h, hipEventCreateWithFlags(&c.stage_ev[idx], hipEventDisableTiming));
   }
   if (!c.free_ev) HIP_TRY(h, hipEventCreateWithFlags(&c.free_ev, hipEventDisableTiming));
@@ -382,7 +311,7 @@ int stage_command(cdpr_engine* h, int kind, const float* src, size_t count, bool
 void set_weight_row(const cdpr_engine* h, StepArgs& a) {
   const int slot = a.ring_slot;
   // (per-robot handles: both Pids share one window, so the velocity Pid's table serves every lane)
-  memcpy(a.wrow, &h->wtab_host[(h->per_robot || h->mode == kModeVelocity) ? 0 : 1][slot * (kWin + 2)], sizeof a.wrow);
+  memcpy(a.wrow, &h->wtab_host[(h->plan.per_robot || h->mode == kModeVelocity) ? 0 : 1][slot * (kWin + 2)], sizeof a.wrow);
 }
 
 // The kernel a launch uses: the routing is planned_kernel's (cdpr_select.hpp: a pure function of the handle's plan and the
@@ -398,24 +327,24 @@ LaunchShape launch_shape(const cdpr_engine* h, int k, bool steady) {
 StepKernel step_kernel_of(const cdpr_engine* h, const PlannedKernel& pk) {
   const uint32_t n = h->n;
   switch (pk.id) {
-    case KernelId::StepSingle: return pick_step_kernel(true, n, h->fk, h->td);
-    case KernelId::StepMulti: return pick_step_kernel(false, n, h->fk, h->td);
-    case KernelId::Lowreg: return pick_lowreg_kernel(n, h->td);
-    case KernelId::OnestepPersist: return pick_onestep_persist_kernel(n, h->fk, h->td);
+    case KernelId::StepSingle: return pick_step_kernel(true, n, h->plan.fk, h->plan.td);
+    case KernelId::StepMulti: return pick_step_kernel(false, n, h->plan.fk, h->plan.td);
+    case KernelId::Lowreg: return pick_lowreg_kernel(n, h->plan.td);
+    case KernelId::OnestepPersist: return pick_onestep_persist_kernel(n, h->plan.fk, h->plan.td);
     case KernelId::Split: return pick_split_kernel(n);
-    case KernelId::Onestep: return pick_onestep_kernel(n, h->fk, h->td);
-    case KernelId::PhysStep: return pick_phys_kernel(n, h->fk, h->td, kPhysStep);
-    case KernelId::Rollout: return pick_rollout_kernel(n, h->fk, h->td);
-    case KernelId::PhysRollout: return pick_phys_kernel(n, h->fk, h->td, kPhysRollout);
-    case KernelId::PrSingle: return pick_pr_kernel(true, false, false, n, h->fk, h->td);
-    case KernelId::PrLowreg: return pick_pr_kernel(true, false, true, n, h->fk, h->td);
+    case KernelId::Onestep: return pick_onestep_kernel(n, h->plan.fk, h->plan.td);
+    case KernelId::PhysStep: return pick_phys_kernel(n, h->plan.fk, h->plan.td, kPhysStep);
+    case KernelId::Rollout: return pick_rollout_kernel(n, h->plan.fk, h->plan.td);
+    case KernelId::PhysRollout: return pick_phys_kernel(n, h->plan.fk, h->plan.td, kPhysRollout);
+    case KernelId::PrSingle: return pick_pr_kernel(true, false, false, n, h->plan.fk, h->plan.td);
+    case KernelId::PrLowreg: return pick_pr_kernel(true, false, true, n, h->plan.fk, h->plan.td);
     case KernelId::PrSplit: return pick_pr_split_kernel(n);
-    case KernelId::PrMulti: return pick_pr_kernel(false, false, false, n, h->fk, h->td);
-    case KernelId::PrRollout: return pick_pr_kernel(false, true, false, n, h->fk, h->td);
-    case KernelId::PairSingle: return pick_pair_kernel(true, n, h->fk, h->td);
-    case KernelId::PairMulti: return pick_pair_kernel(false, n, h->fk, h->td);
+    case KernelId::PrMulti: return pick_pr_kernel(false, false, false, n, h->plan.fk, h->plan.td);
+    case KernelId::PrRollout: return pick_pr_kernel(false, true, false, n, h->plan.fk, h->plan.td);
+    case KernelId::PairSingle: return pick_pair_kernel(true, n, h->plan.fk, h->plan.td);
+    case KernelId::PairMulti: return pick_pair_kernel(false, n, h->plan.fk, h->plan.td);
     case KernelId::PairStream: return pick_pair_stream_kernel(n, h->mode == kModeVelocity);
-    case KernelId::Cable: return pick_cable_kernel(n, h->fk, h->td);
+    case KernelId::Cable: return pick_cable_kernel(n, h->plan.fk, h->plan.td);
     default: return nullptr;  // (general path and precision = 64: their own launch functions)
   }
 }
@@ -429,6 +358,46 @@ bool pair_stream_steady(const cdpr_engine* h, const StepArgs& a) {
 }
 uint32_t step_block_threads(const cdpr_engine* h, int k) { return planned_kernel(h->plan, launch_shape(h, k)).block; }
 
+// cdpr_create's part of a general-path handle: the layout of the controller records, the records, the two Pids' parameter table
+// and their FIR weights by ring head.
+static int build_general(cdpr_engine* h) {
+  const cdpr_config_t& cfg = h->cfg;
+  h->glay.n = (int)h->n;
+  h->glay.nb = (int)std::max(cfg.velocity_pid.d_buffer_length, cfg.position_pid.d_buffer_length);
+  h->glay.ncas = (int)std::max(std::max(cfg.velocity_pid.p_filter.cascade, cfg.velocity_pid.d_filter.cascade),
+                               std::max(cfg.position_pid.p_filter.cascade, cfg.position_pid.d_filter.cascade));
+  const size_t rec_bytes = h->glay.bytes(h->stride);
+  if (rec_bytes >= (1ull << 32)) {  // the record buffer is addressed with 32-bit offsets (one buffer resource)
+    h->err = "general controller path: the controller records of this batch pass 4 GiB; split the batch over several handles";
+    return CDPR_ERR_UNSUPPORTED;
+  }
+  CREATE_TRY(h, "hipMalloc(rec)", h->d_rec.alloc(rec_bytes));
+  fill_gen_pid(cfg.position_pid, h->gpid[0]);
+  fill_gen_pid(cfg.velocity_pid, h->gpid[1]);
+  // FIR weights by ring head: when the newest sample sits in slot `head`, slot j holds the sample of age (head - j) mod
+  // nbuf, whose end-point LS weight (oldest first) is w[nbuf - 1 - age]; slots >= nbuf weigh nothing.  The head slot itself
+  // weighs nothing in the table: the newest sample is still in a register when the FIR runs, its weight rides in the Pid
+  // table (last float)
+  const int nbmax = h->glay.nb > 11 ? kGenMaxBuf : 11, nbp = gen_nbp(nbmax);
+  std::vector<float> wt((size_t)2 * nbmax * nbp, 0.f);
+  const cdpr_pid_params_t* pp[2] = {&cfg.position_pid, &cfg.velocity_pid};
+  float w_new[2] = {0.f, 0.f};
+  for (int p = 0; p < 2; ++p) {
+    double w[CDPR_MAX_D_BUFFER];
+    const int nb = (int)pp[p]->d_buffer_length;
+    if (derivative_weights((uint32_t)nb, pp[p]->d_degree, w) != CDPR_OK) continue;
+    for (int head = 0; head < nb; ++head)
+      for (int j = 0; j < nb; ++j) wt[((size_t)p * nbmax + head) * nbp + j] = (j == head) ? 0.f : (float)w[nb - 1 - (((head - j) % nb + nb) % nb)];
+    w_new[p] = (float)w[nb - 1];
+  }
+  float pt[2 * kGenPidFloats];
+  gen_pid_table(h->gpid[0], pt);
+  gen_pid_table(h->gpid[1], pt + kGenPidFloats);
+  pt[kGenPidFloats - 1] = w_new[0], pt[2 * kGenPidFloats - 1] = w_new[1];
+  if (int rc = upload_table(h, h->d_gptab, pt, sizeof pt, "gptab")) return rc;
+  return upload_table(h, h->d_gwtab, wt.data(), wt.size() * sizeof(float), "gwtab");
+}
+
 // The controller half of a general-path launch: records, latched commands, gains.
 GenCtl general_ctl(const cdpr_engine* h) {
   GenCtl g{};
@@ -438,7 +407,7 @@ GenCtl general_ctl(const cdpr_engine* h) {
   const float* latched[kCmdKinds];
   for (int k = 0; k < kCmdKinds; ++k) latched[k] = h->cmd[k].have ? h->cmd[k].latched() : nullptr;
   g.vel_cmd = latched[CDPR_COMMAND_VELOCITY], g.pos_cmd = latched[CDPR_COMMAND_POSITION], g.frc_cmd = latched[CDPR_COMMAND_FORCE];
-  g.mode_arr = h->per_robot ? h->d_mode : nullptr;
+  g.mode_arr = h->plan.per_robot ? h->d_mode : nullptr;
   g.wtab = h->d_gwtab;
   g.mode = h->mode;
   // JFC.cpp:72 compares the Joy axis (a float32) promoted to double with the double epsilon.  The kernels compare in float32: with the
@@ -452,7 +421,7 @@ GenCtl general_ctl(const cdpr_engine* h) {
   g.pcas_max = std::max(h->gpid[0].pcas, h->gpid[1].pcas);
   g.dcas_max = std::max(h->gpid[0].dcas, h->gpid[1].dcas);
   g.nbuf0 = h->gpid[0].nbuf, g.nbuf1 = h->gpid[1].nbuf;
-  g.hot = h->gen_hot ? 1 : 0;
+  g.hot = h->plan.gen_hot ? 1 : 0;
   {
     const GenPid &p0 = h->gpid[0], &p1 = h->gpid[1];
     const bool same_window = p0.nbuf == p1.nbuf && p0.degree == p1.degree;
@@ -485,7 +454,7 @@ int run_steps_general(cdpr_engine* h, int nsteps, int per_launch, float4* record
   // where the role-split one-step kernel serves the handle, its launches beat the one-wave kernel's multi-step ones
   // (16 384 x 8: 9.2 against 13.7 us per step, 32 768: 10.1 against 21.6; same bits): fused updates and the trajectory
   // record then run as one-step launches
-  if (h->gen_split || h->gen_lean) per_launch = 1;  // (likewise where the lean kernel + one-wave kernel pair steps the handle)
+  if (h->plan.gen_split || h->plan.gen_lean) per_launch = 1;  // (likewise where the lean kernel + one-wave kernel pair steps the handle)
   int done = 0;
   while (done < nsteps) {
     const int k = std::min(per_launch, nsteps - done);
@@ -493,7 +462,7 @@ int run_steps_general(cdpr_engine* h, int nsteps, int per_launch, float4* record
     // lean role-split kernel (two waves per SIMD; the rare controller paths by call) - planned_kernel, cdpr_select.hpp
     const PlannedKernel pk = planned_kernel(h->plan, launch_shape(h, k));
     const bool gsplit = pk.id == KernelId::GenSplit, glean = pk.id == KernelId::GenLean;
-    GenKernel kern = gsplit ? pick_gen_split11(h->n) : glean ? pick_gen_lean11(h->n) : pick_gen_kernel(h->n, h->fk, h->td, false, h->glay.nb > 11, pk.id == KernelId::GenOne);
+    GenKernel kern = gsplit ? pick_gen_split11(h->n) : glean ? pick_gen_lean11(h->n) : pick_gen_kernel(h->n, h->plan.fk, h->plan.td, false, h->glay.nb > 11, pk.id == KernelId::GenOne);
     h->last_kernel = pk;
     a.nsteps = k;
     a.flags = (h->step == 0) ? kFlagFirstWorldStep : 0u;
@@ -515,18 +484,11 @@ int run_steps_general(cdpr_engine* h, int nsteps, int per_launch, float4* record
 // its argument buffers on the FIRST launch: measured ~1 ms), not the first cdpr_update: one launch of exactly that kernel
 // over one workgroup of home-state robots in a scratch buffer, which is then freed.  The handle's own state is not touched.
 int warm_first_launch(cdpr_engine* h) {
-  if (h->general || h->fp64) return CDPR_OK;
+  if (h->plan.general || h->plan.fp64) return CDPR_OK;
   if (const char* w = std::getenv("CDPR_NO_WARM_LAUNCH"))
     if (w[0] == '1') return CDPR_OK;
   const uint32_t rows = 64;
-  std::vector<float4> s((size_t)h->n_state * rows, make_float4(0.f, 0.f, 0.f, 0.f));
-  const double* hp = h->cfg.home_pose;
-  for (uint32_t r = 0; r < rows; ++r) {
-    s[0 * (size_t)rows + r] = make_float4((float)hp[0], (float)hp[1], (float)hp[2], (float)hp[3]);
-    s[1 * (size_t)rows + r] = make_float4((float)hp[4], (float)hp[5], (float)hp[6], 0.f);
-    s[3 * (size_t)rows + r] = make_float4(0.f, (float)hp[0], (float)hp[1], (float)hp[2]);
-    if (h->fk) s[4 * (size_t)rows + r] = make_float4((float)hp[3], (float)hp[4], (float)hp[5], (float)hp[6]);
-  }
+  const std::vector<float4> s = home_state(h, rows);
   DevBuf st, ob, cm, mt;
   HIP_TRY(h, mt.alloc(rows));
   HIP_TRY(h, hipMemsetAsync(mt.p, (int)(kMetaPosition | (20u << kMetaCallShift)), rows, h->stream));
@@ -541,13 +503,13 @@ int warm_first_launch(cdpr_engine* h) {
   a.cmd = cm.as<float>();
   a.dbg = nullptr;
   a.geom = h->d_geom;
-  a.batch = h->lane_cable ? (h->n <= 4 ? 16u : 8u) : h->lane_pair ? 32u : 64u;
+  a.batch = h->plan.lane_cable ? (h->n <= 4 ? 16u : 8u) : h->plan.lane_pair ? 32u : 64u;
   a.stride = rows;
   a.nsteps = 1;
   a.obs_step_stride = 0;
   a.flags = 0u;
   a.publish_mask = 1ull;
-  copy_pid(h->per_robot ? h->pid_vel : h->pid_pos, a);
+  copy_pid(h->plan.per_robot ? h->pid_vel : h->pid_pos, a);
   copy_pid_alt(h->pid_pos, a.alt);
   a.meta = mt.as<uint8_t>();
   a.pid_calls = kCallSat;  // steady state: every branch of the step is taken, as in the launches that follow
@@ -559,12 +521,12 @@ int warm_first_launch(cdpr_engine* h) {
   return CDPR_OK;
 }
 
-// One step-kernel launch over the whole batch, or (h->chunk) the same launch cut into contiguous blocks of robots issued
+// One step-kernel launch over the whole batch, or (h->plan.chunk) the same launch cut into contiguous blocks of robots issued
 // back to back on the handle's stream: every pointer that is indexed by robot moves to the block's first robot, the row
 // stride stays.  Robots are independent, so the results are bit-identical to the single launch (tested).
 void launch_step(cdpr_engine* h, StepKernel kern, uint32_t robots_per_block, dim3 block, const StepArgs& a, uint32_t max_grid = 0) {
   const uint32_t B = a.batch;
-  const uint32_t chunk = (h->chunk && B > h->chunk) ? h->chunk : B;
+  const uint32_t chunk = (h->plan.chunk && B > h->plan.chunk) ? h->plan.chunk : B;
   const uint32_t pieces = (B + chunk - 1u) / chunk;
   const uint32_t each = (((B + pieces - 1u) / pieces) + 63u) & ~63u;  // balanced, whole wavefronts
   for (uint32_t first = 0; first < B; first += each) {
@@ -584,7 +546,7 @@ void launch_step(cdpr_engine* h, StepKernel kern, uint32_t robots_per_block, dim
 
 // the general path's hot rows back into the H slots (cdpr_gen_flush_hot_kernel) before a Pid's records are reset or latched over
 static void flush_hot(cdpr_engine* h) {
-  if (!h->d_rec || !h->gen_hot) return;
+  if (!h->d_rec || !h->plan.gen_hot) return;
   GenFlushArgs fa{};
   fa.rec = h->d_rec, fa.rstride = h->stride, fa.batch = h->batch, fa.lay = h->glay, fa.nbuf = std::max(h->gpid[0].nbuf, 1);
   hipLaunchKernelGGL(cdpr_gen_flush_hot_kernel, dim3((h->batch + 255u) / 256u), dim3(256), 0, h->stream, fa);
@@ -602,7 +564,7 @@ static hipError_t reset_block(cdpr_engine* h, int which) {
 // precision = 64 with the hold branch: Pid::reset of one Pid of every cable (its rows behind the state)
 static hipError_t reset_block64(cdpr_engine* h, int which) {
   for (uint32_t i = 0; i < h->n; ++i) {
-    hipError_t e1 = hipMemsetAsync(h->d_state64 + (size_t)f64_hold_row((int)h->n, (int)i, which, h->hold_win) * h->stride, 0, (size_t)hold_pid_rows(h->hold_win) * h->stride * sizeof(double),
+    hipError_t e1 = hipMemsetAsync(h->d_state64 + (size_t)f64_hold_row((int)h->n, (int)i, which, hold_win(h)) * h->stride, 0, (size_t)hold_pid_rows(hold_win(h)) * h->stride * sizeof(double),
                                    h->stream);
     if (e1 != hipSuccess) return e1;
   }
@@ -614,7 +576,7 @@ static hipError_t reset_block64(cdpr_engine* h, int which) {
 static int latch_per_robot(cdpr_engine* h, int kind, const float* pending, const uint8_t* mask) {
   const CmdKind& K = kCmdKind[kind];
   const dim3 grid((h->batch + 255u) / 256u), block(256);
-  if (h->fp64) {  // the same on the double state (integral rows 20 + 11 i + 10)
+  if (h->plan.fp64) {  // the same on the double state (integral rows 20 + 11 i + 10)
     LatchF64Args lf{};
     lf.mask = mask;
     lf.meta = h->d_mode;
@@ -625,17 +587,17 @@ static int latch_per_robot(cdpr_engine* h, int kind, const float* pending, const
     lf.batch = h->batch;
     lf.n = h->n;
     lf.new_mode = K.meta;
-    lf.hold = h->hold64 ? 1u : 0u;
-    lf.win = (uint32_t)h->win64;
-    lf.hold_win = (uint32_t)h->hold_win;
+    lf.hold = h->plan.hold64 ? 1u : 0u;
+    lf.win = (uint32_t)win64(h);
+    lf.hold_win = (uint32_t)hold_win(h);
     hipLaunchKernelGGL(cdpr_latch_f64_kernel, grid, block, 0, h->stream, lf);
-  } else if (!h->general) {  // one active target row and one Pid record per robot
+  } else if (!h->plan.general) {  // one active target row and one Pid record per robot
     LatchFastArgs lf{};
     lf.mask = mask;
     lf.meta = h->d_mode;
     lf.pending = pending;
     lf.target = h->d_target;
-    lf.hot = h->d_state + (size_t)(plat_slots(h->fk) + 5 * cable_pairs((int)h->n)) * h->stride;
+    lf.hot = h->d_state + (size_t)(plat_slots(h->plan.fk) + 5 * cable_pairs((int)h->n)) * h->stride;
     lf.stride = h->stride;
     lf.batch = h->batch;
     lf.n = h->n;
@@ -677,24 +639,24 @@ static int latch_pending(cdpr_engine* h, bool& reset_pid) {
     CmdChannel& c = h->cmd[k];
     if (!c.pending) continue;
     const CmdKind& K = kCmdKind[k];
-    if (h->per_robot) {
+    if (h->plan.per_robot) {
       // (a batch of a device-resident schedule, cdpr_update_scheduled_kind, is latched from the caller's buffers in place)
       const bool in_place = c.sched_rows != nullptr;
-      if (int rc = latch_per_robot(h, k, in_place ? c.sched_rows : c.d[1], in_place ? c.sched_mask : (c.masked ? c.d_mask : nullptr))) return rc;
+      if (int rc = latch_per_robot(h, k, in_place ? c.sched_rows : c.d[1].p, in_place ? c.sched_mask : (c.masked ? c.d_mask.p : nullptr))) return rc;
       touched[k] = !in_place;
     } else {
       if (c.ext[1]) {  // bound caller buffer: latched by pointer, nothing copied
         c.ext[0] = c.ext[1];
         c.ext[1] = nullptr;
       } else {
-        std::swap(c.d[0], c.d[1]);
+        c.d[0].swap(c.d[1]);
         c.ext[0] = nullptr;
         touched[k] = true;  // what is pending now was the latched buffer of the launches queued so far
       }
       if (K.reset_pid >= 0) {  // entering a mode resets its Pid (fast path: the single record now belongs to that Pid)
         reset_pid = (h->mode != K.mode);
-        if (h->general && reset_pid) HIP_TRY(h, reset_block(h, K.reset_pid));
-        if (h->hold64 && reset_pid) HIP_TRY(h, reset_block64(h, K.reset_pid));
+        if (h->plan.general && reset_pid) HIP_TRY(h, reset_block(h, K.reset_pid));
+        if (h->plan.hold64 && reset_pid) HIP_TRY(h, reset_block64(h, K.reset_pid));
       }
       h->mode = K.mode;
     }
@@ -728,12 +690,12 @@ int run_steps(cdpr_engine* h, int nsteps, int per_launch, float4* record = nullp
 
   bool reset_pid = false;
   if (int rc = latch_pending(h, reset_pid)) return rc;
-  if (h->general) return run_steps_general(h, nsteps, per_launch, record);
-  if (h->fp64) return run_steps_f64(h, nsteps, per_launch, reset_pid, reinterpret_cast<double*>(record));
+  if (h->plan.general) return run_steps_general(h, nsteps, per_launch, record);
+  if (h->plan.fp64) return run_steps_f64(h, nsteps, per_launch, reset_pid, reinterpret_cast<double*>(record));
 
   if (reset_pid) {  // Pid::reset (Pid.cpp:100-115): zero every controller record; rare, so done outside the step kernel
     h->pid_calls = 0;
-    const int P = plat_slots(h->fk);
+    const int P = plat_slots(h->plan.fk);
     HIP_TRY(h, hipMemsetAsync(h->d_state + (size_t)P * h->stride, 0, (size_t)ctrl_slots((int)h->n) * h->stride * sizeof(float4), h->stream));
   }
   StepArgs a = h->base;
@@ -746,7 +708,7 @@ int run_steps(cdpr_engine* h, int nsteps, int per_launch, float4* record = nullp
   // trajectory record: the observable image of step j of the call goes to record + j * n_obs * stride
   const size_t image = (size_t)h->n_obs * h->stride;
   a.obs_step_stride = record ? image : 0;
-  if (h->per_robot) {
+  if (h->plan.per_robot) {
     copy_pid(h->pid_vel, a);
     copy_pid_alt(h->pid_pos, a.alt);
     a.cmd = h->d_target;
@@ -755,7 +717,7 @@ int run_steps(cdpr_engine* h, int nsteps, int per_launch, float4* record = nullp
     copy_pid(h->mode == kModeVelocity ? h->pid_vel : h->pid_pos, a);  // (Force mode: unused, no Pid runs)
     a.cmd = h->cmd[cmd_kind_of_mode(h->mode)].latched();  // position: all zeros until the first jointPositions message: target 0 (PLG.cpp:153-157)
   }
-  const uint32_t robots_per_block = h->lane_cable ? (h->n <= 4 ? 16u : 8u) : h->lane_pair ? 32u : 64u;
+  const uint32_t robots_per_block = h->plan.lane_cable ? (h->n <= 4 ? 16u : 8u) : h->plan.lane_pair ? 32u : 64u;
   const dim3 grid((h->batch + robots_per_block - 1u) / robots_per_block);
 
   constexpr int kGraphChunk = 10;  // launches per captured graph = one ring period: a chain ends on the ring slot it started from.
@@ -765,7 +727,7 @@ int run_steps(cdpr_engine* h, int nsteps, int per_launch, float4* record = nullp
   while (done < nsteps) {
     const int k = std::min(per_launch, nsteps - done);
     a.nsteps = k;
-    a.flags = h->per_robot ? 0u : (h->mode == kModeVelocity ? kFlagActualIsVelocity : h->mode == kModeForce ? kFlagForceMode : 0u);
+    a.flags = h->plan.per_robot ? 0u : (h->mode == kModeVelocity ? kFlagActualIsVelocity : h->mode == kModeForce ? kFlagForceMode : 0u);
     const bool first_world = (h->step == 0);
     if (first_world) a.flags |= kFlagFirstWorldStep;
     // the kernel uses calls != 0 and calls >= nbuf (<= 11): the count saturates, and the ring position follows the world
@@ -796,7 +758,7 @@ int run_steps(cdpr_engine* h, int nsteps, int per_launch, float4* record = nullp
     // (the ring position advances with every step, so a captured chain is only valid from the position it was captured at:
     //  part of the cache key; the call count must be saturated (per-robot handles keep theirs on the device))
     if (record) a.obs = record + (size_t)done * image;
-    const bool steady = !record && !h->sched_refresh && h->use_graphs && (size_t)h->batch * h->n <= 131072u && !first_world && (h->per_robot || a.pid_calls == kCallSat || h->mode == kModeForce) &&
+    const bool steady = !record && !h->sched_refresh && h->use_graphs && (size_t)h->batch * h->n <= 131072u && !first_world && (h->plan.per_robot || a.pid_calls == kCallSat || h->mode == kModeForce) &&
                         h->cfg.publish_period == 0.0 && (nsteps - done) >= kGraphChunk * k;
     if (steady) {
       a.publish_mask = (k >= 64) ? ~0ull : ((1ull << k) - 1ull);
@@ -855,7 +817,7 @@ int run_steps(cdpr_engine* h, int nsteps, int per_launch, float4* record = nullp
     } else {
       a.publish_mask = publish_mask(h, k);
     }
-    launch_step(h, kern, robots_per_block, block, a, (h->persist && k == 1 && !h->per_robot) ? h->persist_grid : 0u);
+    launch_step(h, kern, robots_per_block, block, a, (h->plan.persist && k == 1 && !h->plan.per_robot) ? h->persist_grid : 0u);
     HIP_TRY(h, hipGetLastError());
     h->step += (uint64_t)k;
     if (h->mode != kModeForce) h->pid_calls = sat_pid_calls(h->pid_calls + k - (first_world ? 1 : 0));
@@ -882,14 +844,7 @@ int fetch_fields(cdpr_engine* h, const float4* rows, const std::vector<std::pair
     return CDPR_ERR_INVALID;
   }
   const size_t count = (size_t)h->batch * fields.size();
-  if (h->unpack_cap < count) {
-    HIP_TRY(h, wait_stream(h));
-    if (h->d_unpack) (void)hipFree(h->d_unpack);
-    h->d_unpack = nullptr;
-    h->unpack_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->d_unpack, count * sizeof(float)));
-    h->unpack_cap = count;
-  }
+  HIP_TRY(h, h->d_unpack.ensure(h, count * sizeof(float)));
   UnpackArgs u{};
   u.rows = rows;
   u.out = h->d_unpack;
@@ -956,6 +911,72 @@ int check_fault(cdpr_engine* h) {
 // cdpr_device_download return CDPR_ERR_DEVICE until cdpr_reset - the fp64 read-outs and the FK / TD / limit / debug getters too)
 int checked(cdpr_engine* h, int rc) { return rc != CDPR_OK ? rc : check_fault(h); }
 
+// What every kind of handle gets in cdpr_create: sizes, constants, stream and events, the command buffers, the fp32 tables, the
+// per-robot rows; then the path's own set-up (build_f64, build_general), the home state and the warm launch.
+static int build_handle(cdpr_engine* h) {
+  const cdpr_config_t& cfg = h->cfg;
+  h->n = cfg.n_cables;
+  h->batch = (uint32_t)cfg.batch;
+  h->stride = (h->batch + 63u) & ~63u;
+  // A robot's rows lie `stride` x 16 B apart.  When that is a multiple of 2 MiB (131 072 robots) every row of a wavefront
+  // maps to the same HBM channels and the launch loses 17 % (131 072 x 8: 29.8 -> 24.7 us per step, 262 144: 46-54 -> 43.3;
+  // profiles/r04_stride_padding.txt: this was most of "the 131 072 anomaly").  Any pad of 64 .. 1 088 columns cures it
+  // alike; smaller batches are not padded (16 384: a pad costs 3-4 %).  CDPR_STRIDE_PAD=<columns> forces a pad (A/B).
+  if (h->stride % 131072u == 0u) h->stride += 128u;
+  if (const char* sp = std::getenv("CDPR_STRIDE_PAD")) h->stride = ((h->batch + 63u) & ~63u) + ((uint32_t)(std::max(0L, std::atol(sp)) + 63L) & ~63u);
+  h->dbg = (cfg.stages & CDPR_STAGE_PID_DEBUG) != 0;
+  if (h->plan.persist) {
+    h->persist_grid = (uint32_t)h->cus * 4u;
+    if (const char* pg = std::getenv("CDPR_PERSIST_GRID")) h->persist_grid = (uint32_t)std::max(1L, std::atol(pg));
+  }
+  h->n_state = h->plan.general ? plat_slots(h->plan.fk) : state_slots((int)h->n, h->plan.fk);
+  h->n_obs = obs_slots((int)h->n);
+  memset(&h->base, 0, sizeof h->base);
+  fill_consts(cfg, h->base);
+  fill_pid(cfg.velocity_pid, cfg.dt, h->pid_vel, h->wtab_host[0]);
+  fill_pid(cfg.position_pid, cfg.dt, h->pid_pos, h->wtab_host[1]);
+  engine_reset_host(h);
+  {
+    const char* ng = std::getenv("CDPR_NO_GRAPH");
+    h->use_graphs = !(ng && ng[0] == '1');
+  }
+
+  CREATE_TRY(h, "hipSetDevice", hipSetDevice(h->device));
+  CREATE_TRY(h, "hipStreamCreate", hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  CREATE_TRY(h, "hipEventCreate", hipEventCreate(&h->ev0));
+  CREATE_TRY(h, "hipEventCreate", hipEventCreate(&h->ev1));
+  if (h->plan.fp64) {
+    if (int rc = build_f64(h)) return rc;
+  } else {
+    const size_t slot_bytes = (size_t)h->stride * sizeof(float4);
+    CREATE_TRY(h, "hipMalloc(state)", h->d_state.alloc(slot_bytes * h->n_state));
+    CREATE_TRY(h, "hipMalloc(obs)", h->d_obs.alloc(slot_bytes * h->n_obs));
+  }
+  const size_t cmd_bytes = (size_t)h->stride * h->n * sizeof(float);
+  for (int i = 0; i < 2; ++i)
+    for (CmdChannel& c : h->cmd) {
+      CREATE_TRY(h, "hipMalloc(cmd)", c.d[i].alloc(cmd_bytes));
+      (void)hipMemset(c.d[i], 0, cmd_bytes);
+    }
+  if (int rc = upload_table(h, h->d_wtab, h->wtab_host, sizeof h->wtab_host, "wtab")) return rc;
+  h->pid_vel.wtab = h->d_wtab;
+  h->pid_pos.wtab = h->d_wtab + kWin * (kWin + 2);
+  {
+    std::vector<float> g = geom_pairs(cfg);
+    if (int rc = upload_table(h, h->d_geom, g.data(), g.size() * sizeof(float), "geom")) return rc;
+  }
+  if (h->plan.general)
+    if (int rc = build_general(h)) return rc;
+  if (h->plan.per_robot) {
+    if (!h->plan.general) CREATE_TRY(h, "hipMalloc(target)", h->d_target.alloc(cmd_bytes));
+    CREATE_TRY(h, "hipMalloc(mode)", h->d_mode.alloc(h->batch));
+    for (CmdChannel& c : h->cmd) CREATE_TRY(h, "hipMalloc(mask)", c.d_mask.alloc(h->batch));
+  }
+  if (h->dbg && !h->plan.fp64) CREATE_TRY(h, "hipMalloc(dbg)", h->d_dbg.alloc((size_t)h->batch * CDPR_PID_DEBUG_AXES * sizeof(float)));
+  if (upload_home(h) != CDPR_OK || warm_first_launch(h) != CDPR_OK) return CDPR_ERR_DEVICE;
+  return CDPR_OK;
+}
+
 }  // namespace cdpr_host
 
 // =================================================================================
@@ -1021,197 +1042,14 @@ int cdpr_create(const cdpr_config_t* cfg, int device, cdpr_handle_t* out) {
   cdpr_engine* h = new cdpr_engine();
   h->cfg = *cfg;
   h->device = device;
-  h->n = cfg->n_cables;
-  h->batch = (uint32_t)cfg->batch;
-  h->stride = (h->batch + 63u) & ~63u;
-  // A robot's rows lie `stride` x 16 B apart.  When that is a multiple of 2 MiB (131 072 robots) every row of a wavefront
-  // maps to the same HBM channels and the launch loses 17 % (131 072 x 8: 29.8 -> 24.7 us per step, 262 144: 46-54 -> 43.3;
-  // profiles/r04_stride_padding.txt: this was most of "the 131 072 anomaly").  Any pad of 64 .. 1 088 columns cures it
-  // alike; smaller batches are not padded (16 384: a pad costs 3-4 %).  CDPR_STRIDE_PAD=<columns> forces a pad (A/B).
-  if (h->stride % 131072u == 0u) h->stride += 128u;
-  if (const char* sp = std::getenv("CDPR_STRIDE_PAD")) h->stride = ((h->batch + 63u) & ~63u) + ((uint32_t)(std::max(0L, std::atol(sp)) + 63L) & ~63u);
-  {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-    plan = plan_kernels(*cfg, cus);  // (the general path's role-split limit follows the device's CU count)
-    h->cus = cus;
-  }
-  h->plan = plan;
-  const bool general = plan.general;
-  h->fk = plan.fk;
-  h->td = plan.td;
-  h->dbg = (cfg->stages & CDPR_STAGE_PID_DEBUG) != 0;
-  h->general = plan.general;  // (precision = 64 with the hold branch: the fp64 kernel's HOLD instantiations, not the fp32 general path)
-  h->fp64 = plan.fp64;
-  h->hold64 = plan.hold64;
-  h->tstop64 = plan.tstop64;
-  h->win64 = plan.long64 ? kWinLong : kWin;
-  h->hold_win = plan.hold_long ? kHoldWinLong : kHoldWin;
-  h->per_robot = plan.per_robot;
-  h->phys = plan.phys;
-  h->lane_pair = plan.lane_pair;
-  h->lane_cable = plan.lane_cable;
-  h->lowreg = plan.lowreg;
-  h->chunk = plan.chunk;
-  h->persist = plan.persist;
-  if (h->persist) {
-    h->persist_grid = (uint32_t)h->cus * 4u;
-    if (const char* pg = std::getenv("CDPR_PERSIST_GRID")) h->persist_grid = (uint32_t)std::max(1L, std::atol(pg));
-  }
-  h->onestep_v2 = plan.onestep_v2;
-  h->split = plan.split;
-  h->gen_split = plan.gen_split;
-  h->gen_lean = plan.gen_lean;
-  h->gen_hot = plan.gen_hot;
-  h->pair_stream = plan.pair_stream;
-  h->n_state = general ? plat_slots(h->fk) : state_slots((int)h->n, h->fk);
-  h->n_obs = obs_slots((int)h->n);
-  memset(&h->base, 0, sizeof h->base);
-  fill_consts(*cfg, h->base);
-  auto& wtab_host = h->wtab_host;
-  fill_pid(cfg->velocity_pid, cfg->dt, h->pid_vel, wtab_host[0]);
-  fill_pid(cfg->position_pid, cfg->dt, h->pid_pos, wtab_host[1]);
-  engine_reset_host(h);
-  {
-    const char* ng = std::getenv("CDPR_NO_GRAPH");
-    h->use_graphs = !(ng && ng[0] == '1');
-  }
-
-  auto fail = [&](const char* what, hipError_t code) {
-    g_create_error = std::string(what) + ": " + hipGetErrorString(code);
-    free_all(h);
-    return code == hipErrorOutOfMemory ? CDPR_ERR_NOMEM : CDPR_ERR_DEVICE;
-  };
-  if ((e = hipSetDevice(device)) != hipSuccess) return fail("hipSetDevice", e);
-  if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return fail("hipStreamCreate", e);
-  if ((e = hipEventCreate(&h->ev0)) != hipSuccess) return fail("hipEventCreate", e);
-  if ((e = hipEventCreate(&h->ev1)) != hipSuccess) return fail("hipEventCreate", e);
-  const size_t slot_bytes = (size_t)h->stride * sizeof(float4);
-  if (h->fp64) {
-    const size_t row = (size_t)h->stride * sizeof(double);
-    if ((e = hipMalloc(&h->d_state64, row * state64_rows(h))) != hipSuccess) return fail("hipMalloc(state64)", e);
-    if ((e = hipMalloc(&h->d_obs64, row * f64_obs_rows((int)h->n))) != hipSuccess) return fail("hipMalloc(obs64)", e);
-    const int W64 = h->win64;  // ring length of this handle's fp64 kernels (10, or 31 with windows of 12 .. 32 samples)
-    std::vector<double> g((size_t)h->n * 7), wt((size_t)2 * W64 * (W64 + 2), 0.0);
-    for (uint32_t i = 0; i < h->n; ++i) {
-      for (int k = 0; k < 3; ++k) {
-        g[(size_t)i * 7 + k] = cfg->frame_anchor[i][k];
-        g[(size_t)i * 7 + 3 + k] = cfg->platform_anchor[i][k];
-      }
-      g[(size_t)i * 7 + 6] = cfg->cable_ref_length[i];
-    }
-    const cdpr_pid_params_t* pids[2] = {&cfg->velocity_pid, &cfg->position_pid};
-    for (int t = 0; t < 2; ++t) {  // the rotated weight tables of fill_pid, in double
-      double w[CDPR_MAX_D_BUFFER];
-      std::vector<double> wpad((size_t)W64 + 1, 0.0);
-      if (derivative_weights(pids[t]->d_buffer_length, pids[t]->d_degree, w) == CDPR_OK && pids[t]->d_buffer_length <= (uint32_t)W64 + 1)
-        for (uint32_t j = 0; j < pids[t]->d_buffer_length; ++j) wpad[(size_t)W64 + 1 - pids[t]->d_buffer_length + j] = w[j];
-      double* tab = &wt[(size_t)t * W64 * (W64 + 2)];
-      for (int ws = 0; ws < W64; ++ws) {
-        for (int sl = 0; sl < W64; ++sl) {
-          int j = ((ws - sl) % W64 + W64) % W64;
-          if (j == 0) j = W64;
-          tab[ws * (W64 + 2) + sl] = wpad[(size_t)W64 - j];
-        }
-        tab[ws * (W64 + 2) + W64] = wpad[(size_t)W64];
-      }
-    }
-    if ((e = hipMalloc(&h->d_geom64, g.size() * sizeof(double))) != hipSuccess) return fail("hipMalloc(geom64)", e);
-    if ((e = hipMemcpy(h->d_geom64, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) return fail("hipMemcpy(geom64)", e);
-    if ((e = hipMalloc(&h->d_wtab64, wt.size() * sizeof(double))) != hipSuccess) return fail("hipMalloc(wtab64)", e);
-    if ((e = hipMemcpy(h->d_wtab64, wt.data(), wt.size() * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) return fail("hipMemcpy(wtab64)", e);
-    if (h->dbg && (e = hipMalloc(&h->d_dbg64, (size_t)h->batch * CDPR_PID_DEBUG_AXES * sizeof(double))) != hipSuccess) return fail("hipMalloc(dbg64)", e);
-    F64Args& b = h->base64;
-    memset(&b, 0, sizeof b);
-    b.state = h->d_state64; b.obs = h->d_obs64; b.dbg = h->d_dbg64; b.geom = h->d_geom64;
-    b.batch = h->batch; b.stride = h->stride;
-    b.fk = h->fk ? 1 : 0; b.td = h->td ? 1 : 0;
-    b.dt = cfg->dt; b.half_dt = 0.5 * cfg->dt; b.inv_mass = 1.0 / cfg->mass;
-    b.fgx = cfg->mass * cfg->gravity[0]; b.fgy = cfg->mass * cfg->gravity[1]; b.fgz = cfg->mass * cfg->gravity[2];
-    double inv6[6];
-    mat3_inverse_sym(cfg->inertia, inv6);
-    for (int i = 0; i < 6; ++i) { b.ib[i] = cfg->inertia[i]; b.ibinv[i] = inv6[i]; }
-    b.damping = cfg->joint_damping; b.effort = cfg->effort_limit; b.vel_limit = cfg->velocity_limit;
-    b.unilateral = cfg->unilateral_cables ? 1 : 0;
-    b.travel_on = (cfg->travel_lower != 0.0 || cfg->travel_upper != 0.0) ? 1 : 0;
-    b.travel_lo = cfg->travel_lower; b.travel_hi = cfg->travel_upper;
-    b.ph_lumped = (cfg->passive_damping != 0.0 || cfg->leg_inertia != 0.0 || cfg->cable_axial_mass != 0.0 || cfg->anchor_point_mass != 0.0 || cfg->anchor_inertia != 0.0) ? 1 : 0;
-    b.ph_c = cfg->passive_damping; b.ph_jleg = cfg->leg_inertia; b.ph_max = cfg->cable_axial_mass; b.ph_mpt = cfg->anchor_point_mass;
-    b.ph_iadd_total = cfg->anchor_inertia * (double)cfg->n_cables; b.ph_mass = cfg->mass;
-    b.gx = cfg->gravity[0]; b.gy = cfg->gravity[1]; b.gz = cfg->gravity[2];
-    b.fk_lambda = cfg->fk_lambda; b.fk_tol = cfg->fk_tolerance; b.fk_iters = (int)cfg->fk_max_iterations;
-    b.td_min = cfg->td_f_min; b.td_max = cfg->td_f_max; b.td_mid = 0.5 * (cfg->td_f_min + cfg->td_f_max);
-  } else {
-    if ((e = hipMalloc(&h->d_state, slot_bytes * h->n_state)) != hipSuccess) return fail("hipMalloc(state)", e);
-    if ((e = hipMalloc(&h->d_obs, slot_bytes * h->n_obs)) != hipSuccess) return fail("hipMalloc(obs)", e);
-  }
-  const size_t cmd_bytes = (size_t)h->stride * h->n * sizeof(float);
-  for (int i = 0; i < 2; ++i)
-    for (CmdChannel& c : h->cmd) {
-      if ((e = hipMalloc(&c.d[i], cmd_bytes)) != hipSuccess) return fail("hipMalloc(cmd)", e);
-      (void)hipMemset(c.d[i], 0, cmd_bytes);
-    }
-  if ((e = hipMalloc(&h->d_wtab, sizeof wtab_host)) != hipSuccess) return fail("hipMalloc(wtab)", e);
-  if ((e = hipMemcpy(h->d_wtab, wtab_host, sizeof wtab_host, hipMemcpyHostToDevice)) != hipSuccess) return fail("hipMemcpy(wtab)", e);
-  h->pid_vel.wtab = h->d_wtab;
-  h->pid_pos.wtab = h->d_wtab + kWin * (kWin + 2);
-  {
-    std::vector<float> g = geom_pairs(*cfg);
-    if ((e = hipMalloc(&h->d_geom, g.size() * sizeof(float))) != hipSuccess) return fail("hipMalloc(geom)", e);
-    if ((e = hipMemcpy(h->d_geom, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return fail("hipMemcpy(geom)", e);
-  }
-  if (h->general) {
-    h->glay.n = (int)h->n;
-    h->glay.nb = (int)std::max(cfg->velocity_pid.d_buffer_length, cfg->position_pid.d_buffer_length);
-    h->glay.ncas = (int)std::max(std::max(cfg->velocity_pid.p_filter.cascade, cfg->velocity_pid.d_filter.cascade),
-                                 std::max(cfg->position_pid.p_filter.cascade, cfg->position_pid.d_filter.cascade));
-    const size_t rec_bytes = h->glay.bytes(h->stride);
-    if (rec_bytes >= (1ull << 32)) {  // the record buffer is addressed with 32-bit offsets (one buffer resource)
-      g_create_error = "general controller path: the controller records of this batch pass 4 GiB; split the batch over several handles";
-      free_all(h);
-      return CDPR_ERR_UNSUPPORTED;
-    }
-    if ((e = hipMalloc(&h->d_rec, rec_bytes)) != hipSuccess) return fail("hipMalloc(rec)", e);
-    fill_gen_pid(cfg->position_pid, h->gpid[0]);
-    fill_gen_pid(cfg->velocity_pid, h->gpid[1]);
-    // FIR weights by ring head: when the newest sample sits in slot `head`, slot j holds the sample of age (head - j) mod
-    // nbuf, whose end-point LS weight (oldest first) is w[nbuf - 1 - age]; slots >= nbuf weigh nothing.  The head slot itself
-    // weighs nothing in the table: the newest sample is still in a register when the FIR runs, its weight rides in the Pid
-    // table (last float)
-    const int nbmax = h->glay.nb > 11 ? kGenMaxBuf : 11, nbp = gen_nbp(nbmax);
-    std::vector<float> wt((size_t)2 * nbmax * nbp, 0.f);
-    const cdpr_pid_params_t* pp[2] = {&cfg->position_pid, &cfg->velocity_pid};
-    float w_new[2] = {0.f, 0.f};
-    for (int p = 0; p < 2; ++p) {
-      double w[CDPR_MAX_D_BUFFER];
-      const int nb = (int)pp[p]->d_buffer_length;
-      if (derivative_weights((uint32_t)nb, pp[p]->d_degree, w) != CDPR_OK) continue;
-      for (int head = 0; head < nb; ++head)
-        for (int j = 0; j < nb; ++j) wt[((size_t)p * nbmax + head) * nbp + j] = (j == head) ? 0.f : (float)w[nb - 1 - (((head - j) % nb + nb) % nb)];
-      w_new[p] = (float)w[nb - 1];
-    }
-    float pt[2 * kGenPidFloats];
-    gen_pid_table(h->gpid[0], pt);
-    gen_pid_table(h->gpid[1], pt + kGenPidFloats);
-    pt[kGenPidFloats - 1] = w_new[0], pt[2 * kGenPidFloats - 1] = w_new[1];
-    if ((e = hipMalloc(&h->d_gptab, sizeof pt)) != hipSuccess) return fail("hipMalloc(gptab)", e);
-    if ((e = hipMemcpy(h->d_gptab, pt, sizeof pt, hipMemcpyHostToDevice)) != hipSuccess) return fail("hipMemcpy(gptab)", e);
-    if ((e = hipMalloc(&h->d_gwtab, wt.size() * sizeof(float))) != hipSuccess) return fail("hipMalloc(gwtab)", e);
-    if ((e = hipMemcpy(h->d_gwtab, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return fail("hipMemcpy(gwtab)", e);
-  }
-  if (h->per_robot) {
-    if (!h->general && (e = hipMalloc(&h->d_target, cmd_bytes)) != hipSuccess) return fail("hipMalloc(target)", e);
-    if ((e = hipMalloc(&h->d_mode, h->batch)) != hipSuccess) return fail("hipMalloc(mode)", e);
-    for (CmdChannel& c : h->cmd)
-      if ((e = hipMalloc(&c.d_mask, h->batch)) != hipSuccess) return fail("hipMalloc(mask)", e);
-  }
-  if (h->dbg && !h->fp64)
-    if ((e = hipMalloc(&h->d_dbg, (size_t)h->batch * CDPR_PID_DEBUG_AXES * sizeof(float))) != hipSuccess)
-      return fail("hipMalloc(dbg)", e);
-  if (upload_home(h) != CDPR_OK || warm_first_launch(h) != CDPR_OK) {
+  if (hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->cus <= 0) h->cus = 256;
+  h->plan = plan_kernels(*cfg, h->cus);  // (the general path's role-split limit follows the device's CU count)
+  // every failure from here on releases what the handle has got so far and leaves *out null
+  const int rc = build_handle(h);
+  if (rc != CDPR_OK) {
     g_create_error = h->err;
     free_all(h);
-    return CDPR_ERR_DEVICE;
+    return rc;
   }
   *out = h;
   return CDPR_OK;
@@ -1237,13 +1075,13 @@ int cdpr_reset(cdpr_handle_t h) {
 int cdpr_set_platform_state(cdpr_handle_t h, const float* pose7, const float* twist6) {
   if (!h) return CDPR_ERR_INVALID;
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  if (h->fp64) {
+  if (h->plan.fp64) {
     std::vector<double> p, t;
     if (pose7) p.assign(pose7, pose7 + (size_t)h->batch * 7);
     if (twist6) t.assign(twist6, twist6 + (size_t)h->batch * 6);
     return set_platform_state64(h, pose7 ? p.data() : nullptr, twist6 ? t.data() : nullptr);
   }
-  const int P = plat_slots(h->fk);
+  const int P = plat_slots(h->plan.fk);
   std::vector<float4> s;
   int rc = fetch_slots(h, h->d_state, P, s);
   if (rc != CDPR_OK) return rc;
@@ -1255,7 +1093,7 @@ int cdpr_set_platform_state(cdpr_handle_t h, const float* pose7, const float* tw
       a = make_float4(p[0], p[1], p[2], p[3]);
       b.x = p[4]; b.y = p[5]; b.z = p[6];
       d.y = p[0]; d.z = p[1]; d.w = p[2];  // the FK seed follows the spawn pose
-      if (h->fk) s[4 * st + r] = make_float4(p[3], p[4], p[5], p[6]);
+      if (h->plan.fk) s[4 * st + r] = make_float4(p[3], p[4], p[5], p[6]);
     }
     if (twist6) {
       const float* t = twist6 + (size_t)r * 6;
@@ -1276,7 +1114,7 @@ static int stage_masked(cdpr_engine* h, int kind, const float* axes, size_t coun
     h->err = "null command buffer";
     return CDPR_ERR_INVALID;
   }
-  if (!h->per_robot) {
+  if (!h->plan.per_robot) {
     h->err = "masked commands need a handle created with per_robot_commands = 1";
     return CDPR_ERR_UNSUPPORTED;
   }
@@ -1335,7 +1173,7 @@ static int bind_command(cdpr_engine* h, int kind, const float* d_axes, size_t co
     return CDPR_ERR_INVALID;
   }
   if (count != (size_t)h->n * h->batch) return CDPR_IGNORED;  // one Joy per robot; no broadcast without a copy
-  if (h->per_robot) {
+  if (h->plan.per_robot) {
     h->err = "cdpr_bind_*_command_device: not available on a per_robot_commands handle (commands are latched robot by robot)";
     return CDPR_ERR_UNSUPPORTED;
   }
@@ -1372,7 +1210,7 @@ int cdpr_update_fused(cdpr_handle_t h, int nsteps, int steps_per_launch) { retur
 
 // One observable image: fp32 handles n_obs float4 slot rows, precision = 64 handles f64_obs_rows(n) rows of doubles
 static size_t image_bytes(const cdpr_engine* h) {
-  return h->fp64 ? (size_t)f64_obs_rows((int)h->n) * h->stride * sizeof(double) : (size_t)h->n_obs * h->stride * sizeof(float4);
+  return h->plan.fp64 ? (size_t)f64_obs_rows((int)h->n) * h->stride * sizeof(double) : (size_t)h->n_obs * h->stride * sizeof(float4);
 }
 
 int cdpr_observable_image_bytes(cdpr_handle_t h, size_t* bytes) {
@@ -1416,7 +1254,7 @@ static int scheduled_update(cdpr_engine* h, uint32_t kind, int nsteps, int refre
     h->err = "cdpr_update_scheduled: nsteps >= 0, refresh_steps >= 1 and the command schedule are required";
     return CDPR_ERR_INVALID;
   }
-  if (d_masks && !h->per_robot) {
+  if (d_masks && !h->plan.per_robot) {
     h->err = "cdpr_update_scheduled_kind: robot masks need a handle created with per_robot_commands = 1";
     return CDPR_ERR_UNSUPPORTED;
   }
@@ -1432,7 +1270,7 @@ static int scheduled_update(cdpr_engine* h, uint32_t kind, int nsteps, int refre
   if (nsteps == 0) return CDPR_OK;
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
   if (d_ready && !h->h_fault) {  // the status word a mailbox that never delivers is reported through
-    HIP_TRY(h, hipHostMalloc((void**)&h->h_fault, sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(h, h->h_fault.alloc(sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
     *h->h_fault = 0u;
     HIP_TRY(h, hipHostGetDevicePointer((void**)&h->d_fault, h->h_fault, 0));
   }
@@ -1443,7 +1281,7 @@ static int scheduled_update(cdpr_engine* h, uint32_t kind, int nsteps, int refre
   // batch j becomes the pending command of `kind`, in place
   auto stage_batch = [&](int j) {
     const float* rows = d_commands + (size_t)j * batch_floats;
-    if (h->per_robot) {
+    if (h->plan.per_robot) {
       c.sched_rows = rows;
       c.sched_mask = d_masks ? d_masks + (size_t)j * h->batch : nullptr;
     } else {
@@ -1456,7 +1294,7 @@ static int scheduled_update(cdpr_engine* h, uint32_t kind, int nsteps, int refre
   // would have to reach its robots before batch 0 reaches batch 0's - B independent plugins each keep the last message that
   // reached THEM.  Staging batch 0 would overwrite it silently: refused, the caller latches it with cdpr_update first
   // or leaves it out.  (Uniform handles: the later message of a kind replaces the earlier one, as in the plugin, PLG.cpp:67-83.)
-  if (h->per_robot && c.pending) {
+  if (h->plan.per_robot && c.pending) {
     h->err = "cdpr_update_scheduled_kind: a command of the same kind is still pending on this per-robot handle; step it in with cdpr_update first";
     return CDPR_ERR_INVALID;
   }
@@ -1470,12 +1308,12 @@ static int scheduled_update(cdpr_engine* h, uint32_t kind, int nsteps, int refre
       h->sched_refresh = 0;
       h->sched_ready = nullptr;
       if (!ok) {  // an error in between: drop the batch that was staged but not latched
-        if (c.pending && (h->per_robot || c.ext[1])) c.pending = false;
+        if (c.pending && (h->plan.per_robot || c.ext[1])) c.pending = false;
         c.ext[1] = nullptr;
       }
     }
   } unstage{h, c};
-  const bool in_launch = !(h->general || h->fp64 || h->per_robot || h->lane_cable) && h->cfg.publish_period == 0.0;
+  const bool in_launch = !(h->plan.general || h->plan.fp64 || h->plan.per_robot || h->plan.lane_cable) && h->cfg.publish_period == 0.0;
   bool others = false;
   for (uint32_t k = 0; k < (uint32_t)kCmdKinds; ++k) others = others || (k != kind && h->cmd[k].pending);
   int j = 0, done = 0;
@@ -1501,7 +1339,7 @@ static int scheduled_update(cdpr_engine* h, uint32_t kind, int nsteps, int refre
     h->sched_refresh = refresh_steps;
     h->sched_ready = d_ready ? d_ready + j : nullptr;
     int rest = nsteps - done;
-    if (h->lane_pair && h->pair_stream && !h->fk && !h->td && kind != CDPR_COMMAND_FORCE) {
+    if (h->plan.lane_pair && h->plan.pair_stream && !h->plan.fk && !h->plan.td && kind != CDPR_COMMAND_FORCE) {
       const int new_mode = (kind == CDPR_COMMAND_VELOCITY) ? kModeVelocity : kModePosition;
       const int nbuf = (kind == CDPR_COMMAND_VELOCITY) ? h->pid_vel.nbuf : h->pid_pos.nbuf;
       const int calls = (h->mode == new_mode) ? h->pid_calls : 0;  // (entering the mode resets the Pid)
@@ -1536,18 +1374,20 @@ int cdpr_update_scheduled_kind(cdpr_handle_t h, uint32_t kind, int nsteps, int r
 int cdpr_decode_observables(cdpr_handle_t h, const void* image, float* position, float* velocity, float* effort,
                             float* pose7, float* twist6) {
   if (!h || !image) return CDPR_ERR_INVALID;
-  if (h->fp64) {  // (the float getters of a precision = 64 handle round)
+  if (h->plan.fp64) {  // (the float getters of a precision = 64 handle round)
     decode_image64_to_float(h, static_cast<const double*>(image), position, velocity, effort, pose7, twist6);
     return CDPR_OK;
   }
   const float4* o = static_cast<const float4*>(image);
   const size_t st = h->stride;
-  const int G = joint_groups((int)h->n);
   float* dst[3] = {position, velocity, effort};
   for (int f = 0; f < 3; ++f) {
     if (!dst[f]) continue;
     for (uint32_t r = 0; r < h->batch; ++r)
-      for (uint32_t i = 0; i < h->n; ++i) dst[f][(size_t)r * h->n + i] = comp(o[(size_t)(4 + f * G + i / 4) * st + r], i % 4);
+      for (uint32_t i = 0; i < h->n; ++i) {
+        const std::pair<int, int> sc = obs_joint_field((int)h->n, f, i);
+        dst[f][(size_t)r * h->n + i] = comp(o[(size_t)sc.first * st + r], sc.second);
+      }
   }
   for (uint32_t r = 0; r < h->batch; ++r) {
     const float4 a = o[0 * st + r], b = o[1 * st + r], c = o[2 * st + r], d = o[3 * st + r];
@@ -1600,7 +1440,7 @@ int cdpr_kernel_name(cdpr_handle_t h, char* name, size_t len) {
 }
 
 uint32_t cdpr_mapping(cdpr_handle_t h) {
-  return !h ? CDPR_MAP_AUTO : (h->lane_cable ? CDPR_MAP_LANE_PER_CABLE : h->lane_pair ? CDPR_MAP_LANE_PAIR : CDPR_MAP_LANE_PER_ROBOT);
+  return !h ? CDPR_MAP_AUTO : (h->plan.lane_cable ? CDPR_MAP_LANE_PER_CABLE : h->plan.lane_pair ? CDPR_MAP_LANE_PAIR : CDPR_MAP_LANE_PER_ROBOT);
 }
 
 uint64_t cdpr_step_count(cdpr_handle_t h) { return h ? h->step : 0; }
@@ -1608,12 +1448,11 @@ uint64_t cdpr_step_count(cdpr_handle_t h) { return h ? h->step : 0; }
 int cdpr_get_joint_states(cdpr_handle_t h, float* position, float* velocity, float* effort) {
   if (!h) return CDPR_ERR_INVALID;
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  if (h->fp64) return checked(h, fetch_observables64(h, position, velocity, effort, nullptr, nullptr, true));
-  const int G = joint_groups((int)h->n);
+  if (h->plan.fp64) return checked(h, fetch_observables64(h, position, velocity, effort, nullptr, nullptr, true));
   float* dst[3] = {position, velocity, effort};
   for (int f = 0; f < 3; ++f) {
     std::vector<std::pair<int, int>> fields;
-    for (uint32_t i = 0; i < h->n; ++i) fields.push_back({4 + f * G + (int)(i / 4), (int)(i % 4)});
+    for (uint32_t i = 0; i < h->n; ++i) fields.push_back(obs_joint_field((int)h->n, f, i));
     int rc = fetch_fields(h, h->d_obs, fields, dst[f]);
     if (rc != CDPR_OK) return rc;
   }
@@ -1626,7 +1465,7 @@ int cdpr_get_joint_states(cdpr_handle_t h, float* position, float* velocity, flo
 int cdpr_get_observables(cdpr_handle_t h, float* position, float* velocity, float* effort, float* pose7, float* twist6) {
   if (!h) return CDPR_ERR_INVALID;
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  if (h->fp64) return checked(h, fetch_observables64(h, position, velocity, effort, pose7, twist6, true));
+  if (h->plan.fp64) return checked(h, fetch_observables64(h, position, velocity, effort, pose7, twist6, true));
   const uint32_t n = h->n, width = 3u * n + 13u;
   if (width > kPublishMaxWidth) {  // (the kernel argument holds kPublishMaxWidth (slot, component) pairs)
     h->err = "cdpr_get_observables: more columns than the publish kernel's field table holds";
@@ -1636,31 +1475,23 @@ int cdpr_get_observables(cdpr_handle_t h, float* position, float* velocity, floa
   // lazy set-up, every allocation guarded on its own pointer (a failure half way leaves nothing to leak or to skip next
   // time).  Coherent host memory: the host spins on the completion word while the kernel is still running.
   if (!h->h_pub && count * sizeof(float) <= (2u << 20))  // the pinned image serves the two small tiers only
-    HIP_TRY(h, hipHostMalloc((void**)&h->h_pub, count * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(h, h->h_pub.alloc(count * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
   if (!h->h_pub_done) {
-    HIP_TRY(h, hipHostMalloc((void**)&h->h_pub_done, sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(h, h->h_pub_done.alloc(sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent));
     *h->h_pub_done = 0;
   }
   if (!h->d_pub_arrivals) {
-    HIP_TRY(h, hipMalloc(&h->d_pub_arrivals, sizeof(uint32_t)));
+    HIP_TRY(h, h->d_pub_arrivals.alloc(sizeof(uint32_t)));
     hipError_t me = hipMemsetAsync(h->d_pub_arrivals, 0, sizeof(uint32_t), h->stream);
     if (me != hipSuccess) {  // never launch the publish kernel on an uninitialised arrival counter
-      (void)hipFree(h->d_pub_arrivals);
-      h->d_pub_arrivals = nullptr;
+      h->d_pub_arrivals.release();
       HIP_TRY(h, me);
     }
   }
   // small images go straight to host memory from the gather kernel (a per-step caller of a few robots: ~5 us); large
   // ones through device scratch and the copy engine (kernel stores over PCIe reach ~7 GB/s, the copy engine ~30)
   const bool direct = count * sizeof(float) <= (256u << 10);
-  if (!direct && h->unpack_cap < count) {
-    HIP_TRY(h, wait_stream(h));
-    if (h->d_unpack) (void)hipFree(h->d_unpack);
-    h->d_unpack = nullptr;
-    h->unpack_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->d_unpack, count * sizeof(float)));
-    h->unpack_cap = count;
-  }
+  if (!direct) HIP_TRY(h, h->d_unpack.ensure(h, count * sizeof(float)));
   PublishArgs u{};
   u.rows = h->d_obs;
   if (direct) {
@@ -1676,12 +1507,11 @@ int cdpr_get_observables(cdpr_handle_t h, float* position, float* velocity, floa
   u.batch = h->batch;
   u.n = n;
   u.width = width;
-  const int G = joint_groups((int)n);
   uint32_t j = 0;
   for (int f = 0; f < 3; ++f)
     for (uint32_t i = 0; i < n; ++i, ++j) {
-      u.slot[j] = (uint8_t)(4 + f * G + (int)(i / 4));
-      u.comp[j] = (uint8_t)(i % 4);
+      const std::pair<int, int> sc = obs_joint_field((int)n, f, i);
+      u.slot[j] = (uint8_t)sc.first, u.comp[j] = (uint8_t)sc.second;
     }
   for (const auto& pc : kPoseFields) u.slot[j] = (uint8_t)pc.first, u.comp[j] = (uint8_t)pc.second, ++j;
   for (const auto& pc : kTwistFields) u.slot[j] = (uint8_t)pc.first, u.comp[j] = (uint8_t)pc.second, ++j;
@@ -1730,7 +1560,7 @@ int cdpr_get_observables(cdpr_handle_t h, float* position, float* velocity, floa
 int cdpr_get_platform_state(cdpr_handle_t h, float* pose7, float* twist6) {
   if (!h) return CDPR_ERR_INVALID;
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  if (h->fp64) return checked(h, fetch_observables64(h, nullptr, nullptr, nullptr, pose7, twist6, true));
+  if (h->plan.fp64) return checked(h, fetch_observables64(h, nullptr, nullptr, nullptr, pose7, twist6, true));
   const int rc = fetch_platform(h, h->d_obs, pose7, twist6);
   return rc != CDPR_OK ? rc : check_fault(h);
 }
@@ -1738,9 +1568,9 @@ int cdpr_get_platform_state(cdpr_handle_t h, float* pose7, float* twist6) {
 int cdpr_get_raw_state(cdpr_handle_t h, float* pose7, float* twist6) {
   if (!h) return CDPR_ERR_INVALID;
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  if (h->fp64) {
-    int rc = fetch_rows64(h, h->d_state64, 0, 7, pose7, true);
-    return rc != CDPR_OK ? rc : checked(h, fetch_rows64(h, h->d_state64, 7, 6, twist6, true));
+  if (h->plan.fp64) {
+    int rc = fetch_rows64(h, h->d_state64, kF64Pose, 7, pose7, true);
+    return rc != CDPR_OK ? rc : checked(h, fetch_rows64(h, h->d_state64, kF64Twist, 6, twist6, true));
   }
   const int rc = fetch_platform(h, h->d_state, pose7, twist6);
   return rc != CDPR_OK ? rc : check_fault(h);
@@ -1753,7 +1583,7 @@ int cdpr_get_pid_debug(cdpr_handle_t h, float* axes9) {
     return CDPR_ERR_UNSUPPORTED;
   }
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  if (h->fp64) {
+  if (h->plan.fp64) {
     std::vector<double> d((size_t)h->batch * CDPR_PID_DEBUG_AXES);
     HIP_TRY(h, hipMemcpyAsync(d.data(), h->d_dbg64, d.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, wait_stream(h));
@@ -1768,15 +1598,15 @@ int cdpr_get_pid_debug(cdpr_handle_t h, float* axes9) {
 
 int cdpr_get_fk_state(cdpr_handle_t h, float* pose7, float* residual, int32_t* iterations) {
   if (!h) return CDPR_ERR_INVALID;
-  if (!h->fk) {
+  if (!h->plan.fk) {
     h->err = "CDPR_STAGE_FK not enabled";
     return CDPR_ERR_UNSUPPORTED;
   }
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  if (h->fp64) {
-    int rc = fetch_rows64(h, h->d_state64, 13, 7, pose7, true);
-    if (rc == CDPR_OK) rc = fetch_rows64(h, h->d_obs64, 13, 1, residual, true);
-    return rc != CDPR_OK ? rc : checked(h, fetch_int_row64(h, 14, iterations));
+  if (h->plan.fp64) {
+    int rc = fetch_rows64(h, h->d_state64, kF64StateFk, 7, pose7, true);
+    if (rc == CDPR_OK) rc = fetch_rows64(h, h->d_obs64, kF64ObsResidual, 1, residual, true);
+    return rc != CDPR_OK ? rc : checked(h, fetch_int_row64(h, kF64ObsIterations, iterations));
   }
   // estimate: state slot 3 yzw + slot 4 xyzw; residual / iteration count: observable slot 3 y, z
   int rc = fetch_fields(h, h->d_state, {{3, 1}, {3, 2}, {3, 3}, {4, 0}, {4, 1}, {4, 2}, {4, 3}}, pose7);
@@ -1788,13 +1618,13 @@ int cdpr_get_fk_state(cdpr_handle_t h, float* pose7, float* residual, int32_t* i
 
 int cdpr_get_td_state(cdpr_handle_t h, float* tension, int32_t* infeasible) {
   if (!h) return CDPR_ERR_INVALID;
-  if (!h->td) {
+  if (!h->plan.td) {
     h->err = "CDPR_STAGE_TD not enabled";
     return CDPR_ERR_UNSUPPORTED;
   }
   int rc = cdpr_get_joint_states(h, nullptr, nullptr, tension);  // applied force == distributed tension
   if (rc != CDPR_OK) return rc;
-  rc = h->fp64 ? fetch_int_row64(h, 15, infeasible) : fetch_fields(h, h->d_obs, {{3, 3}}, infeasible, 1u);
+  rc = h->plan.fp64 ? fetch_int_row64(h, kF64ObsFlags, infeasible) : fetch_fields(h, h->d_obs, {{3, 3}}, infeasible, 1u);
   if (rc == CDPR_OK && infeasible)
     for (uint32_t b = 0; b < h->batch; ++b) infeasible[b] &= 1;  // the travel-limit mask shares the component (pack_flags)
   return checked(h, rc);
@@ -1803,7 +1633,7 @@ int cdpr_get_td_state(cdpr_handle_t h, float* tension, int32_t* infeasible) {
 int cdpr_get_limit_state(cdpr_handle_t h, uint32_t* cable_mask) {
   if (!h || !cable_mask) return CDPR_ERR_INVALID;
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  int rc = h->fp64 ? fetch_int_row64(h, 15, reinterpret_cast<int32_t*>(cable_mask)) : fetch_fields(h, h->d_obs, {{3, 3}}, cable_mask, 1u);
+  int rc = h->plan.fp64 ? fetch_int_row64(h, kF64ObsFlags, reinterpret_cast<int32_t*>(cable_mask)) : fetch_fields(h, h->d_obs, {{3, 3}}, cable_mask, 1u);
   if (rc == CDPR_OK)
     for (uint32_t b = 0; b < h->batch; ++b) cable_mask[b] >>= 1;  // bit 0 is the tension-distribution flag
   return checked(h, rc);
@@ -1869,8 +1699,5 @@ int cdpr_profile_end(cdpr_handle_t h, float* elapsed_ms, uint64_t* kernel_launch
   if (kernel_launches) *kernel_launches = h->launches - h->launches_mark;
   return CDPR_OK;
 }
-
-#undef UP
-#undef DOWN
 
 }  // extern "C"

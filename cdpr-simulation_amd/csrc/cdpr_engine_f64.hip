@@ -1,11 +1,41 @@
-// cdpr_engine_f64.hip - host side of cdpr_config_t.precision = 64: the launch chain of the fp64 step kernels (cdpr_step_kernel_f64.hpp),
-// their read-out and the rollout by composition.  Reference paths as in cdpr_engine.hip.
+// cdpr_engine_f64.hip - host side of cdpr_config_t.precision = 64: the handle's set-up (build_f64), the launch chain of the fp64 step
+// kernels (cdpr_step_kernel_f64.hpp), their read-out and the rollout by composition.  Reference paths as in cdpr_engine.hip.
 #include "cdpr_engine_internal.hpp"
 
 namespace cdpr_host {
 
 // rows of an fp64 handle's state: platform, FK estimate, one Pid's rows per cable - and, hold branch live, both Pids' records
-size_t state64_rows(const cdpr_engine* h) { return (size_t)f64_state_rows((int)h->n, h->win64) + (h->hold64 ? (size_t)f64_hold_rows((int)h->n, h->hold_win) : 0); }
+size_t state64_rows(const cdpr_engine* h) { return (size_t)f64_state_rows((int)h->n, win64(h)) + (h->plan.hold64 ? (size_t)f64_hold_rows((int)h->n, hold_win(h)) : 0); }
+
+// cdpr_create's part of a precision = 64 handle: state and observables in double, the cable geometry, the two Pids' rotated weight
+// tables for the ring of this handle's kernels (10, or 31 with windows of 12 .. 32 samples), the debug rows, the constants of a launch
+int build_f64(cdpr_engine* h) {
+  const cdpr_config_t& cfg = h->cfg;
+  const size_t row = (size_t)h->stride * sizeof(double);
+  CREATE_TRY(h, "hipMalloc(state64)", h->d_state64.alloc(row * state64_rows(h)));
+  CREATE_TRY(h, "hipMalloc(obs64)", h->d_obs64.alloc(row * f64_obs_rows((int)h->n)));
+  const int W = win64(h);
+  std::vector<double> g((size_t)h->n * 7), wt((size_t)2 * W * (W + 2), 0.0);
+  for (uint32_t i = 0; i < h->n; ++i) {
+    for (int k = 0; k < 3; ++k) {
+      g[(size_t)i * 7 + k] = cfg.frame_anchor[i][k];
+      g[(size_t)i * 7 + 3 + k] = cfg.platform_anchor[i][k];
+    }
+    g[(size_t)i * 7 + 6] = cfg.cable_ref_length[i];
+  }
+  rotated_weights(cfg.velocity_pid, W, &wt[0]);
+  rotated_weights(cfg.position_pid, W, &wt[(size_t)W * (W + 2)]);
+  if (int rc = upload_table(h, h->d_geom64, g.data(), g.size() * sizeof(double), "geom64")) return rc;
+  if (int rc = upload_table(h, h->d_wtab64, wt.data(), wt.size() * sizeof(double), "wtab64")) return rc;
+  if (h->dbg) CREATE_TRY(h, "hipMalloc(dbg64)", h->d_dbg64.alloc((size_t)h->batch * CDPR_PID_DEBUG_AXES * sizeof(double)));
+  F64Args& b = h->base64;
+  memset(&b, 0, sizeof b);
+  b.state = h->d_state64; b.obs = h->d_obs64; b.dbg = h->d_dbg64; b.geom = h->d_geom64;
+  b.batch = h->batch; b.stride = h->stride;
+  b.fk = h->plan.fk ? 1 : 0; b.td = h->plan.td ? 1 : 0;
+  fill_physics<double>(cfg, b);
+  return CDPR_OK;
+}
 
 // fp64 handles: home state (platform at home, FK seed at home, controller rows zero), observables before the first publish
 int upload_home64(cdpr_engine* h) {
@@ -13,9 +43,9 @@ int upload_home64(cdpr_engine* h) {
   std::vector<double> s(state64_rows(h) * st, 0.0), o((size_t)f64_obs_rows((int)h->n) * st, 0.0);
   for (uint32_t r = 0; r < h->stride; ++r)
     for (int c = 0; c < 7; ++c) {
-      s[(size_t)c * st + r] = h->cfg.home_pose[c];
-      s[(size_t)(13 + c) * st + r] = h->cfg.home_pose[c];
-      o[(size_t)c * st + r] = h->cfg.home_pose[c];
+      s[(size_t)(kF64Pose + c) * st + r] = h->cfg.home_pose[c];
+      s[(size_t)(kF64StateFk + c) * st + r] = h->cfg.home_pose[c];
+      o[(size_t)(kF64Pose + c) * st + r] = h->cfg.home_pose[c];
     }
   HIP_TRY(h, hipMemcpyAsync(h->d_state64, s.data(), s.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(h->d_obs64, o.data(), o.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -40,10 +70,10 @@ void fill_pid64(const cdpr_pid_params_t& p, double dt, F64Args& k) {
 // The arguments of a launch that depend on the handle's mode, not on the step: the Pid(s), the command buffer, the weight table; per-robot
 // handles: both Pids and the meta row; HOLD handles: both Pids, the hold branch's parameters, the cascades' coefficients
 static void f64_mode_args(const cdpr_engine* h, bool vel, bool frc, F64Args& a) {
-  const bool pr = h->per_robot;
+  const bool pr = h->plan.per_robot;
   fill_pid64(vel ? h->cfg.velocity_pid : h->cfg.position_pid, h->cfg.dt, a);
   a.cmd = pr ? h->d_target : h->cmd[frc ? CDPR_COMMAND_FORCE : vel ? CDPR_COMMAND_VELOCITY : CDPR_COMMAND_POSITION].latched();
-  a.wtab = h->d_wtab64 + (vel ? 0 : h->win64 * (h->win64 + 2));
+  a.wtab = h->d_wtab64 + (vel ? 0 : win64(h) * (win64(h) + 2));
   if (pr) {  // mode, Pid call count and so the Pid per lane: the velocity Pid in the primary fields, the position Pid in alt_*
     F64Args p = h->base64;
     fill_pid64(h->cfg.position_pid, h->cfg.dt, p);
@@ -51,7 +81,7 @@ static void f64_mode_args(const cdpr_engine* h, bool vel, bool frc, F64Args& a) 
     a.alt_imax = p.imax, a.alt_imin = p.imin, a.alt_cmax = p.cmax, a.alt_cmin = p.cmin, a.alt_clamp_cmd = p.clamp_cmd;
     a.meta = h->d_mode;
   }
-  if (h->hold64) {  // both Pids alive: the velocity Pid in the primary fields, the position Pid in alt_*
+  if (h->plan.hold64) {  // both Pids alive: the velocity Pid in the primary fields, the position Pid in alt_*
     F64Args v = h->base64, p = h->base64;
     fill_pid64(h->cfg.velocity_pid, h->cfg.dt, v);
     fill_pid64(h->cfg.position_pid, h->cfg.dt, p);
@@ -64,16 +94,12 @@ static void f64_mode_args(const cdpr_engine* h, bool vel, bool frc, F64Args& a) 
     const cdpr_pid_params_t* pids[2] = {&h->cfg.position_pid, &h->cfg.velocity_pid};
     a.any_cas = a.max_cas = 0;
     a.any_noclamp = (!v.clamp_cmd || !p.clamp_cmd) ? 1 : 0;
-    for (int t = 0; t < 2; ++t) {  // BiQuad::SetFc(fc, fs = 1.0, q), Filter.h:130-140, in double
+    for (int t = 0; t < 2; ++t) {  // the cascades' coefficients (biquad_coefficients), zero where a filter has no stage
       const cdpr_filter_params_t* fl[2] = {&pids[t]->p_filter, &pids[t]->d_filter};
       double* co[2] = {a.pcoef[t], a.dcoef[t]};
       for (int f = 0; f < 2; ++f) {
         for (int c = 0; c < 5; ++c) co[f][c] = 0.0;
-        if (!fl[f]->cascade) continue;
-        const double k = std::tan(M_PI * fl[f]->rel_cutoff / 1.0);
-        const double den = k * k + k / fl[f]->quality + 1.0;
-        co[f][0] = k * k / den, co[f][1] = 2.0 * co[f][0], co[f][2] = co[f][0];
-        co[f][3] = 2.0 * (k * k - 1.0) / den, co[f][4] = (k * k - k / fl[f]->quality + 1.0) / den;
+        if (fl[f]->cascade) biquad_coefficients(*fl[f], co[f]);
       }
       a.pcas[t] = (int)std::min<uint32_t>(pids[t]->p_filter.cascade, (uint32_t)kHoldMaxCas);
       a.dcas[t] = (int)std::min<uint32_t>(pids[t]->d_filter.cascade, (uint32_t)kHoldMaxCas);
@@ -84,7 +110,7 @@ static void f64_mode_args(const cdpr_engine* h, bool vel, bool frc, F64Args& a) 
       double w[CDPR_MAX_D_BUFFER];
       const uint32_t nb = pids[t]->d_buffer_length;
       if (derivative_weights(nb, pids[t]->d_degree, w) == CDPR_OK)
-        for (uint32_t age = 0; age < nb && age < (uint32_t)h->hold_win; ++age) a.hold_w[t][age] = w[nb - 1 - age];
+        for (uint32_t age = 0; age < nb && age < (uint32_t)hold_win(h); ++age) a.hold_w[t][age] = w[nb - 1 - age];
     }
   }
 }
@@ -92,14 +118,14 @@ static void f64_mode_args(const cdpr_engine* h, bool vel, bool frc, F64Args& a) 
 // the fp64 kernel a planned id stands for on this handle
 static F64Kernel f64_kernel_for(const cdpr_engine* h, const PlannedKernel& q) {
   const uint32_t n = h->n;
-  const bool pr = h->per_robot, hold_full = h->plan.hold_full;
+  const bool pr = h->plan.per_robot, hold_full = h->plan.hold_full;
   switch (q.id) {
     case KernelId::F64Split: return pick_f64_split_kernel(n, q.f64_lean);
     case KernelId::F64SplitHold: return pick_f64_split_hold_kernel(n, q.f64_lean, hold_full);
     case KernelId::F64Hold: return h->plan.hold_long ? pick_f64_hold_long_kernel(n, false, false) : pick_f64_hold_kernel(n, hold_full);
     case KernelId::F64HoldPr: return h->plan.hold_long ? pick_f64_hold_long_kernel(n, true, false) : pick_f64_hold_pr_kernel(n, hold_full);
-    case KernelId::F64Tstop: return h->plan.hold_long ? pick_f64_hold_long_kernel(n, pr, true) : pick_f64_tstop_kernel(n, pr, h->hold64 ? (hold_full ? 2 : 1) : 0);
-    case KernelId::F64Long: return pick_f64_long_kernel(n, pr, h->tstop64);
+    case KernelId::F64Tstop: return h->plan.hold_long ? pick_f64_hold_long_kernel(n, pr, true) : pick_f64_tstop_kernel(n, pr, h->plan.hold64 ? (hold_full ? 2 : 1) : 0);
+    case KernelId::F64Long: return pick_f64_long_kernel(n, pr, h->plan.tstop64);
     case KernelId::F64Pr: return pick_f64_pr_kernel(n, q.f64_ring_lds);
     default: return pick_f64_kernel(n, q.f64_ring_lds, q.f64_jcache);
   }
@@ -108,13 +134,13 @@ static F64Kernel f64_kernel_for(const cdpr_engine* h, const PlannedKernel& q) {
 // precision = 64: the same host logic (commands are latched by run_steps before this is reached), the fp64 kernel
 int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, double* record) {
   const uint32_t n = h->n;
-  if (reset_pid && !h->hold64) {  // Pid::reset (Pid.cpp:100-115): zero every controller row (hold branch live: the latch reset that Pid's own rows)
+  if (reset_pid && !h->plan.hold64) {  // Pid::reset (Pid.cpp:100-115): zero every controller row (hold branch live: the latch reset that Pid's own rows)
     h->pid_calls = 0;
-    HIP_TRY(h, hipMemsetAsync(h->d_state64 + (size_t)20 * h->stride, 0, (size_t)(h->win64 + 1) * n * h->stride * sizeof(double), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_state64 + (size_t)kF64StateCtrl * h->stride, 0, (size_t)(win64(h) + 1) * n * h->stride * sizeof(double), h->stream));
   }
   F64Args a = h->base64;
   a.stamps = h->base.stamps;
-  const bool pr = h->per_robot;
+  const bool pr = h->plan.per_robot;
   const bool vel = pr || h->mode == kModeVelocity, frc = !pr && h->mode == kModeForce;
   f64_mode_args(h, vel, frc, a);
   const size_t image64 = (size_t)f64_obs_rows((int)n) * h->stride;  // doubles per observable image
@@ -123,7 +149,7 @@ int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, do
   const int ring_env = [] { const char* v = std::getenv("CDPR_F64_RING_LDS"); return v ? atoi(v) : -1; }();  // (read per call: A/B in one process)
   // ... and the structure-matrix rows too (112 KiB: one wave per CU) up to one workgroup per CU
   const int jc_env = [] { const char* v = std::getenv("CDPR_F64_JCACHE"); return v ? atoi(v) : -1; }();  // (read per call: A/B in one process)
-  a.travel_stop = h->tstop64 ? (int)h->cfg.travel_stop : 0;
+  a.travel_stop = h->plan.tstop64 ? (int)h->cfg.travel_stop : 0;
   // one step per launch on FK + TD handles up to one workgroup per CU: estimator wave + controller wave (cdpr_split_kernel_f64)
   const int sp_env = [] { const char* v = std::getenv("CDPR_F64_SPLIT"); return v ? atoi(v) : -1; }();  // (read per call: A/B in one process)
   // (CDPR_F64_SPLIT = 0 never, 1 the LDS-cached build, 2 the lean build whatever the batch)
@@ -150,7 +176,7 @@ int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, do
     if (first_world) a.flags |= kFlagFirstWorldStep;
     if (record) a.obs = record + (size_t)done * image64;
     a.pid_calls = sat_pid_calls(h->pid_calls);
-    a.ring_slot = ring_slot_of(h->step, h->win64);
+    a.ring_slot = ring_slot_of(h->step, win64(h));
     a.step0 = (int)h->step;
     a.publish_mask = publish_mask(h, k);
     if (k == 1 && split_kern) {
@@ -175,14 +201,7 @@ int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, do
 int fetch_rows64(cdpr_engine* h, const double* rows, uint32_t first_row, uint32_t width, void* host_out, bool as_float) {
   if (!host_out) return CDPR_OK;
   const size_t count = (size_t)h->batch * width, bytes = count * (as_float ? sizeof(float) : sizeof(double));
-  if (h->unpack64_cap < bytes) {
-    HIP_TRY(h, wait_stream(h));
-    if (h->d_unpack64) (void)hipFree(h->d_unpack64);
-    h->d_unpack64 = nullptr;
-    h->unpack64_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->d_unpack64, bytes));
-    h->unpack64_cap = bytes;
-  }
+  HIP_TRY(h, h->d_unpack64.ensure(h, bytes));
   Unpack64Args u{};
   u.rows = rows;
   u.out = h->d_unpack64;
@@ -205,7 +224,7 @@ int fetch_rows64(cdpr_engine* h, const double* rows, uint32_t first_row, uint32_
 int fetch_observables64(cdpr_engine* h, void* position, void* velocity, void* effort, void* pose7, void* twist6, bool as_float) {
   const uint32_t n = h->n;
   void* dst[5] = {position, velocity, effort, pose7, twist6};
-  const uint32_t first[5] = {16u, 16u + n, 16u + 2u * n, 0u, 7u}, width[5] = {n, n, n, 7u, 6u};
+  const uint32_t first[5] = {kF64ObsJoint, kF64ObsJoint + n, kF64ObsJoint + 2u * n, kF64Pose, kF64Twist}, width[5] = {n, n, n, 7u, 6u};
   Unpack64MultiArgs u{};
   u.rows = h->d_obs64;
   u.stride = h->stride;
@@ -232,40 +251,33 @@ int fetch_observables64(cdpr_engine* h, void* position, void* velocity, void* ef
   }
   const bool pinned = bytes <= (2u << 20);
   if (pinned) {
-    if (!h->h_pub64) HIP_TRY(h, hipHostMalloc(&h->h_pub64, 2u << 20, hipHostMallocMapped | hipHostMallocCoherent));
+    if (!h->h_pub64) HIP_TRY(h, h->h_pub64.alloc(2u << 20, hipHostMallocMapped | hipHostMallocCoherent));
     HIP_TRY(h, hipHostGetDevicePointer(&u.out, h->h_pub64, 0));
   } else {
-    if (h->unpack64_cap < bytes) {
-      HIP_TRY(h, wait_stream(h));
-      if (h->d_unpack64) (void)hipFree(h->d_unpack64);
-      h->d_unpack64 = nullptr;
-      h->unpack64_cap = 0;
-      HIP_TRY(h, hipMalloc(&h->d_unpack64, bytes));
-      h->unpack64_cap = bytes;
-    }
+    HIP_TRY(h, h->d_unpack64.ensure(h, bytes));
     u.out = h->d_unpack64;
   }
   hipLaunchKernelGGL(cdpr_unpack64_multi_kernel, dim3((uint32_t)(((size_t)h->batch * cum + 255) / 256)), dim3(256), 0, h->stream, u);
   HIP_TRY(h, hipGetLastError());
   if (!pinned)
     for (uint32_t k = 0; k < u.nseg; ++k)
-      HIP_TRY(h, hipMemcpyAsync(want[k], static_cast<const char*>(h->d_unpack64) + (size_t)u.off[k] * esz, (size_t)h->batch * u.width[k] * esz, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(want[k], h->d_unpack64 + (size_t)u.off[k] * esz, (size_t)h->batch * u.width[k] * esz, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, wait_stream(h));
   if (pinned)
-    for (uint32_t k = 0; k < u.nseg; ++k) memcpy(want[k], static_cast<const char*>(h->h_pub64) + (size_t)u.off[k] * esz, (size_t)h->batch * u.width[k] * esz);
+    for (uint32_t k = 0; k < u.nseg; ++k) memcpy(want[k], h->h_pub64 + (size_t)u.off[k] * esz, (size_t)h->batch * u.width[k] * esz);
   return CDPR_OK;
 }
 
 int set_platform_state64(cdpr_engine* h, const double* pose7, const double* twist6) {
   const size_t st = h->stride;
-  std::vector<double> s((size_t)20 * st);
+  std::vector<double> s((size_t)kF64StateCtrl * st);
   HIP_TRY(h, hipMemcpyAsync(s.data(), h->d_state64, s.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, wait_stream(h));
   for (uint32_t r = 0; r < h->batch; ++r) {
     if (pose7)
-      for (int c = 0; c < 7; ++c) s[(size_t)c * st + r] = s[(size_t)(13 + c) * st + r] = pose7[(size_t)r * 7 + c];  // the FK seed follows the spawn pose
+      for (int c = 0; c < 7; ++c) s[(size_t)(kF64Pose + c) * st + r] = s[(size_t)(kF64StateFk + c) * st + r] = pose7[(size_t)r * 7 + c];  // the FK seed follows the spawn pose
     if (twist6)
-      for (int c = 0; c < 6; ++c) s[(size_t)(7 + c) * st + r] = twist6[(size_t)r * 6 + c];
+      for (int c = 0; c < 6; ++c) s[(size_t)(kF64Twist + c) * st + r] = twist6[(size_t)r * 6 + c];
   }
   HIP_TRY(h, hipMemcpyAsync(h->d_state64, s.data(), s.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, wait_stream(h));
@@ -281,13 +293,13 @@ void decode_image64(const cdpr_engine* h, const double* o, T* position, T* veloc
   for (int f = 0; f < 3; ++f) {
     if (!dst[f]) continue;
     for (uint32_t r = 0; r < h->batch; ++r)
-      for (uint32_t i = 0; i < n; ++i) dst[f][(size_t)r * n + i] = (T)o[(size_t)(16 + f * n + i) * st + r];
+      for (uint32_t i = 0; i < n; ++i) dst[f][(size_t)r * n + i] = (T)o[(size_t)(kF64ObsJoint + f * n + i) * st + r];
   }
   for (uint32_t r = 0; r < h->batch; ++r) {
     if (pose7)
-      for (int c = 0; c < 7; ++c) pose7[(size_t)r * 7 + c] = (T)o[(size_t)c * st + r];
+      for (int c = 0; c < 7; ++c) pose7[(size_t)r * 7 + c] = (T)o[(size_t)(kF64Pose + c) * st + r];
     if (twist6)
-      for (int c = 0; c < 6; ++c) twist6[(size_t)r * 6 + c] = (T)o[(size_t)(7 + c) * st + r];
+      for (int c = 0; c < 6; ++c) twist6[(size_t)r * 6 + c] = (T)o[(size_t)(kF64Twist + c) * st + r];
   }
 }
 void decode_image64_to_float(const cdpr_engine* h, const double* image, float* position, float* velocity, float* effort, float* pose7, float* twist6) {
@@ -298,7 +310,7 @@ void decode_image64_to_float(const cdpr_engine* h, const double* image, float* p
 
 int cdpr_decode_observables_f64(cdpr_handle_t h, const void* image, double* position, double* velocity, double* effort, double* pose7, double* twist6) {
   if (!h || !image) return CDPR_ERR_INVALID;
-  if (!h->fp64) {
+  if (!h->plan.fp64) {
     h->err = "cdpr_decode_observables_f64: the handle was not created with precision = 64";
     return CDPR_ERR_UNSUPPORTED;
   }
@@ -308,7 +320,7 @@ int cdpr_decode_observables_f64(cdpr_handle_t h, const void* image, double* posi
 namespace cdpr_host {
 
 static int need_fp64(cdpr_engine* h, const char* what) {
-  if (h->fp64) return CDPR_OK;
+  if (h->plan.fp64) return CDPR_OK;
   h->err = std::string(what) + ": the handle was not created with precision = 64";
   return CDPR_ERR_UNSUPPORTED;
 }
@@ -325,8 +337,8 @@ int cdpr_get_raw_state_f64(cdpr_handle_t h, double* pose7, double* twist6) {
   if (!h) return CDPR_ERR_INVALID;
   if (int rc = need_fp64(h, "cdpr_get_raw_state_f64")) return rc;
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  int rc = fetch_rows64(h, h->d_state64, 0, 7, pose7, false);
-  return rc != CDPR_OK ? rc : checked(h, fetch_rows64(h, h->d_state64, 7, 6, twist6, false));
+  int rc = fetch_rows64(h, h->d_state64, kF64Pose, 7, pose7, false);
+  return rc != CDPR_OK ? rc : checked(h, fetch_rows64(h, h->d_state64, kF64Twist, 6, twist6, false));
 }
 
 int cdpr_set_platform_state_f64(cdpr_handle_t h, const double* pose7, const double* twist6) {
@@ -356,27 +368,21 @@ int rollout_enqueue_f64(cdpr_engine* h, int samples, int horizon, const float* d
   const uint64_t traj = (uint64_t)h->batch * (uint64_t)samples;
   const size_t cols = (size_t)((traj + 63u) & ~(uint64_t)63u);
   const uint32_t rows = (uint32_t)state64_rows(h);  // (hold branch live: both Pids' records of every cable travel with a trajectory)
-  if (h->roll64_cols < cols) {
-    HIP_TRY(h, wait_stream(h));
-    for (void** p64 : {(void**)&h->d_roll64, (void**)&h->d_roll64_acc, (void**)&h->d_roll64_cmd, (void**)&h->d_roll64_meta}) {
-      if (*p64) (void)hipFree(*p64);
-      *p64 = nullptr;
-    }
-    h->roll64_cols = 0;
-    HIP_TRY(h, hipMalloc(&h->d_roll64, (size_t)rows * cols * sizeof(double)));
-    HIP_TRY(h, hipMalloc(&h->d_roll64_acc, cols * sizeof(double)));
-    HIP_TRY(h, hipMalloc(&h->d_roll64_cmd, cols * n * sizeof(float)));
-    if (h->per_robot) HIP_TRY(h, hipMalloc(&h->d_roll64_meta, cols));
-    h->roll64_cols = cols;
-  }
-  const bool pr = h->per_robot;
+  // (the four grow together; roll64_cols, the trajectories' row stride, never shrinks, so a buffer that failed to grow comes back at that size)
+  const size_t cap = std::max(cols, h->roll64_cols);
+  HIP_TRY(h, h->d_roll64.ensure(h, (size_t)rows * cap * sizeof(double)));
+  HIP_TRY(h, h->d_roll64_acc.ensure(h, cap * sizeof(double)));
+  HIP_TRY(h, h->d_roll64_cmd.ensure(h, cap * n * sizeof(float)));
+  if (h->plan.per_robot) HIP_TRY(h, h->d_roll64_meta.ensure(h, cap));
+  h->roll64_cols = cap;
+  const bool pr = h->plan.per_robot;
   const bool reset = pr || h->mode != kModeVelocity;  // JFC.cpp:113-115: the copies start from a reset velocity Pid, the handle's rows stay (per-robot handles: per robot, from its meta byte)
   const uint32_t blocks = (uint32_t)((traj + 255u) / 256u);
   Roll64Args e{};
   e.src = h->d_state64, e.dst = h->d_roll64, e.src_stride = h->stride, e.dst_stride = (uint32_t)h->roll64_cols, e.rows = rows, e.batch = h->batch,
-  e.samples = (uint32_t)samples, e.zero_from = (reset && !h->hold64) ? 20u : rows;
-  if (h->hold64 && reset) {  // ... there the velocity Pid's own record of every cable is what the Joy resets
-    e.hold_base = (uint32_t)f64_state_rows((int)n), e.hold_cable_rows = (uint32_t)hold_cable_rows(h->hold_win), e.hold_pid_rows = (uint32_t)hold_pid_rows(h->hold_win);
+  e.samples = (uint32_t)samples, e.zero_from = (reset && !h->plan.hold64) ? (uint32_t)kF64StateCtrl : rows;
+  if (h->plan.hold64 && reset) {  // ... there the velocity Pid's own record of every cable is what the Joy resets
+    e.hold_base = (uint32_t)f64_state_rows((int)n), e.hold_cable_rows = (uint32_t)hold_cable_rows(hold_win(h)), e.hold_pid_rows = (uint32_t)hold_pid_rows(hold_win(h));
     e.hold_zero_pid = 2u;  // 1 + the Pid's index
   }
   if (pr) e.meta_src = h->d_mode, e.meta_dst = h->d_roll64_meta;
@@ -401,7 +407,7 @@ int rollout_enqueue_f64(cdpr_engine* h, int samples, int horizon, const float* d
   const PlannedKernel pk = planned_kernel(h->plan, shape);
   F64Kernel kern = f64_kernel_for(h, pk);
   h->last_kernel = pk;
-  a.travel_stop = h->tstop64 ? (int)h->cfg.travel_stop : 0;
+  a.travel_stop = h->plan.tstop64 ? (int)h->cfg.travel_stop : 0;
   int calls = reset ? 0 : h->pid_calls;  // (uniform handles; per-robot handles count in the meta bytes)
   for (int k = 0; k < horizon; ++k) {
     Roll64CmdArgs c{};
@@ -410,7 +416,7 @@ int rollout_enqueue_f64(cdpr_engine* h, int samples, int horizon, const float* d
     const bool first_world = (h->step + (uint64_t)k) == 0;
     a.flags = (pr ? 0u : kFlagActualIsVelocity) | (first_world ? kFlagFirstWorldStep : 0u);
     a.pid_calls = sat_pid_calls(calls);
-    a.ring_slot = ring_slot_of(h->step + (uint64_t)k, h->win64);
+    a.ring_slot = ring_slot_of(h->step + (uint64_t)k, win64(h));
     a.step0 = (int)(h->step + (uint64_t)k);
     hipLaunchKernelGGL(kern, dim3((uint32_t)((traj + 63u) / 64u)), dim3(64), 0, h->stream, a);
     calls = sat_pid_calls(calls + (first_world ? 0 : 1));

@@ -1,7 +1,9 @@
-// cdpr_engine_internal.hpp - what the translation units of the host side share: the handle (struct cdpr_engine), the error macro
-// and the helpers one unit defines and another calls.  Units: cdpr_engine.hip (create / destroy, commands, the fp32 launch chains,
-// read-out), cdpr_engine_f64.hip (precision = 64), cdpr_engine_rollout.hip (cdpr_rollout_velocity*), cdpr_engine_solvers.hip
-// (cdpr_solve_ik / fk / td).  Not installed, not part of the C-ABI (include/cdpr.h is).
+// cdpr_engine_internal.hpp - what the translation units of the host side share: the owners of device and pinned memory (DevBuf,
+// PinnedBuf), the handle (struct cdpr_engine: its routing is h->plan and nothing else, its buffers are owner members that go with
+// it), the error macros and the helpers one unit defines and another calls.  Units: cdpr_engine.hip (create / destroy, the general
+// path's set-up, commands, the fp32 launch chains, read-out), cdpr_engine_f64.hip (precision = 64: set-up, launch chain, read-out),
+// cdpr_engine_rollout.hip (cdpr_rollout_velocity*), cdpr_engine_solvers.hip (cdpr_solve_ik / fk / td).  Not installed, not part
+// of the C-ABI (include/cdpr.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,20 +39,80 @@ enum Mode { kModeForce = 0, kModePosition = 1, kModeVelocity = 2 };  // JFC.h:35
     }                                                                                            \
   } while (0)
 
+// a failed step of cdpr_create: the message into the handle, the code the ABI returns (cdpr_create hands both on and frees the handle)
+#define CREATE_TRY(h, what, expr)                                                                \
+  do {                                                                                           \
+    hipError_t e_ = (expr);                                                                      \
+    if (e_ != hipSuccess) {                                                                      \
+      (h)->err = std::string(what) + ": " + hipGetErrorString(e_);                               \
+      return e_ == hipErrorOutOfMemory ? CDPR_ERR_NOMEM : CDPR_ERR_DEVICE;                       \
+    }                                                                                            \
+  } while (0)
+
+}  // namespace cdpr_host
+struct cdpr_engine;
+namespace cdpr_host {
+
+hipError_t wait_stream(cdpr_engine* h);  // poll, then block (cdpr_engine.hip)
+
+// The owner of one device allocation (cap bytes): freed with its owner - the handle, or a function's scratch.  Reads as the T* it holds.
+template <typename T = void>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr, cap = 0;
+  }
+  hipError_t alloc(size_t bytes) {
+    release();
+    const hipError_t e = hipMalloc((void**)&p, bytes ? bytes : 4);
+    if (e == hipSuccess) cap = bytes;
+    else p = nullptr;
+    return e;
+  }
+  // grow-only scratch: a buffer too short is replaced once the handle's stream, which may still use it, has drained; a failed
+  // allocation leaves p null and cap 0
+  hipError_t ensure(cdpr_engine* h, size_t bytes) {
+    if (cap >= bytes) return hipSuccess;
+    const hipError_t e = wait_stream(h);
+    return e != hipSuccess ? e : alloc(bytes);
+  }
+  void swap(DevBuf& o) { std::swap(p, o.p), std::swap(cap, o.cap); }
+  operator T*() const { return p; }
+  template <typename U> U* as() const { return static_cast<U*>(p); }
+};
+
+// ... and of one pinned host allocation (hipHostMalloc)
+template <typename T>
+struct PinnedBuf {
+  T* p = nullptr;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+  hipError_t alloc(size_t bytes, unsigned flags) { return hipHostMalloc((void**)&p, bytes, flags); }
+  operator T*() const { return p; }
+};
+
 // Everything one command kind owns.  The handle keeps one record per kind, cdpr_engine::cmd[], indexed by the ABI's
 // CDPR_COMMAND_VELOCITY / _POSITION / _FORCE (0, 1, 2); what differs between the kinds is kCmdKind below.
 struct CmdChannel {
-  float* d[2] = {nullptr, nullptr};          // the engine's own device buffers: [0] latched, [1] pending
+  DevBuf<float> d[2];                        // the engine's own device buffers: [0] latched, [1] pending
   // zero-copy commands (cdpr_bind_*_command_device): a caller-owned device buffer takes the place of d[0] / d[1]
   const float* ext[2] = {nullptr, nullptr};
-  uint8_t* d_mask = nullptr;                 // per-robot handles: the pending command's mask, uint8[B]
+  DevBuf<uint8_t> d_mask;                    // per-robot handles: the pending command's mask, uint8[B]
   bool pending = false;
   bool masked = false;                       // the pending command came with a mask
   bool have = false;                         // a command of this kind has been latched since Load
   // Host-side Joy batches travel on their own stream (cdpr_set_*_command with a host pointer): the caller's rows go into
   // one of two pinned staging buffers and from there to the PENDING device buffer while earlier launches still
   // run; the call returns without waiting.
-  float* h_stage[2] = {nullptr, nullptr};
+  PinnedBuf<float> h_stage[2];
   hipEvent_t stage_ev[2] = {nullptr, nullptr};  // the copy out of that staging buffer has completed
   bool stage_ev_set[2] = {false, false};
   int stage_idx = 0;
@@ -62,7 +124,7 @@ struct CmdChannel {
   const float* sched_rows = nullptr;
   const uint8_t* sched_mask = nullptr;
 
-  const float* latched() const { return ext[0] ? ext[0] : d[0]; }  // what the launches read: the bound buffer where one is latched
+  const float* latched() const { return ext[0] ? ext[0] : d[0].p; }  // what the launches read: the bound buffer where one is latched
 };
 
 constexpr int kCmdKinds = 3;
@@ -84,48 +146,34 @@ using namespace cdpr_host;
 
 struct cdpr_engine {
   cdpr_config_t cfg{};
+  KernelPlan plan;          // the routing cdpr_create took for this configuration (cdpr_select.hpp): the only copy, every reader takes h->plan.X
   int device = 0;
   hipStream_t stream = nullptr;
   uint32_t n = 0, batch = 0, stride = 0;
-  bool fk = false, td = false, dbg = false;
+  bool dbg = false;
   int n_state = 0, n_obs = 0;
-  float4* d_state = nullptr;
-  float4* d_obs = nullptr;
-  float* d_dbg = nullptr;
-  float* d_geom = nullptr;  // pair-interleaved cable geometry, staged in LDS by the kernel
+  DevBuf<float4> d_state, d_obs;
+  DevBuf<float> d_dbg;
+  DevBuf<float> d_geom;     // pair-interleaved cable geometry, staged in LDS by the kernel
   int pid_calls = 0;        // Pid::update calls since the last Pid reset (uniform over the batch)
-  bool lane_pair = false;   // two lanes per robot (cdpr_step_kernel_pair.hpp) instead of one
-  bool lane_cable = false;  // one lane per cable, 8 (or 4) lanes per robot (cdpr_step_kernel_cable.hpp)
-  bool phys = false;        // lumped-leg physics terms enabled: the PHYS instantiations of the first-generation kernels
-  bool lowreg = false;      // one-step launches use the <= 256-register build (two waves per SIMD; large batches)
-  bool gen_split = false;   // general path: one-step launches use the role-split kernel (FK + TD, n >= 6, windows <= 11, <= 2 workgroups per CU)
-  bool gen_hot = false;     // general path: robots in the deep steady state keep mLastTime / mIerr in hot rows instead of their H slots (GenHot; CDPR_GEN_HOT=0: off)
-  bool gen_lean = false;    // general path, larger batches: one-step launches use the lean role-split kernel (two waves per SIMD, the rare
-                            // controller paths by call: cdpr_general_split.hpp)
-  bool persist = false;     // one-step launches use the persistent one-wave kernel: one wave per SIMD walks over blocks of 64
-                            // robots, the next block's rows in flight under the current block's arithmetic (large batches)
-  uint32_t persist_grid = 0;  // waves of such a launch: SIMDs of the device
-  bool split = false;       // FK + TD one-step launches use cdpr_split_kernel (estimator wave + controller wave per 64 robots)
+  uint32_t persist_grid = 0;  // waves of a launch of the persistent one-wave kernel (plan.persist): SIMDs of the device
   int sched_refresh = 0;            // cdpr_update_scheduled in progress: Joy batches per launch (StepArgs::sched_*)
   const uint32_t* sched_ready = nullptr;
-  uint32_t* h_fault = nullptr;      // pinned, device-mapped status word: a schedule mailbox that never delivered (kernels OR bits into it)
+  PinnedBuf<uint32_t> h_fault;      // pinned, device-mapped status word: a schedule mailbox that never delivered (kernels OR bits into it)
   uint32_t* d_fault = nullptr;      // its device address
-  uint32_t chunk = 0;       // > 0: a step over the batch is issued as back-to-back launches over contiguous blocks of at most
-                            // this many robots (batches between one and ~5 robots per hardware lane: see cdpr_create)
-  bool onestep_v2 = true;   // one-step launches use cdpr_onestep_kernel (controller rows through LDS); CDPR_ONESTEP=1: first generation
   // general controller path (hold branch, cascades, long windows): see cdpr_general_step.hpp
-  bool general = false;
-  float* d_rec = nullptr;    // record rows: [mLastPosition per cable][position Pid rows][velocity Pid rows], one column per robot
-  float* d_gwtab = nullptr;  // FIR weights by ring head, [pid][head][slot]
-  float* d_gptab = nullptr;  // the two Pids' parameters as the kernel stages them in LDS (gen_pid_table)
+  DevBuf<float> d_rec;       // record rows: [mLastPosition per cable][position Pid rows][velocity Pid rows], one column per robot
+  DevBuf<float> d_gwtab;     // FIR weights by ring head, [pid][head][slot]
+  DevBuf<float> d_gptab;     // the two Pids' parameters as the kernel stages them in LDS (gen_pid_table)
   GenPid gpid[2]{};
   GenLayout glay{};          // rows of a Pid block: sized by the configured window length and cascade count
-  double* d_roll64 = nullptr;    // MPC rollout on a precision = 64 handle: the trajectories' state rows, their cost accumulators, the step's Joy batch
-  double* d_roll64_acc = nullptr;
-  float* d_roll64_cmd = nullptr;
-  uint8_t* d_roll64_meta = nullptr;  // ... per-robot handles: every trajectory's mode / Pid call count byte
+  // MPC rollout on a precision = 64 handle: the trajectories' state rows, their cost accumulators, the step's Joy batch,
+  // per-robot handles: every trajectory's mode / Pid call count byte.  Grow-only, sized together for roll64_cols columns (their row stride)
+  DevBuf<double> d_roll64, d_roll64_acc;
+  DevBuf<float> d_roll64_cmd;
+  DevBuf<uint8_t> d_roll64_meta;
   size_t roll64_cols = 0;
-  float* d_roll_rec = nullptr;   // MPC rollout on the general path: every trajectory's private copy of the records
+  DevBuf<float> d_roll_rec;      // MPC rollout on the general path: every trajectory's private copy of the records
   size_t roll_rec_cols = 0;      // columns d_roll_rec can hold
   // hipGraph cache: chains of identical steady-state launches (see run_steps)
   struct GraphEntry {
@@ -138,65 +186,123 @@ struct cdpr_engine {
   };
   std::vector<GraphEntry> graphs;
   PlannedKernel last_kernel;  // what the last step launch ran on (cdpr_kernel_name)
-  int hold_win = kHoldWin;  // precision = 64, HOLD handles: samples a Pid record's window holds (kHoldWinLong with derivative windows of 12 .. 32 samples)
-  int win64 = kWin;         // precision = 64: prior errors kept per cable (kWinLong on handles with windows of 12 .. 32 samples)
-  KernelPlan plan;          // the routing cdpr_create took for this configuration (cdpr_select.hpp)
   int cus = 256;
   bool use_graphs = true;
-  bool pair_stream = true;  // cdpr_pair_stream_kernel serves the steady several-steps launches of lane-pair handles (CDPR_PAIR_STREAM=0: never; A/B and tests)
   CmdChannel cmd[kCmdKinds];  // command state, one record per kind
-  // per-robot command arrival (cfg.per_robot_commands): every robot has its own mode; general controller path only
-  bool per_robot = false;
-  uint8_t* d_mode = nullptr;        // uint8[B]: 1 = Position, 2 = Velocity; on the register-resident path also the robot's
+  // per-robot command arrival (plan.per_robot): every robot has its own mode
+  DevBuf<uint8_t> d_mode;           // uint8[B]: 1 = Position, 2 = Velocity; on the register-resident path also the robot's
                                     // Pid call count in bits 2-7 (StepArgs::meta)
-  float* d_target = nullptr;        // per-robot handles on the register-resident path: float[B][n], every robot's ACTIVE target row
+  DevBuf<float> d_target;           // per-robot handles on the register-resident path: float[B][n], every robot's ACTIVE target row
   hipStream_t copy_stream = nullptr;  // host-side Joy batches travel on their own stream (CmdChannel::h_stage)
   int mode = kModePosition;
   uint64_t step = 0;
   double prev_publish = 0.0;
   StepArgs base{};               // world/body/FK/TD constants, pointers; Pid fields filled per launch
   StepArgs pid_vel{}, pid_pos{};  // only the Pid fields of these are used
-  float* d_wtab = nullptr;        // [velocity | position] rotated derivative-weight tables, kWin * (kWin + 2) floats each
+  DevBuf<float> d_wtab;           // [velocity | position] rotated derivative-weight tables, kWin * (kWin + 2) floats each
   float wtab_host[2][kWin * (kWin + 2)]{};  // the same tables on the host: one-step launches take their row by value
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   uint64_t launches = 0, launches_mark = 0;
   // cdpr_get_observables: pinned, device-mapped host image of one published step + completion word
-  float* h_pub = nullptr;        // host pointer (hipHostMalloc)
-  uint64_t* h_pub_done = nullptr;
-  uint32_t* d_pub_arrivals = nullptr;
+  PinnedBuf<float> h_pub;
+  PinnedBuf<uint64_t> h_pub_done;
+  DevBuf<uint32_t> d_pub_arrivals;
   uint64_t pub_epoch = 0;
-  // MPC rollout scratch, persistent and grow-only (no hipMalloc / hipFree inside a rollout)
-  float* d_roll_ref = nullptr;   // float[B][3]
-  float* d_roll_cost = nullptr;  // float[B][samples]
-  size_t roll_cost_cap = 0;      // trajectories d_roll_cost can hold
+  // MPC rollout scratch, persistent and grow-only (no hipMalloc / hipFree inside a rollout that fits)
+  DevBuf<float> d_roll_ref;      // float[B][3]
+  DevBuf<float> d_roll_cost;     // float[B][samples]
   uint64_t roll_pending = 0;     // trajectories of the launched, not yet fetched rollout
-  // cdpr_config_t.precision = 64: the step in double (cdpr_step_kernel_f64.hpp); its own state, observables, tables
-  bool fp64 = false;
-  bool tstop64 = false;  // ... with the joint stop modelled (travel_stop > 0; TSTOP kernels)
-  bool hold64 = false;   // ... with the position-hold branch live (velocity_epsilon >= 0): both Pids of every cable in rows behind the state (HOLD kernels)
-  double* d_state64 = nullptr;
-  double* d_obs64 = nullptr;
-  double* d_geom64 = nullptr;    // [n][7]
-  double* d_wtab64 = nullptr;    // [velocity | position] x [10][12]
-  double* d_dbg64 = nullptr;
-  void* d_unpack64 = nullptr;    // read-out scratch of the fp64 getters (bytes)
-  void* h_pub64 = nullptr;       // mapped pinned image the fp64 getters of small batches are gathered into (2 MiB)
-  size_t unpack64_cap = 0;
+  // cdpr_config_t.precision = 64 (plan.fp64): the step in double (cdpr_step_kernel_f64.hpp); its own state, observables, tables
+  DevBuf<double> d_state64, d_obs64;
+  DevBuf<double> d_geom64;       // [n][7]
+  DevBuf<double> d_wtab64;       // [velocity | position] x [10][12]
+  DevBuf<double> d_dbg64;
+  DevBuf<char> d_unpack64;       // read-out scratch of the fp64 getters, grow-only
+  PinnedBuf<char> h_pub64;       // mapped pinned image the fp64 getters of small batches are gathered into (2 MiB)
   F64Args base64{};
-  float* d_unpack = nullptr;     // read-out scratch (cdpr_get_*): robot-major copy of the requested fields, grow-only
-  size_t unpack_cap = 0;
+  DevBuf<float> d_unpack;        // read-out scratch (cdpr_get_*): robot-major copy of the requested fields, grow-only
   std::string err;
 };
 
 namespace cdpr_host {
 
-// Scratch device buffer holding caller data for the one-shot solvers.
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 4); }
-  template <typename T> T* as() { return static_cast<T*>(p); }
-};
+// precision = 64: prior errors kept per cable (the ring of the handle's kernels), and the samples a HOLD record's window holds
+inline int win64(const cdpr_engine* h) { return h->plan.long64 ? kWinLong : kWin; }
+inline int hold_win(const cdpr_engine* h) { return h->plan.hold_long ? kHoldWinLong : kHoldWin; }
+
+// fp32 observable image: (slot, component) of joint field f (0 position, 1 velocity, 2 effort) of cable i
+inline std::pair<int, int> obs_joint_field(int n, int f, uint32_t i) { return {4 + f * joint_groups(n) + (int)(i / 4), (int)(i % 4)}; }
+
+int derivative_weights(uint32_t n, uint32_t degree, double* w);  // cdpr_engine.hip
+
+// A Pid's end-point LS derivative weights rotated per ring position, as T, for a ring of W errors: row ws (W + 2 entries) serves the
+// launch whose new error goes to slot ws.  Slot (ws - j) mod W then holds the error of j steps ago (j = 1 .. W; j = W is slot ws
+// itself, the sample about to be overwritten), whose weight is wpad[W - j]; entry W is the weight of the new error itself.
+template <typename T>
+void rotated_weights(const cdpr_pid_params_t& p, int W, T* tab) {
+  double w[CDPR_MAX_D_BUFFER];
+  std::vector<T> wpad((size_t)W + 1, (T)0);  // oldest..newest, zero padded at the old end to W + 1 entries
+  if (derivative_weights(p.d_buffer_length, p.d_degree, w) == CDPR_OK && p.d_buffer_length <= (uint32_t)W + 1)
+    for (uint32_t j = 0; j < p.d_buffer_length; ++j) wpad[(size_t)W + 1 - p.d_buffer_length + j] = (T)w[j];
+  for (int ws = 0; ws < W; ++ws) {
+    for (int s = 0; s < W; ++s) {
+      int j = ((ws - s) % W + W) % W;
+      if (j == 0) j = W;
+      tab[ws * (W + 2) + s] = wpad[(size_t)W - j];
+    }
+    tab[ws * (W + 2) + W] = wpad[(size_t)W];
+    tab[ws * (W + 2) + W + 1] = (T)0;
+  }
+}
+
+// The world / body / FK / TD constants StepArgs (T = float) and F64Args (T = double) share: every value is computed in double
+// and then cast.
+template <typename T, typename Args>
+void fill_physics(const cdpr_config_t& c, Args& k) {
+  k.dt = (T)c.dt;
+  k.half_dt = (T)(0.5 * c.dt);
+  k.inv_mass = (T)(1.0 / c.mass);
+  k.fgx = (T)(c.mass * c.gravity[0]);
+  k.fgy = (T)(c.mass * c.gravity[1]);
+  k.fgz = (T)(c.mass * c.gravity[2]);
+  double inv[6];
+  mat3_inverse_sym(c.inertia, inv);
+  for (int i = 0; i < 6; ++i) {
+    k.ib[i] = (T)c.inertia[i];
+    k.ibinv[i] = (T)inv[i];
+  }
+  k.damping = (T)c.joint_damping;
+  k.effort = (T)c.effort_limit;
+  k.vel_limit = (T)c.velocity_limit;
+  k.unilateral = c.unilateral_cables ? 1 : 0;
+  k.travel_lo = (T)c.travel_lower;
+  k.travel_hi = (T)c.travel_upper;
+  k.travel_on = (c.travel_lower != 0.0 || c.travel_upper != 0.0) ? 1 : 0;
+  k.ph_lumped = lumped_legs_on(c) ? 1 : 0;
+  k.ph_c = (T)c.passive_damping;
+  k.ph_jleg = (T)c.leg_inertia;
+  k.ph_max = (T)c.cable_axial_mass;
+  k.ph_mpt = (T)c.anchor_point_mass;
+  k.ph_iadd_total = (T)(c.anchor_inertia * (double)c.n_cables);
+  k.ph_mass = (T)c.mass;
+  k.gx = (T)c.gravity[0];
+  k.gy = (T)c.gravity[1];
+  k.gz = (T)c.gravity[2];
+  k.fk_lambda = (T)c.fk_lambda;
+  k.fk_tol = (T)c.fk_tolerance;
+  k.fk_iters = (int)c.fk_max_iterations;
+  k.td_min = (T)c.td_f_min;
+  k.td_max = (T)c.td_f_max;
+  k.td_mid = (T)(0.5 * (c.td_f_min + c.td_f_max));
+}
+
+// a device copy of a host table (cdpr_create)
+template <typename T>
+int upload_table(cdpr_engine* h, DevBuf<T>& d, const void* src, size_t bytes, const char* name) {
+  CREATE_TRY(h, "hipMalloc(" + std::string(name) + ")", d.alloc(bytes));
+  CREATE_TRY(h, "hipMemcpy(" + std::string(name) + ")", hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+  return CDPR_OK;
+}
 
 // the kind whose latched command a uniform handle in `mode` reads
 inline int cmd_kind_of_mode(int mode) { return mode == kModeVelocity ? (int)CDPR_COMMAND_VELOCITY : mode == kModeForce ? (int)CDPR_COMMAND_FORCE : (int)CDPR_COMMAND_POSITION; }
@@ -208,11 +314,10 @@ inline int ring_slot_of(uint64_t step) { return (int)((step + 8u) % (uint64_t)kW
 inline int ring_slot_of(uint64_t step, int w) { return (int)((step + (uint64_t)(w - 2)) % (uint64_t)w); }
 
 // cdpr_engine.hip
-hipError_t wait_stream(cdpr_engine* h);  // poll, then block
 int set_device(cdpr_engine* h);
 int check_fault(cdpr_engine* h);
 int checked(cdpr_engine* h, int rc);
-int derivative_weights(uint32_t n, uint32_t degree, double* w);
+void biquad_coefficients(const cdpr_filter_params_t& f, double co[5]);  // a0 a1 a2 b1 b2
 double sim_time(uint64_t step, double dt);
 uint64_t publish_mask(cdpr_engine* h, int k);  // which of the next k world steps publish; advances prev_publish
 LaunchShape launch_shape(const cdpr_engine* h, int k, bool steady = false);
@@ -225,6 +330,7 @@ void copy_pid_alt(const StepArgs& src, PidSet& dst);
 GenCtl general_ctl(const cdpr_engine* h);
 int fetch_slots(cdpr_engine* h, const float4* dsrc, int nslots, std::vector<float4>& host);
 // cdpr_engine_f64.hip
+int build_f64(cdpr_engine* h);  // cdpr_create's part of a precision = 64 handle
 size_t state64_rows(const cdpr_engine* h);
 int upload_home64(cdpr_engine* h);
 int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, double* record = nullptr);

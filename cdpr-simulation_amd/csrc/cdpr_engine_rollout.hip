@@ -5,8 +5,8 @@
 namespace cdpr_host {
 
 static int rollout_enqueue(cdpr_engine* h, int samples, int horizon, const float* d_commands, const float* d_ref, float* d_cost) {
-  if (h->fp64) return rollout_enqueue_f64(h, samples, horizon, d_commands, d_ref, d_cost);
-  if (h->general) {
+  if (h->plan.fp64) return rollout_enqueue_f64(h, samples, horizon, d_commands, d_ref, d_cost);
+  if (h->plan.general) {
     // every trajectory steps a private copy of its robot's controller records (both Pids of every cable: the hold branch
     // switches between them from step to step): one column per trajectory in a persistent, grow-only scratch
     const uint64_t traj = (uint64_t)h->batch * (uint64_t)samples;
@@ -16,14 +16,8 @@ static int rollout_enqueue(cdpr_engine* h, int samples, int horizon, const float
       h->err = "rollout on the general controller path: the trajectories' controller records pass 4 GiB; use fewer samples per call";
       return CDPR_ERR_UNSUPPORTED;
     }
-    if (h->roll_rec_cols < cols) {
-      HIP_TRY(h, wait_stream(h));
-      if (h->d_roll_rec) (void)hipFree(h->d_roll_rec);
-      h->d_roll_rec = nullptr;
-      h->roll_rec_cols = 0;
-      HIP_TRY(h, hipMalloc(&h->d_roll_rec, bytes));
-      h->roll_rec_cols = cols;
-    }
+    h->roll_rec_cols = std::max(cols, h->roll_rec_cols);  // (the records' column stride: never shrinks)
+    HIP_TRY(h, h->d_roll_rec.ensure(h, h->glay.bytes(h->roll_rec_cols)));
     if (h->step + (uint64_t)horizon >= (1ull << 31)) {
       h->err = "general controller path: world-step counter would pass 2^31";
       return CDPR_ERR_UNSUPPORTED;
@@ -49,7 +43,7 @@ static int rollout_enqueue(cdpr_engine* h, int samples, int horizon, const float
     g.rstride = (uint32_t)h->roll_rec_cols;
     g.rec_bytes = (uint32_t)h->glay.bytes(h->roll_rec_cols);
     g.now_step = (int)h->step;
-    GenKernel kern = pick_gen_kernel(h->n, h->fk, h->td, true, h->glay.nb > 11, false);
+    GenKernel kern = pick_gen_kernel(h->n, h->plan.fk, h->plan.td, true, h->glay.nb > 11, false);
     hipLaunchKernelGGL(kern, dim3((uint32_t)((traj + 63u) / 64u)), dim3(64), 0, h->stream, a, g);
     HIP_TRY(h, hipGetLastError());
     LaunchShape rs = launch_shape(h, horizon);
@@ -73,10 +67,10 @@ static int rollout_enqueue(cdpr_engine* h, int samples, int horizon, const float
   if (h->step == 0) a.flags |= kFlagFirstWorldStep;
   // a Joy on jointVelocities while in Position mode resets the velocity Pid (JFC.cpp:113-115); the handle's own
   // records stay untouched, the rollout starts from zeroed copies (per-robot handles: decided per lane from meta)
-  if (!h->per_robot && h->mode != kModeVelocity) a.flags |= kFlagRolloutResetPid;
+  if (!h->plan.per_robot && h->mode != kModeVelocity) a.flags |= kFlagRolloutResetPid;
   a.pid_calls = (h->mode == kModeVelocity) ? sat_pid_calls(h->pid_calls) : 0;
   a.ring_slot = ring_slot_of(h->step);
-  if (h->per_robot) {
+  if (h->plan.per_robot) {
     copy_pid_alt(h->pid_pos, a.alt);
     a.meta = h->d_mode;
   }
@@ -130,15 +124,8 @@ int cdpr_rollout_velocity_launch(cdpr_handle_t h, int samples, int horizon, cons
     return CDPR_ERR_INVALID;
   }
   const uint64_t traj = (uint64_t)h->batch * (uint64_t)samples;
-  if (!h->d_roll_ref) HIP_TRY(h, hipMalloc(&h->d_roll_ref, (size_t)h->batch * 3 * sizeof(float)));
-  if (h->roll_cost_cap < traj) {  // grow-only; the stream may still be reading the old buffer
-    HIP_TRY(h, wait_stream(h));
-    if (h->d_roll_cost) (void)hipFree(h->d_roll_cost);
-    h->d_roll_cost = nullptr;
-    h->roll_cost_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->d_roll_cost, (size_t)traj * sizeof(float)));
-    h->roll_cost_cap = traj;
-  }
+  HIP_TRY(h, h->d_roll_ref.ensure(h, (size_t)h->batch * 3 * sizeof(float)));
+  HIP_TRY(h, h->d_roll_cost.ensure(h, (size_t)traj * sizeof(float)));
   // the caller may reuse ref_position on return: a pageable source is staged before hipMemcpyAsync returns
   HIP_TRY(h, hipMemcpyAsync(h->d_roll_ref, ref_position, (size_t)h->batch * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
   rc = rollout_enqueue(h, samples, horizon, d_commands, h->d_roll_ref, h->d_roll_cost);

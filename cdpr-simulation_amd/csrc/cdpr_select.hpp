@@ -3,7 +3,7 @@
 //
 // Through round 5 these rules lived inside cdpr_create and select_step_kernel (cdpr_engine.hip): what AUTO picks for a given
 // (cables, stages, batch, controller features, precision) could only be observed by running it.  Here they are one unit that
-// the engine calls (cdpr_create copies the plan into the handle; every launch asks planned_kernel for its kernel) and that
+// the engine calls (cdpr_create keeps the plan in the handle, its only copy; every launch asks planned_kernel for its kernel) and that
 // the C-ABI exposes without a GPU (cdpr_plan_kernel, include/cdpr.h): tests/test_kernel_selection.py enumerates the matrix
 // on the CPU and pins the kernel name for every cell (tests/golden/kernel_selection.json).
 //
@@ -84,6 +84,11 @@ inline std::string fast_path_obstacle(const cdpr_config_t& c) {
   return "";
 }
 
+// "lumped legs on": any of the lumped-leg terms is non-zero (the kernels' ph_lumped)
+inline bool lumped_legs_on(const cdpr_config_t& c) {
+  return c.passive_damping != 0.0 || c.leg_inertia != 0.0 || c.cable_axial_mass != 0.0 || c.anchor_point_mass != 0.0 || c.anchor_inertia != 0.0;
+}
+
 // What cdpr_create decides from the configuration alone.
 struct KernelPlan {
   int rc = CDPR_OK;      // CDPR_OK, or why no handle can be made (error says it)
@@ -120,8 +125,7 @@ inline KernelPlan plan_kernels(const cdpr_config_t& c, int cus = 256, EnvFn env 
   p.n = c.n_cables;
   p.batch = (uint32_t)c.batch;
   // the PHYS instantiations carry the lumped legs and the joint stop
-  const bool phys_cfg = cfg->passive_damping != 0.0 || cfg->leg_inertia != 0.0 || cfg->cable_axial_mass != 0.0 || cfg->anchor_point_mass != 0.0 ||
-                        cfg->anchor_inertia != 0.0 || cfg->travel_stop != 0;
+  const bool phys_cfg = lumped_legs_on(c) || cfg->travel_stop != 0;
   // per-robot commands run on the register-resident kernels too (PR instantiations); only what those cannot represent
   // (hold branch, cascades, long windows, cmdLimit 0), and per-robot modes combined with the lumped-leg physics or with
   // two Pids that fit different derivative windows, take the general controller path
@@ -146,8 +150,6 @@ inline KernelPlan plan_kernels(const cdpr_config_t& c, int cus = 256, EnvFn env 
   const bool clean64 = cfg->precision == 64 && windows_fit;
   // ... and with the optional physics - the joint stop, the lumped legs (round 6) - on uniform-mode handles without the hold branch:
   // the TSTOP instantiations
-  const bool lumped_cfg = cfg->passive_damping != 0.0 || cfg->leg_inertia != 0.0 || cfg->cable_axial_mass != 0.0 || cfg->anchor_point_mass != 0.0 || cfg->anchor_inertia != 0.0;
-  (void)lumped_cfg;
   // ... and derivative windows of 12 .. 32 samples as the ONLY thing beyond the register-resident path (round 6): the plain one-wave
   // fp64 kernel with a ring of 31 errors per cable (uniform-mode handles, reduced physics)
   // (later in round 6: with per-robot modes - both Pids on one window, as on every register-resident per-robot handle - and with the

@@ -113,7 +113,11 @@ struct F64Args {
 #endif
 
 constexpr int kWinLong = 31;  // the ring of a derivative window of 12 .. 32 samples (CDPR_MAX_D_BUFFER - 1)
-__host__ __device__ constexpr int f64_state_rows(int n, int w = kWin) { return 20 + (w + 1) * n; }
+// rows of the state and of the observable image that the host reads and writes by name: pose (7 rows) and twist (6) lead both; the state
+// goes on with the FK estimate (7) and the controller rows, the image with the FK residual, its iteration count, the flags, the joint rows
+constexpr int kF64Pose = 0, kF64Twist = 7, kF64StateFk = 13, kF64StateCtrl = 20;
+constexpr int kF64ObsResidual = 13, kF64ObsIterations = 14, kF64ObsFlags = 15, kF64ObsJoint = 16;
+__host__ __device__ constexpr int f64_state_rows(int n, int w = kWin) { return kF64StateCtrl + (w + 1) * n; }
 // HOLD handles keep BOTH Pids of every cable behind those rows: per cable mLastPosition (JFC.h:45), then per Pid (0 position,
 // 1 velocity) one packed word (kHwHead ... kHwWas below) |
 // mIerr | the window's values | the window's stamps (world steps, exact in a double) | mCmd | the biquads' states
@@ -130,7 +134,7 @@ __host__ __device__ constexpr int f64_hold_rows(int n, int hw = kHoldWin) { retu
 // the packed word of a Pid record (the bits of a double, moved, never computed with): bits 0-31 mLastTime as a world step | 32-37 ring
 // head | 38-43 samples in the window | 44-51 length of the newest run of consecutive steps, saturating | 52 mWasLastTime
 constexpr int kHwHead = 32, kHwCount = 38, kHwRun = 44, kHwWas = 52;
-__host__ __device__ constexpr int f64_obs_rows(int n) { return 16 + 3 * n; }
+__host__ __device__ constexpr int f64_obs_rows(int n) { return kF64ObsJoint + 3 * n; }
 
 // 1 / sqrt(x) to double precision: v_rsq_f64 (about 26 good bits) + two Newton steps, y <- y + y e / 2 with e = 1 - x y^2
 // (quadratic: 2^-26 -> 2^-51 -> rounding).  The library's sqrt() followed by a division is ~55 double instructions, this is
