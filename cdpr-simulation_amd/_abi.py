@@ -5,7 +5,7 @@ loader and the function prototypes are in `_native.py`.
 """
 import ctypes as C
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 MAX_CABLES = 12
 MAX_D_BUFFER = 32
 MAX_D_DEGREE = 4

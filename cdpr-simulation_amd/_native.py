@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("CDPR_LIB", "libcdpr_hip.so"))  # 
 # every symbol include/cdpr.h declares
 EXPORTS = [
     "cdpr_abi_version", "cdpr_config_size", "cdpr_device_count", "cdpr_device_pci_bus_id", "cdpr_bytes_per_state_step", "cdpr_derivative_weights",
-    "cdpr_create", "cdpr_destroy", "cdpr_reset", "cdpr_last_error", "cdpr_set_platform_state",
+    "cdpr_create", "cdpr_destroy", "cdpr_reset", "cdpr_last_error", "cdpr_set_platform_state", "cdpr_reset_robots", "cdpr_reset_robots_device",
     "cdpr_set_velocity_command", "cdpr_set_position_command", "cdpr_set_velocity_command_device",
     "cdpr_set_position_command_device", "cdpr_bind_velocity_command_device", "cdpr_bind_position_command_device",
     "cdpr_set_velocity_command_masked", "cdpr_set_position_command_masked", "cdpr_set_force_command", "cdpr_set_force_command_device",
@@ -61,6 +61,8 @@ def lib():
     L.cdpr_last_error.argtypes = [H]
     L.cdpr_last_error.restype = C.c_char_p
     L.cdpr_set_platform_state.argtypes = [H, fp, fp]
+    L.cdpr_reset_robots.argtypes = [H, C.POINTER(C.c_uint8), fp, fp]
+    L.cdpr_reset_robots_device.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in ("cdpr_set_velocity_command", "cdpr_set_position_command", "cdpr_set_force_command"):
         getattr(L, name).argtypes = [H, fp, C.c_size_t]
     for name in ("cdpr_set_velocity_command_device", "cdpr_set_position_command_device", "cdpr_bind_velocity_command_device",

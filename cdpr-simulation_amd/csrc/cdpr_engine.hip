@@ -227,7 +227,7 @@ void free_all(cdpr_engine* h) {
   for (CmdChannel& c : h->cmd)
     for (hipEvent_t ev : {c.stage_ev[0], c.stage_ev[1], c.free_ev})
       if (ev) (void)hipEventDestroy(ev);
-  for (hipEvent_t ev : {h->ev0, h->ev1})
+  for (hipEvent_t ev : {h->ev0, h->ev1, h->reset_ev[0], h->reset_ev[1]})
     if (ev) (void)hipEventDestroy(ev);
   for (hipStream_t st : {h->copy_stream, h->stream})
     if (st) (void)hipStreamDestroy(st);
@@ -249,7 +249,7 @@ void engine_reset_host(cdpr_engine* h) {
 
 // Everything the copy stream still has in flight lands before the compute stream (or the host) touches a pending buffer
 // in any other way than latching it (device-side staging, masked merges, resets).
-static int drain_copy_stream(cdpr_engine* h) {
+int drain_copy_stream(cdpr_engine* h) {
   if (h->copy_stream) HIP_TRY(h, hipStreamSynchronize(h->copy_stream));
   for (CmdChannel& c : h->cmd) c.ready_wait = nullptr;
   return CDPR_OK;

@@ -2,8 +2,8 @@
 // PinnedBuf), the handle (struct cdpr_engine: its routing is h->plan and nothing else, its buffers are owner members that go with
 // it), the error macros and the helpers one unit defines and another calls.  Units: cdpr_engine.hip (create / destroy, the general
 // path's set-up, commands, the fp32 launch chains, read-out), cdpr_engine_f64.hip (precision = 64: set-up, launch chain, read-out),
-// cdpr_engine_rollout.hip (cdpr_rollout_velocity*), cdpr_engine_solvers.hip (cdpr_solve_ik / fk / td).  Not installed, not part
-// of the C-ABI (include/cdpr.h is).
+// cdpr_engine_rollout.hip (cdpr_rollout_velocity*), cdpr_engine_solvers.hip (cdpr_solve_ik / fk / td), cdpr_engine_reset.hip
+// (cdpr_reset_robots*).  Not installed, not part of the C-ABI (include/cdpr.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -212,6 +212,13 @@ struct cdpr_engine {
   DevBuf<float> d_roll_ref;      // float[B][3]
   DevBuf<float> d_roll_cost;     // float[B][samples]
   uint64_t roll_pending = 0;     // trajectories of the launched, not yet fetched rollout
+  // cdpr_reset_robots (host form): the caller's mask, poses and twists go through one of two pinned staging blocks into persistent
+  // device scratch on the handle's stream ([uint8 mask[B], padded to 16 B | float pose[B][7] | float twist[B][6]], sized once: B is fixed)
+  DevBuf<char> d_reset_args;
+  PinnedBuf<char> h_reset_stage[2];
+  hipEvent_t reset_ev[2] = {nullptr, nullptr};  // the copy out of that staging block has completed
+  bool reset_ev_set[2] = {false, false};
+  int reset_idx = 0;
   // cdpr_config_t.precision = 64 (plan.fp64): the step in double (cdpr_step_kernel_f64.hpp); its own state, observables, tables
   DevBuf<double> d_state64, d_obs64;
   DevBuf<double> d_geom64;       // [n][7]
@@ -315,6 +322,7 @@ inline int ring_slot_of(uint64_t step, int w) { return (int)((step + (uint64_t)(
 
 // cdpr_engine.hip
 int set_device(cdpr_engine* h);
+int drain_copy_stream(cdpr_engine* h);
 int check_fault(cdpr_engine* h);
 int checked(cdpr_engine* h, int rc);
 void biquad_coefficients(const cdpr_filter_params_t& f, double co[5]);  // a0 a1 a2 b1 b2

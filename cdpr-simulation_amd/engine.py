@@ -92,6 +92,22 @@ class Engine:
         t = None if twist6 is None else np.ascontiguousarray(twist6, dtype=np.float32).reshape(self.B, 6)
         self._check(lib().cdpr_set_platform_state(self._h, _fp(p), _fp(t)))
 
+    def reset_robots(self, mask, pose7=None, twist6=None) -> None:
+        """Model reset of the robots with mask[b] != 0 (Config.perRobotCommands) while the others run on (cdpr_reset_robots):
+        platform at pose7[b] / twist6[b] (None: the home pose / zero; rows of the other robots are ignored), controller as after
+        Load (JFC.h:69-73, PLG.cpp:153-157).  The world clock, the other robots and every pending command stay as they are.
+        Queued on the engine's stream: after every update so far, before every later one; the arrays may be reused at once."""
+        m = np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.B)
+        p = None if pose7 is None else np.ascontiguousarray(pose7, dtype=np.float32).reshape(self.B, 7)
+        t = None if twist6 is None else np.ascontiguousarray(twist6, dtype=np.float32).reshape(self.B, 6)
+        self._check(lib().cdpr_reset_robots(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8)), _fp(p), _fp(t)))
+
+    def reset_robots_device(self, d_mask: int, d_pose7: int = 0, d_twist6: int = 0) -> None:
+        """The same from device buffers (uint8[B], float[B][7], float[B][6]; 0 = home pose / zero twist): nothing is copied or
+        synchronised, the buffers must stay valid until the stream has passed the reset (cdpr_reset_robots_device)."""
+        self._check(lib().cdpr_reset_robots_device(self._h, C.c_void_p(d_mask) if d_mask else None, C.c_void_p(d_pose7) if d_pose7 else None,
+                                                   C.c_void_p(d_twist6) if d_twist6 else None))
+
     def _command(self, fn, fn_masked, axes, mask) -> int:
         a = np.ascontiguousarray(axes, dtype=np.float32).ravel()
         if mask is None:

@@ -62,6 +62,16 @@ class ShardedEngine:
         for e, p, t in zip(self.engines, ps, ts):
             e.set_platform_state(p, t)
 
+    def reset_robots(self, mask, pose7=None, twist6=None):
+        """Engine.reset_robots over the shards: mask and rows split by shard_range, like the masked commands."""
+        import numpy as np
+
+        m = np.asarray(mask, dtype=np.uint8).reshape(self.B)
+        ps = [None] * len(self.engines) if pose7 is None else self._split(np.asarray(pose7, dtype=np.float32).reshape(self.B, 7), 7)
+        ts = [None] * len(self.engines) if twist6 is None else self._split(np.asarray(twist6, dtype=np.float32).reshape(self.B, 6), 6)
+        for e, (lo, hi), p, t in zip(self.engines, self.spans, ps, ts):
+            e.reset_robots(m[lo:hi], p, t)
+
     def _command(self, name, axes, mask):
         import numpy as np
 

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define CDPR_ABI_VERSION 6u   /* 6 = 5 + cdpr_plan_kernel, cdpr_kernel_name, CDPR_MAX_CABLES 8 -> 12 (cdpr_config_t's anchor arrays grow); 5 = 4 + cdpr_update_scheduled_kind, cdpr_device_pci_bus_id, cdpr_decode_observables_f64 */
+#define CDPR_ABI_VERSION 7u   /* 7 = 6 + cdpr_reset_robots, cdpr_reset_robots_device; 6 = 5 + cdpr_plan_kernel, cdpr_kernel_name, CDPR_MAX_CABLES 8 -> 12 (cdpr_config_t's anchor arrays grow); 5 = 4 + cdpr_update_scheduled_kind, cdpr_device_pci_bus_id, cdpr_decode_observables_f64 */
 #define CDPR_MAX_CABLES 12u         /* PLG.h:20 fixes 4 (kCableCount); cube.yaml:21-29 is a free-length `points` list: the engine takes 1..12
                                       (9..12: uniform-mode fp32 handles on the lane-per-robot kernels, FK and TD included; see cdpr_create) */
 #define CDPR_MAX_D_BUFFER 32u       /* Pid: mDbufferLength                      */
@@ -205,6 +205,28 @@ const char *cdpr_last_error(cdpr_handle_t h);       /* h may be NULL: last creat
  * twist6[B][6] (world-frame linear, angular).  Either may be NULL (unchanged).
  * Stands in for spawning the model at a pose (launch file `-x -y -z -R -P -Y`). */
 int cdpr_set_platform_state(cdpr_handle_t h, const float *pose7, const float *twist6);
+
+/* Model reset of chosen robots while the batch keeps running (a Monte-Carlo sweep, an RL-style environment batch or an MPC loop
+ * re-seeding the instances that diverged): the robots with robot_mask[b] != 0 (uint8[B]) are left exactly as cdpr_create /
+ * cdpr_reset leave every robot, at pose7[b] / twist6[b] (float[B][7] / float[B][6]; NULL = home_pose / zero; rows of the other
+ * robots are never read) in place of home_pose and zero:
+ *   platform   the pose as given (no normalisation, as cdpr_set_platform_state), the twist, the FK seed at the pose;
+ *   controller JointForceCalculator::reset() (JFC.h:69-73) plus the state Load leaves (PLG.cpp:153-157): Position mode, position
+ *              and velocity target 0, force 0, both Pids reset - integral 0, the next Pid::update is the "first" and returns 0
+ *              (Pid.cpp:123-126), derivative windows empty, stamps gone, biquad states 0, mCmd 0 - and mLastPosition 0;
+ *   read-outs  the robot's observables show the new pose and zeros elsewhere, as before the first publish; its `pid` debug row,
+ *              limit flags, FK residual and iterations and infeasible flag are cleared (precision = 64: in double).
+ * Untouched: the world-step counter and the publish clock (time goes on: a model reset, not a world reset), every bit of every
+ * other robot, the status word, the caller's bound or scheduled command buffers, and every pending command - one addressed to
+ * a reset robot stays pending and is latched at the next cdpr_update onto the reset robot, as a Joy sent right after Load.
+ * Stream-ordered: after every update queued so far, before every later one.  Needs cdpr_config_t.per_robot_commands = 1 (any
+ * such handle, precision = 64 included: a float pose becomes a double exactly), else CDPR_ERR_UNSUPPORTED - a uniform handle
+ * keeps one mode and one Pid call count for the whole batch.  NULL handle or mask: CDPR_ERR_INVALID.
+ * cdpr_reset_robots: host arrays, copied before the call returns; the work is queued, the stream is not waited for.
+ * cdpr_reset_robots_device: device buffers (a loop that computes its "done" mask on the GPU), nothing copied or synchronised;
+ * they must stay valid until the stream has passed the reset. */
+int cdpr_reset_robots(cdpr_handle_t h, const uint8_t *robot_mask, const float *pose7, const float *twist6);
+int cdpr_reset_robots_device(cdpr_handle_t h, const uint8_t *d_robot_mask, const float *d_pose7, const float *d_twist6);
 
 /* Replaces cableVelocityCommandCallback / cablePositionCommandCallback
  * (PLG.cpp:67-83).  `count` = number of floats in `axes`: n*B (one Joy per
