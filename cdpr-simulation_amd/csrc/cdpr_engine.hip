@@ -356,6 +356,14 @@ bool pair_stream_steady(const cdpr_engine* h, const StepArgs& a) {
   return h->step != 0 && h->mode != kModeForce && a.pid_calls >= a.nbuf && h->cfg.publish_period == 0.0 && !a.dbg && !a.travel_on &&
          !(a.vel_limit > 0.f) && !a.unilateral && a.effort >= 0.f && a.clamp_cmd && !h->sched_ready;
 }
+// May a launch of the role-split kernel with the arguments `a` take the controller wave's steady-state instantiation
+// (split_controller_wave<N, false, true, VEL>, cdpr_onestep_kernel.hpp)?  It has no code for anything the generic one tests per launch
+// and these facts decide: a uniform handle in Velocity or Position mode, past world step 0, the derivative window full, every step
+// published, no `pid` topic, no travel flags.  CDPR_SPLIT_STEADY=0: never (A/B, tests).  Same bits either way (tested).
+bool split_steady_launch(const cdpr_engine* h, const PlannedKernel& pk, const StepArgs& a) {
+  return pk.id == KernelId::Split && h->split_steady && !h->plan.per_robot && h->step != 0 && h->mode != kModeForce && a.pid_calls != 0 &&
+         a.pid_calls >= a.nbuf && h->cfg.publish_period == 0.0 && !a.dbg && !a.travel_on;
+}
 uint32_t step_block_threads(const cdpr_engine* h, int k) { return planned_kernel(h->plan, launch_shape(h, k)).block; }
 
 // cdpr_create's part of a general-path handle: the layout of the controller records, the records, the two Pids' parameter table
@@ -517,6 +525,15 @@ int warm_first_launch(cdpr_engine* h) {
   set_weight_row(h, a);
   hipLaunchKernelGGL(select_step_kernel(h, 1), dim3(1), dim3(step_block_threads(h, 1)), 0, h->stream, a);
   HIP_TRY(h, hipGetLastError());
+  // ... and of the role-split kernel's steady-state instantiations, which the launches take from the step on that fills the window
+  // (split_steady_launch): both modes' - a Joy of the other kind may arrive at any step
+  if (planned_kernel(h->plan, launch_shape(h, 1)).id == KernelId::Split && h->split_steady) {
+    for (const bool vel : {false, true}) {
+      copy_pid(vel ? h->pid_vel : h->pid_pos, a);
+      hipLaunchKernelGGL(pick_split_steady_kernel(h->n, vel), dim3(1), dim3(128), 0, h->stream, a);
+      HIP_TRY(h, hipGetLastError());
+    }
+  }
   HIP_TRY(h, wait_stream(h));
   return CDPR_OK;
 }
@@ -740,6 +757,9 @@ int run_steps(cdpr_engine* h, int nsteps, int per_launch, float4* record = nullp
     const int kk = h->sched_refresh ? std::max(k, 2) : k;
     const PlannedKernel pk = planned_kernel(h->plan, launch_shape(h, kk, pair_stream_steady(h, a)));
     StepKernel kern = step_kernel_of(h, pk);
+    // the role-split kernel keeps its identity (pk, cdpr_kernel_name) whichever instantiation of its controller wave a launch takes
+    h->last_variant = split_steady_launch(h, pk, a) ? 1 : 0;
+    if (h->last_variant) kern = pick_split_steady_kernel(h->n, h->mode == kModeVelocity);
     const dim3 block(pk.block);
     const bool stream = pk.id == KernelId::PairStream;  // steady state of a plain lane-pair handle: the branch-free several-steps kernel
     auto weights_for = [&](StepArgs& x) {                // ... which reads the weights by AGE from the row of ring position 0
@@ -937,6 +957,7 @@ static int build_handle(cdpr_engine* h) {
   fill_pid(cfg.position_pid, cfg.dt, h->pid_pos, h->wtab_host[1]);
   engine_reset_host(h);
   {
+    if (const char* ss = std::getenv("CDPR_SPLIT_STEADY")) h->split_steady = !(ss[0] == '0');
     const char* ng = std::getenv("CDPR_NO_GRAPH");
     h->use_graphs = !(ng && ng[0] == '1');
   }
@@ -1638,6 +1659,10 @@ int cdpr_get_limit_state(cdpr_handle_t h, uint32_t* cable_mask) {
     for (uint32_t b = 0; b < h->batch; ++b) cable_mask[b] >>= 1;  // bit 0 is the tension-distribution flag
   return checked(h, rc);
 }
+
+// Which instantiation the last step launch of run_steps took: 0 = the planned kernel as cdpr_kernel_name gives it, 1 = the role-split
+// kernel's steady-state controller wave (split_steady_launch).  Host-side state; for tests and A/B scripts, not part of the C-ABI header.
+int cdpr_debug_last_variant(cdpr_handle_t h) { return h ? h->last_variant : -1; }
 
 #ifdef CDPR_STAMPS
 // diagnostic builds only: point the step kernel at a stamp buffer (uint64[blocks][8]); nullptr disables

@@ -186,6 +186,8 @@ struct cdpr_engine {
   };
   std::vector<GraphEntry> graphs;
   PlannedKernel last_kernel;  // what the last step launch ran on (cdpr_kernel_name)
+  int last_variant = 0;       // ... and which instantiation of it (cdpr_debug_last_variant): 1 = the role-split kernel's steady-state controller wave
+  bool split_steady = true;   // CDPR_SPLIT_STEADY=0: the role-split kernel always runs its generic instantiation
   int cus = 256;
   bool use_graphs = true;
   CmdChannel cmd[kCmdKinds];  // command state, one record per kind

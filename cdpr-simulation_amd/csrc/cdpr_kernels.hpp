@@ -57,6 +57,7 @@ StepKernel pick_pr_kernel(bool single, bool rollout, bool lowreg, uint32_t n, bo
 StepKernel pick_onestep_kernel(uint32_t n, bool fk, bool td);
 StepKernel pick_onestep_persist_kernel(uint32_t n, bool fk, bool td);  // one wave per SIMD walking over blocks of 64 robots
 StepKernel pick_split_kernel(uint32_t n);
+StepKernel pick_split_steady_kernel(uint32_t n, bool vel);  // the same kernel for steady-state launches (split_steady_launch, cdpr_engine.hip)
 StepKernel pick_pr_split_kernel(uint32_t n);
 // k_pair.hip / k_cable.hip: the other two wavefront mappings
 StepKernel pick_pair_kernel(bool single, uint32_t n, bool fk, bool td);

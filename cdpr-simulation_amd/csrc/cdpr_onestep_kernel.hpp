@@ -39,12 +39,13 @@ CDPR_DEV void row_to_lds(const float4* src, float4* dst_row) {
 // Pid::update for every cable pair (Pid.cpp:122-191; the same statements as in cdpr_step_kernel).  PR (per-robot handles):
 // `calls` and `is_vel` are the lane's own, the coefficients and weights are selected per lane, and a robot whose Pid was
 // just reset (calls == 0: "first call returns 0", Pid.cpp:123-126) keeps force 0 and its integral.
-template <int NP, bool PR = false>
+// FULL: the caller knows that the derivative window holds nbuf samples (calls >= nbuf).
+template <int NP, bool PR = false, bool FULL = false>
 CDPR_DEV void pid_pairs(const StepArgs& a, int calls, bool is_vel, const v2f (&desired)[NP], const v2f (&actual)[NP], const v2f (&win)[NP][kWin],
                         v2f (&ierr)[NP], v2f (&f)[NP], v2f (&e_new)[NP], float& dbg_p, float& dbg_i, float& dbg_d, bool is_force = false) {
   const PidCoef c = pid_coef<PR>(a, is_vel);
   const bool run = (!PR || calls != 0) && !is_force;  // is_force (PR only): the robot is driven open loop (JFC.cpp:67-70)
-  const bool full = calls >= c.nbuf;  // derive(): 0 until the window holds nbuf samples (Pid.cpp:200-203)
+  const bool full = FULL || calls >= c.nbuf;  // derive(): 0 until the window holds nbuf samples (Pid.cpp:200-203)
   // the host put the weights of this launch's ring position (StepArgs::ring_slot) into the arguments; on per-robot handles
   // both Pids fit the same window (same length and degree: cdpr_create sends anything else down the general path), so
   // the weights stay scalars whatever the lane's mode
@@ -654,51 +655,35 @@ CDPR_DEV void split_estimator_wave(const StepArgs& a, float* geo, float gval, ui
   __builtin_amdgcn_s_barrier();  // #2: tensions and estimator results are out
 }
 
-// PR = true: per-robot handles (StepArgs::meta, see cdpr_step_kernel.hpp): the controller wave takes mode and Pid call
-// count per lane; the estimator wave is the same.
-template <int N, bool PR = false>
-__global__ __launch_bounds__(128, 2) void cdpr_split_kernel(const StepArgs a) {
+// The controller wave of a role-split workgroup (cdpr_split_kernel): platform + controller rows -> IK (structure matrix, joint positions /
+// rates) -> early observables -> per-cable PID -> forces out -> [tensions from the estimator wave] SetForce limits -> remaining
+// observables -> world step -> state.  x_force / x_tension: v2f rows of 64, x_est: float rows of 64 (split_estimator_wave's XS = ES = 64).
+//
+// STEADY: the instantiation for launches of which the host knows (split_steady_launch, cdpr_engine.hip) that the handle is uniform and in
+// Velocity (VEL) or Position mode, that this is not world step 0, that the derivative window is full (calls >= nbuf), that the step is
+// published and that neither the `pid` topic nor the travel flags are on.  Every floating-point operation is the generic instantiation's,
+// in its order and on its operands (same device functions, same bits: tested); what goes is what those facts make dead or wave-uniform:
+// the selects on `full`, on the mode and on the first step with the zero defaults they choose from, the debug and travel-flag code, and
+// with them the 14 spilled scalar registers (0 here, 234 VGPRs against 247).  The ring row's layout is a scalar branch on the launch's
+// ring position (the compiler turns the half-row choice back into selects where that is shorter).  Measured and not in the tree: the
+// rows through a buffer descriptor instead of a 64-bit address each, 0.2 us per step slower.  The clamps stay
+// max(min()) pairs: v_med3_f32 returns the LOWER bound for a NaN operand where the pair returns the upper one, so it is not bit-equal
+// for any of the bounds in use.
+template <int N, bool PR, bool STEADY, bool VEL>
+CDPR_DEV void split_controller_wave(const StepArgs& a, float* geo, float gval, uint32_t lane, uint32_t r, uint32_t rr, bool live, size_t st, uint32_t off,
+                                    uint32_t woff, const float4& p0, const float4& p1, const float4& p2, const float4& p3, v2f* x_force, const v2f* x_tension,
+                                    const float* x_est) {
+  static_assert(!(STEADY && PR), "the steady instantiation serves uniform handles");
   constexpr int NP = cable_pairs(N);
   constexpr int P = plat_slots(true);
   constexpr int G = joint_groups(N);
   constexpr int NH = (NP + 1) / 2;
-  __shared__ __attribute__((aligned(16))) float lds[2][NP * kGeomFloatsPerPair];  // one geometry copy per wave: no barrier before first use
-  __shared__ v2f x_force[NP][64];      // controller -> estimator: raw per-cable forces
-  __shared__ v2f x_tension[NP][64];    // estimator -> controller: distributed tensions (before the SetForce limits)
-  __shared__ float x_est[6][64];       // estimator -> controller: fk x y z, residual, iterations, infeasible flag
-
-  // which of the two waves estimates: swapped from workgroup to workgroup (bits of the workgroup index chosen by the
-  // host, StepArgs::split_swap) so that the two waves a SIMD hosts tend to be one of each role
-  const uint32_t swap = __builtin_popcount(blockIdx.x & a.split_swap) & 1u;
-  const uint32_t wave = (threadIdx.x >> 6) ^ swap, lane = threadIdx.x & 63u;
-  const uint32_t r = blockIdx.x * 64u + lane;
-  const uint32_t rr = (r < a.batch) ? r : (a.batch - 1u);  // tail lanes shadow the last robot, stores are masked
-  const bool live = r < a.batch;
-  const size_t st = a.stride;
-  const uint32_t off = rr * 16u, woff = r * 16u;
-  float* const geo = lds[wave];
-
-  if (wave == 0) CDPR_SPLIT_STAMP(0);
-#ifdef CDPR_STAMPS
-  if (a.stamps && lane == 0)  // where this wave runs: HW_ID (wave, SIMD, CU, SH, SE) | XCC_ID << 16, per PHYSICAL wave of the workgroup
-    reinterpret_cast<uint32_t*>(&a.stamps[(size_t)blockIdx.x * 8 + 7])[threadIdx.x >> 6] =
-        (__builtin_amdgcn_s_getreg((16 - 1) << 11 | 4) & 0xffffu) | ((__builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) & 0xfu) << 16);
-#endif
-  const float gval = (lane < NP * kGeomFloatsPerPair) ? a.geom[lane] : 0.f;
-  const float4 p0 = load_slot(a.state, st, 0, off), p1 = load_slot(a.state, st, 1, off), p2 = load_slot(a.state, st, 2, off),
-               p3 = load_slot(a.state, st, 3, off);
-  if (wave == 0) {
-    split_estimator_wave<N, 64, 64>(a, geo, gval, lane, live, st, off, woff, p0, p1, p3, &x_force[0][0], &x_tension[0][0], &x_est[0][0]);
-    return;
-  }
-  // ---------------------------------------------------------------------------------------------------- controller wave
 #if CDPR_SPLIT_PRIO == 2 || CDPR_SPLIT_PRIO == 5
   __builtin_amdgcn_s_setprio(3);  // (5: from its first instruction to the force hand-off)
 #endif
 #if CDPR_CTL_LOAD_DELAY > 0
   __builtin_amdgcn_s_sleep(CDPR_CTL_LOAD_DELAY);  // the estimator waves' two rows go first through the memory system
 #endif
-  constexpr int kCtrl = 5 * NP + NH;
   float4 wraw[NP][5], hraw[NH];
 #pragma unroll
   for (int k = 0; k < NP; ++k) {
@@ -707,7 +692,6 @@ __global__ __launch_bounds__(128, 2) void cdpr_split_kernel(const StepArgs a) {
   }
 #pragma unroll
   for (int g = 0; g < NH; ++g) hraw[g] = load_slot(a.state, st, P + 5 * NP + g, off);
-  (void)kCtrl;
   v2f desired[NP];
 #pragma unroll
   for (int k = 0; k < NP; ++k) desired[k] = splat(0.f);
@@ -751,7 +735,7 @@ __global__ __launch_bounds__(128, 2) void cdpr_split_kernel(const StepArgs a) {
                     fma2(s.vz, jac[k][2], fma2(s.vy, jac[k][1], splat(s.vx) * jac[k][0])))));
     }
   }
-  const bool publish = (a.publish_mask & 1ull) != 0ull;
+  const bool publish = STEADY || (a.publish_mask & 1ull) != 0ull;
   if (publish && live) {
     store_slot(a.obs, st, 0, woff, make_float4(s.px, s.py, s.pz, s.qx));
     store_slot(a.obs, st, 1, woff, make_float4(s.qy, s.qz, s.qw, s.vx));
@@ -775,16 +759,16 @@ __global__ __launch_bounds__(128, 2) void cdpr_split_kernel(const StepArgs a) {
   }
   float dbg_p = 0.f, dbg_i = 0.f, dbg_d = 0.f;
   bool dbg_wrote = false;
-  const bool first_world = (a.flags & kFlagFirstWorldStep) != 0u;
+  const bool first_world = !STEADY && (a.flags & kFlagFirstWorldStep) != 0u;
   uint32_t meta = 0u;
   if (PR) meta = a.meta[rr];
   const int calls = PR ? (int)(meta >> kMetaCallShift) : a.pid_calls;
   if (PR && live && !first_world) a.meta[r] = (uint8_t)((meta & kMetaModeMask) | ((uint32_t)min(calls + 1, (int)kMetaCallMax) << kMetaCallShift));
-  const bool force_mode = !PR && (a.flags & kFlagForceMode) != 0u;  // UpdateMode::Force on a uniform handle (JFC.cpp:67-70)
+  const bool force_mode = !STEADY && !PR && (a.flags & kFlagForceMode) != 0u;  // UpdateMode::Force on a uniform handle (JFC.cpp:67-70)
   if (force_mode && !first_world) {
 #pragma unroll
     for (int k = 0; k < NP; ++k) f[k] = desired[k];
-  } else if (!first_world && (PR || calls != 0)) {
+  } else if (STEADY || (!first_world && (PR || calls != 0))) {
     v2f win[NP][kWin];
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
@@ -794,7 +778,7 @@ __global__ __launch_bounds__(128, 2) void cdpr_split_kernel(const StepArgs a) {
         win[k][2 * m + 1] = (v2f){wraw[k][m].z, wraw[k][m].w};
       }
     }
-    const bool actual_is_vel = PR ? ((meta & kMetaModeMask) == kMetaVelocity) : ((a.flags & kFlagActualIsVelocity) != 0u);
+    const bool actual_is_vel = STEADY ? VEL : PR ? ((meta & kMetaModeMask) == kMetaVelocity) : ((a.flags & kFlagActualIsVelocity) != 0u);
     v2f actual[NP];
 #pragma unroll
     for (int k = 0; k < NP; ++k) actual[k] = actual_is_vel ? qd[k] : q[k];
@@ -803,14 +787,22 @@ __global__ __launch_bounds__(128, 2) void cdpr_split_kernel(const StepArgs a) {
 #if CDPR_SPLIT_PRIO == 3 || CDPR_SPLIT_PRIO == 4
     __builtin_amdgcn_s_setprio(3);  // (experiment) the forces are what the estimator wave will wait for
 #endif
-    pid_pairs<NP, PR>(a, calls, actual_is_vel, desired, actual, win, ierr, f, e_new, dbg_p, dbg_i, dbg_d, is_force);
+    pid_pairs<NP, PR, STEADY>(a, calls, actual_is_vel, desired, actual, win, ierr, f, e_new, dbg_p, dbg_i, dbg_d, is_force);
     dbg_wrote = (!PR || calls != 0) && !is_force;
     if (live) {
 #pragma unroll
       for (int m = 0; m < 5; ++m) {
         if (m == (ring_slot >> 1)) {
+          if (!STEADY) {
 #pragma unroll
-          for (int k = 0; k < NP; ++k) CDPR_STORE_STATE(a.state, st, P + 5 * k + m, woff, ring_row(win[k], m, e_new[k], ring_slot));
+            for (int k = 0; k < NP; ++k) CDPR_STORE_STATE(a.state, st, P + 5 * k + m, woff, ring_row(win[k], m, e_new[k], ring_slot));
+          } else if (ring_slot & 1) {  // the row's layout by a scalar branch: the new error in the upper half ...
+#pragma unroll
+            for (int k = 0; k < NP; ++k) CDPR_STORE_STATE(a.state, st, P + 5 * k + m, woff, make_float4(win[k][2 * m].x, win[k][2 * m].y, e_new[k].x, e_new[k].y));
+          } else {  // ... or in the lower one
+#pragma unroll
+            for (int k = 0; k < NP; ++k) CDPR_STORE_STATE(a.state, st, P + 5 * k + m, woff, make_float4(e_new[k].x, e_new[k].y, win[k][2 * m + 1].x, win[k][2 * m + 1].y));
+          }
         }
       }
 #pragma unroll
@@ -821,7 +813,7 @@ __global__ __launch_bounds__(128, 2) void cdpr_split_kernel(const StepArgs a) {
     }
   }
 #pragma unroll
-  for (int k = 0; k < NP; ++k) x_force[k][lane] = f[k];
+  for (int k = 0; k < NP; ++k) x_force[k * 64 + lane] = f[k];
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the forces are in LDS (vector memory operations stay in flight)
   CDPR_CTL_STAMP(4);
@@ -834,9 +826,9 @@ __global__ __launch_bounds__(128, 2) void cdpr_split_kernel(const StepArgs a) {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
   v2f applied[NP];
 #pragma unroll
-  for (int k = 0; k < NP; ++k) applied[k] = x_tension[k][lane];
-  const float fkx = x_est[0][lane], fky = x_est[1][lane], fkz = x_est[2][lane], fk_res = x_est[3][lane], fk_it = x_est[4][lane],
-              td_flag = x_est[5][lane];
+  for (int k = 0; k < NP; ++k) applied[k] = x_tension[k * 64 + lane];
+  const float fkx = x_est[0 * 64 + lane], fky = x_est[1 * 64 + lane], fkz = x_est[2 * 64 + lane], fk_res = x_est[3 * 64 + lane],
+              fk_it = x_est[4 * 64 + lane], td_flag = x_est[5 * 64 + lane];
   if (a.vel_limit > 0.f) {  // Joint::SetForce velocity truncation [EXT]
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
@@ -848,7 +840,7 @@ __global__ __launch_bounds__(128, 2) void cdpr_split_kernel(const StepArgs a) {
 #pragma unroll
     for (int k = 0; k < NP; ++k) applied[k] = max2(min2(applied[k], splat(a.effort)), splat(-a.effort));
   }
-  if (a.dbg && live) {  // `pid` topic, cable 0 only (PLG.cpp:223-227; Pid.cpp:139-142,158-168)
+  if (!STEADY && a.dbg && live) {  // `pid` topic, cable 0 only (PLG.cpp:223-227; Pid.cpp:139-142,158-168)
     float* d = a.dbg + (size_t)r * 9;
     if (dbg_wrote) {
       d[0] = dbg_p;
@@ -859,7 +851,7 @@ __global__ __launch_bounds__(128, 2) void cdpr_split_kernel(const StepArgs a) {
     d[4] = applied[0].x;
   }
   if (publish && live) {
-    store_slot(a.obs, st, 3, woff, make_float4(s.wz, fk_res, fk_it, a.travel_on ? pack_flags((int)td_flag, travel_mask<N>(a, q)) : td_flag));
+    store_slot(a.obs, st, 3, woff, make_float4(s.wz, fk_res, fk_it, (!STEADY && a.travel_on) ? pack_flags((int)td_flag, travel_mask<N>(a, q)) : td_flag));
 #pragma unroll
     for (int g = 0; g < G; ++g) {
       const int k0 = 2 * g, k1 = (2 * g + 1 < NP) ? 2 * g + 1 : 2 * g;
@@ -894,5 +886,49 @@ __global__ __launch_bounds__(128, 2) void cdpr_split_kernel(const StepArgs a) {
   }
   CDPR_CTL_STAMP(6);
 }
+
+// PR = true: per-robot handles (StepArgs::meta, see cdpr_step_kernel.hpp): the controller wave takes mode and Pid call
+// count per lane; the estimator wave is the same.
+// (the kernel's body: cdpr_split_kernel<N, PR> and cdpr_split_steady_kernel<N, VEL> below differ in the controller wave's instantiation only)
+template <int N, bool PR, bool STEADY, bool VEL>
+CDPR_DEV void split_kernel_body(const StepArgs& a) {
+  constexpr int NP = cable_pairs(N);
+  __shared__ __attribute__((aligned(16))) float lds[2][NP * kGeomFloatsPerPair];  // one geometry copy per wave: no barrier before first use
+  __shared__ v2f x_force[NP][64];      // controller -> estimator: raw per-cable forces
+  __shared__ v2f x_tension[NP][64];    // estimator -> controller: distributed tensions (before the SetForce limits)
+  __shared__ float x_est[6][64];       // estimator -> controller: fk x y z, residual, iterations, infeasible flag
+
+  // which of the two waves estimates: swapped from workgroup to workgroup (bits of the workgroup index chosen by the
+  // host, StepArgs::split_swap) so that the two waves a SIMD hosts tend to be one of each role
+  const uint32_t swap = __builtin_popcount(blockIdx.x & a.split_swap) & 1u;
+  const uint32_t wave = (threadIdx.x >> 6) ^ swap, lane = threadIdx.x & 63u;
+  const uint32_t r = blockIdx.x * 64u + lane;
+  const uint32_t rr = (r < a.batch) ? r : (a.batch - 1u);  // tail lanes shadow the last robot, stores are masked
+  const bool live = r < a.batch;
+  const size_t st = a.stride;
+  const uint32_t off = rr * 16u, woff = r * 16u;
+  float* const geo = lds[wave];
+
+  if (wave == 0) CDPR_SPLIT_STAMP(0);
+#ifdef CDPR_STAMPS
+  if (a.stamps && lane == 0)  // where this wave runs: HW_ID (wave, SIMD, CU, SH, SE) | XCC_ID << 16, per PHYSICAL wave of the workgroup
+    reinterpret_cast<uint32_t*>(&a.stamps[(size_t)blockIdx.x * 8 + 7])[threadIdx.x >> 6] =
+        (__builtin_amdgcn_s_getreg((16 - 1) << 11 | 4) & 0xffffu) | ((__builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) & 0xfu) << 16);
+#endif
+  const float gval = (lane < NP * kGeomFloatsPerPair) ? a.geom[lane] : 0.f;
+  const float4 p0 = load_slot(a.state, st, 0, off), p1 = load_slot(a.state, st, 1, off), p2 = load_slot(a.state, st, 2, off),
+               p3 = load_slot(a.state, st, 3, off);
+  if (wave == 0) {
+    split_estimator_wave<N, 64, 64>(a, geo, gval, lane, live, st, off, woff, p0, p1, p3, &x_force[0][0], &x_tension[0][0], &x_est[0][0]);
+    return;
+  }
+  split_controller_wave<N, PR, STEADY, VEL>(a, geo, gval, lane, r, rr, live, st, off, woff, p0, p1, p2, p3, &x_force[0][0], &x_tension[0][0], &x_est[0][0]);
+}
+template <int N, bool PR = false>
+__global__ __launch_bounds__(128, 2) void cdpr_split_kernel(const StepArgs a) { split_kernel_body<N, PR, false, false>(a); }
+// The same kernel with the controller wave's steady-state instantiation (split_controller_wave<N, false, true, VEL>): the host's choice
+// per launch (split_steady_launch, cdpr_engine.hip), reported under cdpr_split_kernel<N, false>'s name by cdpr_kernel_name.
+template <int N, bool VEL>
+__global__ __launch_bounds__(128, 2) void cdpr_split_steady_kernel(const StepArgs a) { split_kernel_body<N, false, true, VEL>(a); }
 
 }  // namespace cdpr

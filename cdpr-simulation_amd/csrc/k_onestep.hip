@@ -18,6 +18,15 @@ StepKernel pick_split_kernel(uint32_t n) {
   }
   return nullptr;
 }
+// the role-split kernel with the controller wave's steady-state instantiation (cdpr_split_steady_kernel<N, VEL>)
+StepKernel pick_split_steady_kernel(uint32_t n, bool vel) {
+  switch (n) {
+    case 6: return vel ? cdpr_split_steady_kernel<6, true> : cdpr_split_steady_kernel<6, false>;
+    case 7: return vel ? cdpr_split_steady_kernel<7, true> : cdpr_split_steady_kernel<7, false>;
+    case 8: return vel ? cdpr_split_steady_kernel<8, true> : cdpr_split_steady_kernel<8, false>;
+  }
+  return nullptr;
+}
 StepKernel pick_pr_split_kernel(uint32_t n) {
   switch (n) {
     case 6: return cdpr_split_kernel<6, true>;

@@ -225,6 +225,14 @@ class Engine:
         return buf.value.decode()
 
     @property
+    def last_variant(self) -> int:
+        """Which instantiation of `kernel_name` the last step launch took (cdpr_debug_last_variant, a debug getter outside the
+        C-ABI header): 1 = the role-split kernel with its steady-state controller wave, 0 = the kernel as named."""
+        fn = lib().cdpr_debug_last_variant
+        fn.argtypes, fn.restype = [C.c_void_p], C.c_int
+        return int(fn(self._h))
+
+    @property
     def mapping(self) -> str:
         return {_abi.MAP_LANE_PER_ROBOT: "lane-per-robot", _abi.MAP_LANE_PAIR: "lane-pair", _abi.MAP_LANE_PER_CABLE: "lane-per-cable"}.get(int(lib().cdpr_mapping(self._h)), "auto")
 
