@@ -105,10 +105,7 @@ __global__ __launch_bounds__(128, 1) void cdpr_gen_split_kernel(const StepArgs a
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
   Platform s;
-  s.px = p0.x; s.py = p0.y; s.pz = p0.z; s.qx = p0.w;
-  s.qy = p1.x; s.qz = p1.y; s.qw = p1.z; s.vx = p1.w;
-  s.vy = p2.x; s.vz = p2.y; s.wx = p2.z; s.wy = p2.w;
-  s.wz = p3.x;
+  unpack_platform(p0, p1, p2, p3.x, s);
 
   const int now = g.now_step;
   const bool first_world = (a.flags & kFlagFirstWorldStep) != 0u;
@@ -190,27 +187,8 @@ __global__ __launch_bounds__(128, 1) void cdpr_gen_split_kernel(const StepArgs a
   for (int k = 0; k < NP; ++k) applied[k] = x_tension[k][lane];
   const float fkx = x_est[0][lane], fky = x_est[1][lane], fkz = x_est[2][lane], fk_res = x_est[3][lane], fk_it = x_est[4][lane],
               td_flag = x_est[5][lane];
-  if (a.vel_limit > 0.f) {  // Joint::SetForce velocity truncation [EXT]
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      applied[k].x = (qd[k].x > a.vel_limit && applied[k].x > 0.f) || (qd[k].x < -a.vel_limit && applied[k].x < 0.f) ? 0.f : applied[k].x;
-      applied[k].y = (qd[k].y > a.vel_limit && applied[k].y > 0.f) || (qd[k].y < -a.vel_limit && applied[k].y < 0.f) ? 0.f : applied[k].y;
-    }
-  }
-  if (a.effort >= 0.f) {  // Joint::SetForce clamp (cube.sdf:438)
-#pragma unroll
-    for (int k = 0; k < NP; ++k) applied[k] = max2(min2(applied[k], splat(a.effort)), splat(-a.effort));
-  }
-  if (a.dbg && live) {  // `pid` topic, cable 0 only: stale entries stay (Pid.cpp:139-142,158-168)
-    float* d = a.dbg + (size_t)r * 9;
-    if (dbg.pi) {
-      d[0] = dbg.p;
-      d[1] = dbg.i;
-      d[3] = dbg.des;
-    }
-    if (dbg.dw) d[2] = dbg.d;
-    d[4] = applied[0].x;
-  }
+  setforce_limits<NP>(a, qd, applied);
+  if (a.dbg && live) write_pid_topic(a.dbg + (size_t)r * 9, dbg.pi, dbg.dw, dbg.p, dbg.i, dbg.d, dbg.des, applied[0].x);
   if (publish && live) {  // the rest of the observables
     store_slot(obs, st, 3, woff, make_float4(s.wz, fk_res, fk_it, pack_flags((int)td_flag, travel_mask<N>(a, q))));
 #pragma unroll
@@ -354,18 +332,8 @@ CDPR_DEV void lean_controller_epilogue(const StepArgs& a, LeanShared<N>& sm, flo
   for (int k = 0; k < NP; ++k) applied[k] = x_tension[k][lane];
   const float fkx = x_est[0][lane], fky = x_est[1][lane], fkz = x_est[2][lane], fk_res = x_est[3][lane], fk_it = x_est[4][lane],
               td_flag = x_est[5][lane];
-  if (a.vel_limit > 0.f) {  // Joint::SetForce velocity truncation [EXT]
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      applied[k].x = (qd[k].x > a.vel_limit && applied[k].x > 0.f) || (qd[k].x < -a.vel_limit && applied[k].x < 0.f) ? 0.f : applied[k].x;
-      applied[k].y = (qd[k].y > a.vel_limit && applied[k].y > 0.f) || (qd[k].y < -a.vel_limit && applied[k].y < 0.f) ? 0.f : applied[k].y;
-    }
-  }
-  if (a.effort >= 0.f) {  // Joint::SetForce clamp (cube.sdf:438)
-#pragma unroll
-    for (int k = 0; k < NP; ++k) applied[k] = max2(min2(applied[k], splat(a.effort)), splat(-a.effort));
-  }
-  if (a.dbg) {  // `pid` topic, cable 0 only: stale entries stay (Pid.cpp:139-142,158-168)
+  setforce_limits<NP>(a, qd, applied);
+  if (a.dbg) {  // `pid` topic: write_pid_topic's five words, stores predicated through their offsets (no divergent branch here)
     const auto drs = __builtin_amdgcn_make_buffer_rsrc(a.dbg, 0, (int)(a.batch * 9u * sizeof(float)), 0x00020000);
     const uint32_t d0 = r * 36u;
     auto put = [&](bool on, uint32_t k, float v) { __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), drs, on ? d0 + 4u * k : 0xFFFFFFFFu, 0, 0); };
@@ -489,10 +457,7 @@ CDPR_LEAN_TAIL_ATTR void gen_lean_cold_tail(lean_f4 s0, lean_f4 s1, lean_f4 s2, 
     for (int i = 0; i < N; ++i) target[i] = tv[i];
   }
   Platform s;
-  s.px = s0.x; s.py = s0.y; s.pz = s0.z; s.qx = s0.w;
-  s.qy = s1.x; s.qz = s1.y; s.qw = s1.z; s.vx = s1.w;
-  s.vy = s2.x; s.vz = s2.y; s.wx = s2.z; s.wy = s2.w;
-  s.wz = s_wz;
+  unpack_platform(s0, s1, s2, s_wz, s);
   v2f q[NP], qd[NP];  // pairs 2k, 2k+1 of q in spill[k / 2], of qd behind them, then the structure matrix (LeanSpill)
 #pragma unroll
   for (int k = 0; k < NP; k += 2) {
@@ -606,10 +571,7 @@ __global__ __launch_bounds__(128, 2) void cdpr_gen_lean_kernel(const StepArgs a,
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
   Platform s;
-  s.px = p0.x; s.py = p0.y; s.pz = p0.z; s.qx = p0.w;
-  s.qy = p1.x; s.qz = p1.y; s.qw = p1.z; s.vx = p1.w;
-  s.vy = p2.x; s.vz = p2.y; s.wx = p2.z; s.wy = p2.w;
-  s.wz = p3.x;
+  unpack_platform(p0, p1, p2, p3.x, s);
 
   const int now = g.now_step;
   int sel[N];

@@ -1416,10 +1416,7 @@ __global__ __launch_bounds__(64, 1) void cdpr_gen_step_kernel(const StepArgs a, 
   CDPR_STAMP(2);
 #endif
   Platform s;
-  s.px = p0.x; s.py = p0.y; s.pz = p0.z; s.qx = p0.w;
-  s.qy = p1.x; s.qz = p1.y; s.qw = p1.z; s.vx = p1.w;
-  s.vy = p2.x; s.vz = p2.y; s.wx = p2.z; s.wy = p2.w;
-  s.wz = p3.x;
+  unpack_platform(p0, p1, p2, p3.x, s);
   float fkx = p3.y, fky = p3.z, fkz = p3.w, fkqx = p4.x, fkqy = p4.y, fkqz = p4.z, fkqw = p4.w;
   float cost = 0.f, refx = 0.f, refy = 0.f, refz = 0.f;
   if (ROLLOUT) {
@@ -1612,16 +1609,7 @@ __global__ __launch_bounds__(64, 1) void cdpr_gen_step_kernel(const StepArgs a, 
       for (int k = 0; k < NP; ++k) applied[k] = max2(min2(applied[k], splat(a.effort)), splat(-a.effort));
     }
 
-    if (!ROLLOUT && a.dbg && live) {  // `pid` topic, cable 0 only: stale entries stay (Pid.cpp:139-142,158-168)
-      float* d = a.dbg + (size_t)r * 9;
-      if (dbg.pi) {
-        d[0] = dbg.p;
-        d[1] = dbg.i;
-        d[3] = dbg.des;
-      }
-      if (dbg.dw) d[2] = dbg.d;
-      d[4] = applied[0].x;
-    }
+    if (!ROLLOUT && a.dbg && live) write_pid_topic(a.dbg + (size_t)r * 9, dbg.pi, dbg.dw, dbg.p, dbg.i, dbg.d, dbg.des, applied[0].x);
     if (publish && live) {  // the rest of the observables
       store_slot(obs, st, 3, woff, make_float4(s.wz, fk_res, (float)fk_it, pack_flags(td_flag, travel_mask<N>(a, q))));
 #pragma unroll

@@ -1,8 +1,10 @@
 // cdpr_onestep_kernel.hpp — the one-world-step-per-launch kernel (gfx950, fp32, lane-per-robot), second generation.
 //
-// Same arithmetic as cdpr_step_kernel<N, FK, TD, SINGLE = true> (the device functions are shared, the file is
-// compiled with -ffp-contract=off, so the two are bit-identical — tested), re-staged around what the profile of the
-// first generation showed (profiles/r02a_onestep_summary.json: one wave per SIMD, 47 % of wave cycles issuing,
+// Same arithmetic as cdpr_step_kernel<N, FK, TD, SINGLE = true> (the device functions are shared: the leaf helpers of
+// cdpr_step_kernel.hpp and the stages of cdpr_step_stages.hpp that this file calls - unpack_platform, setforce_limits,
+// write_pid_topic; the other stages are restated statement by statement, with a pointer where a shared function exists -
+// and the file is compiled with -ffp-contract=off, so the two are bit-identical — tested), re-staged around what the
+// profile of the first generation showed (profiles/r02a_onestep_summary.json: one wave per SIMD, 47 % of wave cycles issuing,
 // 27 % waiting on memory, 25 % dependent-issue stalls):
 //
 //   * the controller rows (20 ring rows + 2 integral rows at n = 8: 22 of the 29 rows a robot reads) are NOT needed
@@ -180,10 +182,7 @@ __global__ __launch_bounds__(64, 1) void cdpr_onestep_kernel(const StepArgs a_in
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
   Platform s;
-  s.px = p0.x; s.py = p0.y; s.pz = p0.z; s.qx = p0.w;
-  s.qy = p1.x; s.qz = p1.y; s.qw = p1.z; s.vx = p1.w;
-  s.vy = p2.x; s.vz = p2.y; s.wx = p2.z; s.wy = p2.w;
-  s.wz = p3.x;
+  unpack_platform(p0, p1, p2, p3.x, s);
   float fkx = p3.y, fky = p3.z, fkz = p3.w, fkqx = p4.x, fkqy = p4.y, fkqz = p4.z, fkqw = p4.w;
 
   // ---- controller rows and the Joy: global -> LDS, in flight until the PID stage.  Issued AFTER the platform rows
@@ -399,28 +398,9 @@ __global__ __launch_bounds__(64, 1) void cdpr_onestep_kernel(const StepArgs a_in
 #pragma unroll
     for (int k = 0; k < NP; ++k) applied[k] = f[k];
   }
-  if (a.vel_limit > 0.f) {  // Joint::SetForce velocity truncation [EXT]
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      applied[k].x = (qd[k].x > a.vel_limit && applied[k].x > 0.f) || (qd[k].x < -a.vel_limit && applied[k].x < 0.f) ? 0.f : applied[k].x;
-      applied[k].y = (qd[k].y > a.vel_limit && applied[k].y > 0.f) || (qd[k].y < -a.vel_limit && applied[k].y < 0.f) ? 0.f : applied[k].y;
-    }
-  }
-  if (a.effort >= 0.f) {  // Joint::SetForce clamp (cube.sdf:438)
-#pragma unroll
-    for (int k = 0; k < NP; ++k) applied[k] = max2(min2(applied[k], splat(a.effort)), splat(-a.effort));
-  }
+  setforce_limits<NP>(a, qd, applied);
 
-  if (a.dbg && live) {  // `pid` topic, cable 0 only (PLG.cpp:223-227; Pid.cpp:139-142,158-168)
-    float* d = a.dbg + (size_t)r * 9;
-    if (dbg_wrote) {
-      d[0] = dbg_p;
-      d[1] = dbg_i;
-      d[2] = dbg_d;
-      d[3] = desired[0].x;
-    }
-    d[4] = applied[0].x;
-  }
+  if (a.dbg && live) write_pid_topic(a.dbg + (size_t)r * 9, dbg_wrote, dbg_wrote, dbg_p, dbg_i, dbg_d, desired[0].x, applied[0].x);
   if (publish && live) {  // the rest of the observables
     store_slot(a.obs, st, 3, woff, make_float4(s.wz, fk_res, (float)fk_it, pack_flags(td_flag, travel_mask<N>(a, q))));
 #pragma unroll
@@ -718,10 +698,7 @@ CDPR_DEV void split_controller_wave(const StepArgs& a, float* geo, float gval, u
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
   Platform s;
-  s.px = p0.x; s.py = p0.y; s.pz = p0.z; s.qx = p0.w;
-  s.qy = p1.x; s.qz = p1.y; s.qw = p1.z; s.vx = p1.w;
-  s.vy = p2.x; s.vz = p2.y; s.wx = p2.z; s.wy = p2.w;
-  s.wz = p3.x;
+  unpack_platform(p0, p1, p2, p3.x, s);
 
   // ---- IK on the state at t_k; the structure matrix stays alive for the world step (this wave runs no Newton stage)
   v2f len[NP], q[NP], qd[NP], jac[NP][6];
@@ -829,27 +806,8 @@ CDPR_DEV void split_controller_wave(const StepArgs& a, float* geo, float gval, u
   for (int k = 0; k < NP; ++k) applied[k] = x_tension[k * 64 + lane];
   const float fkx = x_est[0 * 64 + lane], fky = x_est[1 * 64 + lane], fkz = x_est[2 * 64 + lane], fk_res = x_est[3 * 64 + lane],
               fk_it = x_est[4 * 64 + lane], td_flag = x_est[5 * 64 + lane];
-  if (a.vel_limit > 0.f) {  // Joint::SetForce velocity truncation [EXT]
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      applied[k].x = (qd[k].x > a.vel_limit && applied[k].x > 0.f) || (qd[k].x < -a.vel_limit && applied[k].x < 0.f) ? 0.f : applied[k].x;
-      applied[k].y = (qd[k].y > a.vel_limit && applied[k].y > 0.f) || (qd[k].y < -a.vel_limit && applied[k].y < 0.f) ? 0.f : applied[k].y;
-    }
-  }
-  if (a.effort >= 0.f) {  // Joint::SetForce clamp (cube.sdf:438)
-#pragma unroll
-    for (int k = 0; k < NP; ++k) applied[k] = max2(min2(applied[k], splat(a.effort)), splat(-a.effort));
-  }
-  if (!STEADY && a.dbg && live) {  // `pid` topic, cable 0 only (PLG.cpp:223-227; Pid.cpp:139-142,158-168)
-    float* d = a.dbg + (size_t)r * 9;
-    if (dbg_wrote) {
-      d[0] = dbg_p;
-      d[1] = dbg_i;
-      d[2] = dbg_d;
-      d[3] = desired[0].x;
-    }
-    d[4] = applied[0].x;
-  }
+  setforce_limits<NP>(a, qd, applied);
+  if (!STEADY && a.dbg && live) write_pid_topic(a.dbg + (size_t)r * 9, dbg_wrote, dbg_wrote, dbg_p, dbg_i, dbg_d, desired[0].x, applied[0].x);
   if (publish && live) {
     store_slot(a.obs, st, 3, woff, make_float4(s.wz, fk_res, fk_it, (!STEADY && a.travel_on) ? pack_flags((int)td_flag, travel_mask<N>(a, q)) : td_flag));
 #pragma unroll

@@ -77,42 +77,18 @@ __global__ __launch_bounds__(64) void cdpr_solver_kernel(const SolveArgs a) {
     }
   } else if (OP == kSolveFk) {
     // Newton-Raphson FK ([NEW] SURVEY 8(a) row 14): pose7 is the seed, lengths the measurement
-    v2f meas[NP], elen[NP], unused[NP];
+    v2f meas[NP];
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
       meas[k].x = a.lengths[(size_t)r * N + 2 * k];
       meas[k].y = (2 * k + 1 < N) ? a.lengths[(size_t)r * N + 2 * k + 1] : 0.f;
     }
-    bool active = true;
+    float fk_res = 0.f;
     int it_done = 0;
-    for (int it = 0; it < a.fk_iters; ++it) {
-      ik_pairs<N, false>(lds, px, py, pz, qx, qy, qz, qw, elen, jac, unused);
-      v2f res[NP];
-      v2f rm = splat(0.f);
-#pragma unroll
-      for (int k = 0; k < NP; ++k) {
-        res[k] = meas[k] - elen[k];
-        rm = max2(rm, abs2(res[k]));
-      }
-      active = active && !(fmaxf(rm.x, rm.y) < a.fk_tol);
-      float g[6];
-      jt_times<NP>(jac, res, g);
-      normal_solve<NP>(jac, a.fk_lambda, g);
-      if (active) {
-        px += g[0];
-        py += g[1];
-        pz += g[2];
-        quat_apply_rotvec(qx, qy, qz, qw, g[3], g[4], g[5]);
-        ++it_done;
-      }
-    }
-    ik_pairs<N, false>(lds, px, py, pz, qx, qy, qz, qw, elen, jac, unused);
-    v2f rm = splat(0.f);
-#pragma unroll
-    for (int k = 0; k < NP; ++k) rm = max2(rm, abs2(meas[k] - elen[k]));
+    newton_fk<N>(a.fk_iters, a.fk_lambda, a.fk_tol, lds, meas, px, py, pz, qx, qy, qz, qw, jac, fk_res, it_done);
     float* o = a.pose_out + (size_t)r * 7;
     o[0] = px; o[1] = py; o[2] = pz; o[3] = qx; o[4] = qy; o[5] = qz; o[6] = qw;
-    if (a.residual) a.residual[r] = fmaxf(rm.x, rm.y);
+    if (a.residual) a.residual[r] = fk_res;
     if (a.iters) a.iters[r] = it_done;
   } else {
     // tension distribution for an explicit wrench ([NEW] SURVEY 8(a) row 15):

@@ -863,6 +863,14 @@ CDPR_DEV StepArgs block_args(const StepArgs& a_in) {
   }
 }
 
+}  // namespace cdpr
+
+// Stages of a world step on the helpers above that are defined once and shared by the kernel families (which calls which:
+// the header's own top).
+#include "cdpr_step_stages.hpp"
+
+namespace cdpr {
+
 // LOWREG = true (one-step kernel, large batches): fit two waves per SIMD (<= 256 registers) by NOT keeping what can be
 // recomputed: the cable constants are re-read from LDS in every Newton iteration instead of being hoisted into 48
 // registers, and the true structure matrix is rebuilt after the Newton stage instead of living through it.
@@ -950,10 +958,7 @@ __global__ __launch_bounds__(64, LOWREG ? 2 : CDPR_LPR_WAVES) void cdpr_step_ker
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
   Platform s;
-  s.px = p0.x; s.py = p0.y; s.pz = p0.z; s.qx = p0.w;
-  s.qy = p1.x; s.qz = p1.y; s.qw = p1.z; s.vx = p1.w;
-  s.vy = p2.x; s.vz = p2.y; s.wx = p2.z; s.wy = p2.w;
-  s.wz = p3.x;
+  unpack_platform(p0, p1, p2, p3.x, s);
   float fkx = p3.y, fky = p3.z, fkz = p3.w, fkqx = p4.x, fkqy = p4.y, fkqz = p4.z, fkqw = p4.w;
 
   // controller records as cable pairs: ring of the last 10 errors, integral
@@ -1260,16 +1265,7 @@ __global__ __launch_bounds__(64, LOWREG ? 2 : CDPR_LPR_WAVES) void cdpr_step_ker
       for (int k = 0; k < NP; ++k) applied[k] = max2(min2(applied[k], splat(a.effort)), splat(-a.effort));
     }
 
-    if (!ROLLOUT && a.dbg && live) {  // `pid` topic, cable 0 only (PLG.cpp:223-227; Pid.cpp:139-142,158-168)
-      float* d = a.dbg + (size_t)r * 9;
-      if (dbg_wrote) {
-        d[0] = dbg_p;
-        d[1] = dbg_i;
-        d[2] = dbg_d;
-        d[3] = desired[0].x;
-      }
-      d[4] = applied[0].x;
-    }
+    if (!ROLLOUT && a.dbg && live) write_pid_topic(a.dbg + (size_t)r * 9, dbg_wrote, dbg_wrote, dbg_p, dbg_i, dbg_d, desired[0].x, applied[0].x);
 
     CDPR_STAMP(5);
     // ---- observables of step t_k (PLG.cpp:236-242, 248-280)

@@ -108,10 +108,7 @@ __global__ __launch_bounds__(64, 2) void cdpr_step_kernel_pair(const StepArgs a)
   const float* mylds = lds + par * (NPL * kGeomFloatsPerPair);
 
   Platform s;
-  s.px = p0.x; s.py = p0.y; s.pz = p0.z; s.qx = p0.w;
-  s.qy = p1.x; s.qz = p1.y; s.qw = p1.z; s.vx = p1.w;
-  s.vy = p2.x; s.vz = p2.y; s.wx = p2.z; s.wy = p2.w;
-  s.wz = p3.x;
+  unpack_platform(p0, p1, p2, p3.x, s);
   float fkx = p3.y, fky = p3.z, fkz = p3.w, fkqx = p4.x, fkqy = p4.y, fkqz = p4.z, fkqw = p4.w;
 
   v2f win[NPL][kWin], ierr[NPL];
@@ -143,12 +140,7 @@ __global__ __launch_bounds__(64, 2) void cdpr_step_kernel_pair(const StepArgs a)
     // ---- IK rows of this lane's cables on the state at t_k
     v2f len[NPL], jac[NPL][6], l0[NPL], q[NPL], qd[NPL];
     ik_rows<NPL, false, true>(mylds, s.px, s.py, s.pz, s.qx, s.qy, s.qz, s.qw, len, jac, l0);
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) {
-      q[k] = l0[k] - len[k];
-      qd[k] = -fma2(s.wz, jac[k][5], fma2(s.wy, jac[k][4], fma2(s.wx, jac[k][3],
-                    fma2(s.vz, jac[k][2], fma2(s.vy, jac[k][1], splat(s.vx) * jac[k][0])))));
-    }
+    joint_coords<NPL>(s, len, l0, jac, q, qd);
 
     CDPR_STAMP(2);
     // ---- per-cable force (PLG.cpp:222-228 -> JFC.cpp:59-96 -> Pid.cpp:122-191)
@@ -303,28 +295,9 @@ __global__ __launch_bounds__(64, 2) void cdpr_step_kernel_pair(const StepArgs a)
 #pragma unroll
       for (int k = 0; k < NPL; ++k) applied[k] = f[k];
     }
-    if (a.vel_limit > 0.f) {  // Joint::SetForce velocity truncation [EXT]: no pushing a runaway joint further out
-#pragma unroll
-      for (int k = 0; k < NPL; ++k) {
-        applied[k].x = (qd[k].x > a.vel_limit && applied[k].x > 0.f) || (qd[k].x < -a.vel_limit && applied[k].x < 0.f) ? 0.f : applied[k].x;
-        applied[k].y = (qd[k].y > a.vel_limit && applied[k].y > 0.f) || (qd[k].y < -a.vel_limit && applied[k].y < 0.f) ? 0.f : applied[k].y;
-      }
-    }
-    if (a.effort >= 0.f) {
-#pragma unroll
-      for (int k = 0; k < NPL; ++k) applied[k] = max2(min2(applied[k], splat(a.effort)), splat(-a.effort));
-    }
+    setforce_limits<NPL>(a, qd, applied);
 
-    if (a.dbg && live && par == 0u) {  // `pid` topic, cable 0 only
-      float* d = a.dbg + (size_t)r * 9;
-      if (dbg_wrote) {
-        d[0] = dbg_p;
-        d[1] = dbg_i;
-        d[2] = dbg_d;
-        d[3] = desired[0].x;
-      }
-      d[4] = applied[0].x;
-    }
+    if (a.dbg && live && par == 0u) write_pid_topic(a.dbg + (size_t)r * 9, dbg_wrote, dbg_wrote, dbg_p, dbg_i, dbg_d, desired[0].x, applied[0].x);
 
     CDPR_STAMP(5);
     // ---- observables of step t_k: lane 0 writes the platform rows, each lane its own joint group
@@ -572,12 +545,7 @@ __global__ __launch_bounds__(64, 2) void cdpr_pair_stream_kernel(const StepArgs 
     // ---- IK rows of this lane's cables on the state at t_k
     v2f len[NPL], jac[NPL][6], l0[NPL], q[NPL], qd[NPL];
     ik_rows<NPL, false, true>(mylds, s.px, s.py, s.pz, s.qx, s.qy, s.qz, s.qw, len, jac, l0);
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) {
-      q[k] = l0[k] - len[k];
-      qd[k] = -fma2(s.wz, jac[k][5], fma2(s.wy, jac[k][4], fma2(s.wx, jac[k][3],
-                    fma2(s.vz, jac[k][2], fma2(s.vy, jac[k][1], splat(s.vx) * jac[k][0])))));
-    }
+    joint_coords<NPL>(s, len, l0, jac, q, qd);
     // ---- per-cable force (PLG.cpp:222-228 -> JFC.cpp:59-96 -> Pid.cpp:122-191), windows full
     v2f f[NPL];
 #pragma unroll
