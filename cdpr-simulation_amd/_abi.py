@@ -5,7 +5,7 @@ loader and the function prototypes are in `_native.py`.
 """
 import ctypes as C
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 MAX_CABLES = 12
 MAX_D_BUFFER = 32
 MAX_D_DEGREE = 4
@@ -23,6 +23,10 @@ ERR_NOMEM = -4
 STAGE_FK = 0x1
 STAGE_TD = 0x2
 STAGE_PID_DEBUG = 0x4
+
+# cdpr_done_rule_t.enable / the reason word of cdpr_evaluate_done
+DONE_NONFINITE, DONE_WORKSPACE, DONE_TILT, DONE_SPEED, DONE_RATE, DONE_FK_RESIDUAL, DONE_INFEASIBLE, DONE_TRAVEL, DONE_TIMEOUT = (1 << k for k in range(9))
+DONE_COUNTS = 16  # counts[0] = robots done, counts[1 + k] = robots with reason bit k
 
 PLAN_FIRST_WORLD_STEP, PLAN_SCHEDULED, PLAN_ROLLOUT, PLAN_NOT_STEADY = 1, 2, 4, 8  # cdpr_plan_kernel flags
 MAP_AUTO = 0
@@ -89,4 +93,19 @@ class ConfigStruct(C.Structure):
         ("travel_upper", C.c_double),
         ("travel_stop", C.c_uint32),
         ("reserved3_", C.c_uint32),
+    ]
+
+
+class DoneRuleStruct(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("enable", C.c_uint32),
+        ("pos_lo", C.c_float * 3),
+        ("pos_hi", C.c_float * 3),
+        ("min_up", C.c_float),
+        ("max_speed", C.c_float),
+        ("max_rate", C.c_float),
+        ("max_fk_residual", C.c_float),
+        ("max_steps", C.c_uint32),
+        ("reserved_", C.c_uint32),
     ]

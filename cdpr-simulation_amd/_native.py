@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("CDPR_LIB", "libcdpr_hip.so"))  # 
 EXPORTS = [
     "cdpr_abi_version", "cdpr_config_size", "cdpr_device_count", "cdpr_device_pci_bus_id", "cdpr_bytes_per_state_step", "cdpr_derivative_weights",
     "cdpr_create", "cdpr_destroy", "cdpr_reset", "cdpr_last_error", "cdpr_set_platform_state", "cdpr_reset_robots", "cdpr_reset_robots_device",
+    "cdpr_done_rule_size", "cdpr_evaluate_done_device", "cdpr_evaluate_done", "cdpr_reset_done_device", "cdpr_get_episode_start",
     "cdpr_set_velocity_command", "cdpr_set_position_command", "cdpr_set_velocity_command_device",
     "cdpr_set_position_command_device", "cdpr_bind_velocity_command_device", "cdpr_bind_position_command_device",
     "cdpr_set_velocity_command_masked", "cdpr_set_position_command_masked", "cdpr_set_force_command", "cdpr_set_force_command_device",
@@ -63,6 +64,12 @@ def lib():
     L.cdpr_set_platform_state.argtypes = [H, fp, fp]
     L.cdpr_reset_robots.argtypes = [H, C.POINTER(C.c_uint8), fp, fp]
     L.cdpr_reset_robots_device.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]
+    rulep, u8p, u32p = C.POINTER(_abi.DoneRuleStruct), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    L.cdpr_done_rule_size.restype = C.c_size_t
+    L.cdpr_evaluate_done_device.argtypes = [H, rulep, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cdpr_evaluate_done.argtypes = [H, rulep, u8p, u32p, u32p]
+    L.cdpr_reset_done_device.argtypes = [H, rulep, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cdpr_get_episode_start.argtypes = [H, u32p]
     for name in ("cdpr_set_velocity_command", "cdpr_set_position_command", "cdpr_set_force_command"):
         getattr(L, name).argtypes = [H, fp, C.c_size_t]
     for name in ("cdpr_set_velocity_command_device", "cdpr_set_position_command_device", "cdpr_bind_velocity_command_device",
@@ -113,5 +120,7 @@ def lib():
         raise ImportError("libcdpr_hip.so ABI version mismatch")
     if L.cdpr_config_size() != C.sizeof(_abi.ConfigStruct):
         raise ImportError("cdpr_config_t layout mismatch between include/cdpr.h and _abi.py")
+    if L.cdpr_done_rule_size() != C.sizeof(_abi.DoneRuleStruct):
+        raise ImportError("cdpr_done_rule_t layout mismatch between include/cdpr.h and _abi.py")
     _lib = L
     return L

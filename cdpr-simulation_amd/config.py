@@ -8,6 +8,7 @@ dictionary dumped from the ROS parameter server loads unchanged.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from dataclasses import dataclass, field, replace
 from typing import Dict, List, Mapping, Sequence
@@ -302,6 +303,36 @@ class Config:
         s.fk_tolerance = float(self.fkTolerance)
         s.td_f_min = float(m.f_min if self.tdFMin is None else self.tdFMin)
         s.td_f_max = float(m.f_max if self.tdFMax is None else self.tdFMax)
+        return s
+
+
+@dataclass
+class DoneRule:
+    """Which robots a loop should put back (cdpr_done_rule_t): Engine.evaluate_done / evaluate_done_device / reset_done_device.
+    `enable` holds the _abi.DONE_* bits the rule may raise; the defaults enable nothing.  A robot is done when any enabled condition
+    holds: a non-finite pose or twist value (NONFINITE), a position outside [pos_lo, pos_hi] on some axis (WORKSPACE; on the bound is
+    inside), R33 = 1 - 2 (qx^2 + qy^2) / (q . q) below min_up (TILT), |v| above max_speed (SPEED), |w| above max_rate (RATE), an FK
+    residual above max_fk_residual (FK_RESIDUAL, needs STAGE_FK), the tension-distribution flag (INFEASIBLE, needs STAGE_TD), any
+    travel-limit bit (TRAVEL), or max_steps world steps since the robot's last model reset (TIMEOUT).  The thresholds are float32."""
+
+    enable: int = 0
+    pos_lo: Sequence[float] = (0.0, 0.0, 0.0)
+    pos_hi: Sequence[float] = (0.0, 0.0, 0.0)
+    min_up: float = 0.0
+    max_speed: float = 0.0
+    max_rate: float = 0.0
+    max_fk_residual: float = 0.0
+    max_steps: int = 0
+
+    def to_struct(self) -> _abi.DoneRuleStruct:
+        s = _abi.DoneRuleStruct()
+        s.struct_size = C.sizeof(_abi.DoneRuleStruct)
+        s.enable = int(self.enable)
+        for k in range(3):
+            s.pos_lo[k] = float(self.pos_lo[k])
+            s.pos_hi[k] = float(self.pos_hi[k])
+        s.min_up, s.max_speed, s.max_rate, s.max_fk_residual = float(self.min_up), float(self.max_speed), float(self.max_rate), float(self.max_fk_residual)
+        s.max_steps = int(self.max_steps)
         return s
 
 

@@ -194,6 +194,7 @@ std::vector<float4> home_state(const cdpr_engine* h, uint32_t rows) {
 }
 
 int upload_home(cdpr_engine* h) {
+  HIP_TRY(h, hipMemsetAsync(h->d_episode, 0, (size_t)h->stride * sizeof(uint32_t), h->stream));  // every episode starts at world step 0
   if (h->plan.fp64) return upload_home64(h);
   std::vector<float4> s = home_state(h, h->stride);
   HIP_TRY(h, hipMemcpyAsync(h->d_state, s.data(), s.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream));
@@ -993,6 +994,7 @@ static int build_handle(cdpr_engine* h) {
     CREATE_TRY(h, "hipMalloc(mode)", h->d_mode.alloc(h->batch));
     for (CmdChannel& c : h->cmd) CREATE_TRY(h, "hipMalloc(mask)", c.d_mask.alloc(h->batch));
   }
+  CREATE_TRY(h, "hipMalloc(episode)", h->d_episode.alloc((size_t)h->stride * sizeof(uint32_t)));
   if (h->dbg && !h->plan.fp64) CREATE_TRY(h, "hipMalloc(dbg)", h->d_dbg.alloc((size_t)h->batch * CDPR_PID_DEBUG_AXES * sizeof(float)));
   if (upload_home(h) != CDPR_OK || warm_first_launch(h) != CDPR_OK) return CDPR_ERR_DEVICE;
   return CDPR_OK;

@@ -3,7 +3,7 @@
 // it), the error macros and the helpers one unit defines and another calls.  Units: cdpr_engine.hip (create / destroy, the general
 // path's set-up, commands, the fp32 launch chains, read-out), cdpr_engine_f64.hip (precision = 64: set-up, launch chain, read-out),
 // cdpr_engine_rollout.hip (cdpr_rollout_velocity*), cdpr_engine_solvers.hip (cdpr_solve_ik / fk / td), cdpr_engine_reset.hip
-// (cdpr_reset_robots*).  Not installed, not part of the C-ABI (include/cdpr.h is).
+// (cdpr_reset_robots*), cdpr_engine_done.hip (cdpr_evaluate_done*, cdpr_reset_done_device, cdpr_get_episode_start).  Not installed, not part of the C-ABI (include/cdpr.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -221,6 +221,11 @@ struct cdpr_engine {
   hipEvent_t reset_ev[2] = {nullptr, nullptr};  // the copy out of that staging block has completed
   bool reset_ev_set[2] = {false, false};
   int reset_idx = 0;
+  // episode clock: uint32[stride], the world step (low word) of every robot's last model reset; zero after create / cdpr_reset and
+  // on uniform handles.  d_done: scratch of cdpr_evaluate_done's host form and the mask of cdpr_reset_done_device
+  // ([uint8 mask[B], padded to 16 B | uint32 reason[B] | uint32 counts[CDPR_DONE_COUNTS]], sized once)
+  DevBuf<uint32_t> d_episode;
+  DevBuf<char> d_done;
   // cdpr_config_t.precision = 64 (plan.fp64): the step in double (cdpr_step_kernel_f64.hpp); its own state, observables, tables
   DevBuf<double> d_state64, d_obs64;
   DevBuf<double> d_geom64;       // [n][7]
@@ -339,6 +344,8 @@ void copy_pid(const StepArgs& src, StepArgs& dst);
 void copy_pid_alt(const StepArgs& src, PidSet& dst);
 GenCtl general_ctl(const cdpr_engine* h);
 int fetch_slots(cdpr_engine* h, const float4* dsrc, int nslots, std::vector<float4>& host);
+// cdpr_engine_reset.hip
+int launch_reset(cdpr_engine* h, const uint8_t* d_mask, const float* d_pose, const float* d_twist);
 // cdpr_engine_f64.hip
 int build_f64(cdpr_engine* h);  // cdpr_create's part of a precision = 64 handle
 size_t state64_rows(const cdpr_engine* h);

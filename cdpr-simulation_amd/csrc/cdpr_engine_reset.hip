@@ -20,10 +20,12 @@ static int reset_checks(cdpr_engine* h, const void* mask, const char* what) {
 
 // Queue the reset behind every update queued so far.  d_mask uint8[B], d_pose float[B][7] or null (home), d_twist float[B][6] or null
 // (zero): device buffers.  h->mode, h->pid_calls (not used on per-robot handles), the world step, the publish clock, the status word
-// and every pending command stay as they are.
-static int launch_reset(cdpr_engine* h, const uint8_t* d_mask, const float* d_pose, const float* d_twist) {
+// and every pending command stay as they are; the reset robots' episode clock takes the world step of the call.  (Also the second
+// launch of cdpr_reset_done_device, cdpr_engine_done.hip.)
+int launch_reset(cdpr_engine* h, const uint8_t* d_mask, const float* d_pose, const float* d_twist) {
   ResetWhere who{};
   who.mask = d_mask, who.pose = d_pose, who.twist = d_twist, who.batch = h->batch;
+  who.episode_start = h->d_episode, who.step = (uint32_t)h->step;
   for (int c = 0; c < 7; ++c) who.home[c] = (float)h->cfg.home_pose[c];
   const dim3 grid((h->batch + 255u) / 256u), block(256);
   if (h->plan.fp64) {

@@ -1,7 +1,7 @@
 // cdpr_reset.hpp — model reset of chosen robots of a per-robot handle (cdpr_reset_robots[_device]): the robots of the mask go back
 // to what cdpr_create / cdpr_reset leave for every robot - JointForceCalculator::reset() (JFC.h:69-73) plus the state Load leaves
 // (PLG.cpp:153-157: Position mode, target 0) - at a pose and twist of the caller's; the world clock, the other robots and every
-// pending command stay as they are.  One kernel per record layout: the register-resident per-robot records (cdpr_step_kernel.hpp),
+// pending command stay as they are; the robot's episode clock restarts (one dword store).  One kernel per record layout: the register-resident per-robot records (cdpr_step_kernel.hpp),
 // the general path's record buffer with its hot rows (cdpr_general_step.hpp), the precision = 64 rows (cdpr_step_kernel_f64.hpp).
 //
 // As the latch kernels (cdpr_latch.hpp): one thread per robot, 256 per block, the mask byte read once, a robot outside the mask
@@ -20,6 +20,8 @@ struct ResetWhere {
   const float* twist;   // float[B][6], or nullptr = zero
   float home[7];        // cdpr_config_t.home_pose
   uint32_t batch;
+  uint32_t* episode_start;  // uint32[B]: the world step of the robot's last model reset (cdpr_get_episode_start, CDPR_DONE_TIMEOUT)
+  uint32_t step;        // low word of cdpr_step_count at the call
 };
 
 // the robot's pose and twist: its rows of the caller's buffers, or home and zero
@@ -77,6 +79,7 @@ static __global__ __launch_bounds__(256) void cdpr_reset_fast_kernel(const Reset
   for (uint32_t g = 0; g < a.hot_rows; ++g) a.hot[(size_t)g * a.plat.stride + r] = make_float4(0.f, 0.f, 0.f, 0.f);
   a.meta[r] = (uint8_t)kMetaPosition;
   for (uint32_t i = 0; i < a.n; ++i) a.target[(size_t)r * a.n + i] = 0.f;
+  a.who.episode_start[r] = a.who.step;
 }
 
 // General path: the robot's column of the whole record buffer - mLastPosition slots, both Pids' slots (region A) and rows (region
@@ -110,6 +113,7 @@ static __global__ __launch_bounds__(256) void cdpr_reset_gen_kernel(const ResetG
 #pragma unroll
   for (int k = 0; k < 3; ++k)
     for (uint32_t i = 0; i < a.n; ++i) a.latched[k][(size_t)r * a.n + i] = 0.f;
+  a.who.episode_start[r] = a.who.step;
 }
 
 // precision = 64: the double rows of pose, twist and FK estimate (a float pose becomes a double exactly); the integral rows
@@ -162,6 +166,7 @@ static __global__ __launch_bounds__(256) void cdpr_reset_f64_kernel(const ResetF
   for (uint32_t i = 0; i < a.n; ++i) a.target[(size_t)r * a.n + i] = 0.f;
   if (a.dbg)
     for (int c = 0; c < CDPR_PID_DEBUG_AXES; ++c) a.dbg[(size_t)r * CDPR_PID_DEBUG_AXES + c] = 0.0;
+  a.who.episode_start[r] = a.who.step;
 }
 
 }  // namespace cdpr

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _abi
 from ._native import lib
-from .config import Config
+from .config import Config, DoneRule
 
 
 class CdprError(RuntimeError):
@@ -107,6 +107,43 @@ class Engine:
         synchronised, the buffers must stay valid until the stream has passed the reset (cdpr_reset_robots_device)."""
         self._check(lib().cdpr_reset_robots_device(self._h, C.c_void_p(d_mask) if d_mask else None, C.c_void_p(d_pose7) if d_pose7 else None,
                                                    C.c_void_p(d_twist6) if d_twist6 else None))
+
+    # -- done rules: who should be put back, decided on the device
+    @staticmethod
+    def _rule(rule):
+        """a DoneRule, or its struct built once (DoneRule.to_struct()) by a loop that calls every step"""
+        return rule if isinstance(rule, _abi.DoneRuleStruct) else rule.to_struct()
+
+    def evaluate_done(self, rule: DoneRule) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The verdict of `rule` on the state the engine holds now (cdpr_evaluate_done): mask uint8[B] (0 or 1), reason uint32[B] (the
+        rule's enabled _abi.DONE_* bits that hold for the robot), counts uint32[_abi.DONE_COUNTS] (counts[0] robots done, counts[1 + k]
+        robots with reason bit k).  A pure function of raw_state, fk_state (residual), td_state (infeasible), limit_state,
+        episode_start and step_count.  Waits for the stream once."""
+        mask, reason, counts = np.empty(self.B, dtype=np.uint8), np.empty(self.B, dtype=np.uint32), np.empty(_abi.DONE_COUNTS, dtype=np.uint32)
+        s = self._rule(rule)
+        u32 = C.POINTER(C.c_uint32)
+        self._check(lib().cdpr_evaluate_done(self._h, C.byref(s), mask.ctypes.data_as(C.POINTER(C.c_uint8)), reason.ctypes.data_as(u32), counts.ctypes.data_as(u32)))
+        return mask, reason, counts
+
+    def evaluate_done_device(self, rule: DoneRule, d_mask: int, d_reason: int = 0, d_counts: int = 0) -> None:
+        """The same into device buffers (uint8[B], uint32[B], uint32[_abi.DONE_COUNTS]; 0 = not wanted): queued on the engine's stream,
+        nothing copied back or waited for (cdpr_evaluate_done_device).  d_mask is what reset_robots_device takes."""
+        s = self._rule(rule)
+        self._check(lib().cdpr_evaluate_done_device(self._h, C.byref(s), C.c_void_p(d_mask) if d_mask else None, C.c_void_p(d_reason) if d_reason else None,
+                                                    C.c_void_p(d_counts) if d_counts else None))
+
+    def reset_done_device(self, rule: DoneRule, d_pose7: int = 0, d_twist6: int = 0, d_counts: int = 0) -> None:
+        """Evaluate `rule` and reset the robots it finds done, with no host wait in between (cdpr_reset_done_device): d_pose7 / d_twist6
+        as for reset_robots_device, d_counts receives the verdict's counts.  Needs Config.perRobotCommands."""
+        s = self._rule(rule)
+        self._check(lib().cdpr_reset_done_device(self._h, C.byref(s), C.c_void_p(d_pose7) if d_pose7 else None, C.c_void_p(d_twist6) if d_twist6 else None,
+                                                 C.c_void_p(d_counts) if d_counts else None))
+
+    def episode_start(self) -> np.ndarray:
+        """uint32[B]: the world step (low 32 bits of step_count) of every robot's last model reset; 0 after create and reset()."""
+        start = np.empty(self.B, dtype=np.uint32)
+        self._check(lib().cdpr_get_episode_start(self._h, start.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return start
 
     def _command(self, fn, fn_masked, axes, mask) -> int:
         a = np.ascontiguousarray(axes, dtype=np.float32).ravel()

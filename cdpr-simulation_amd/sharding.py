@@ -72,6 +72,28 @@ class ShardedEngine:
         for e, (lo, hi), p, t in zip(self.engines, self.spans, ps, ts):
             e.reset_robots(m[lo:hi], p, t)
 
+    def evaluate_done(self, rule):
+        """Engine.evaluate_done over the shards: masks and reasons concatenated in shard_range order, counts summed."""
+        import numpy as np
+
+        parts = [e.evaluate_done(rule) for e in self.engines]
+        return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]), np.sum([p[2] for p in parts], axis=0, dtype=np.uint32)
+
+    def reset_done_device(self, rule, d_pose7=None, d_twist6=None, d_counts=None):
+        """Engine.reset_done_device on every shard.  The device buffers belong to the shards' own GPUs: one pointer per shard (a list in
+        shard order, rows [0, hi - lo) of that shard's robots), or None = home pose / zero twist / no counts on every shard."""
+        k = len(self.engines)
+        ps, ts, cs = ([0] * k if x is None else list(x) for x in (d_pose7, d_twist6, d_counts))
+        if not len(ps) == len(ts) == len(cs) == k:
+            raise ValueError("reset_done_device: one device pointer per shard")
+        for e, p, t, c in zip(self.engines, ps, ts, cs):
+            e.reset_done_device(rule, p, t, c)
+
+    def episode_start(self):
+        import numpy as np
+
+        return np.concatenate([e.episode_start() for e in self.engines])
+
     def _command(self, name, axes, mask):
         import numpy as np
 

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define CDPR_ABI_VERSION 7u   /* 7 = 6 + cdpr_reset_robots, cdpr_reset_robots_device; 6 = 5 + cdpr_plan_kernel, cdpr_kernel_name, CDPR_MAX_CABLES 8 -> 12 (cdpr_config_t's anchor arrays grow); 5 = 4 + cdpr_update_scheduled_kind, cdpr_device_pci_bus_id, cdpr_decode_observables_f64 */
+#define CDPR_ABI_VERSION 8u   /* 8 = 7 + cdpr_done_rule_t, cdpr_evaluate_done, cdpr_evaluate_done_device, cdpr_reset_done_device, cdpr_get_episode_start, cdpr_done_rule_size; 7 = 6 + cdpr_reset_robots, cdpr_reset_robots_device; 6 = 5 + cdpr_plan_kernel, cdpr_kernel_name, CDPR_MAX_CABLES 8 -> 12 (cdpr_config_t's anchor arrays grow); 5 = 4 + cdpr_update_scheduled_kind, cdpr_device_pci_bus_id, cdpr_decode_observables_f64 */
 #define CDPR_MAX_CABLES 12u         /* PLG.h:20 fixes 4 (kCableCount); cube.yaml:21-29 is a free-length `points` list: the engine takes 1..12
                                       (9..12: uniform-mode fp32 handles on the lane-per-robot kernels, FK and TD included; see cdpr_create) */
 #define CDPR_MAX_D_BUFFER 32u       /* Pid: mDbufferLength                      */
@@ -224,9 +224,63 @@ int cdpr_set_platform_state(cdpr_handle_t h, const float *pose7, const float *tw
  * keeps one mode and one Pid call count for the whole batch.  NULL handle or mask: CDPR_ERR_INVALID.
  * cdpr_reset_robots: host arrays, copied before the call returns; the work is queued, the stream is not waited for.
  * cdpr_reset_robots_device: device buffers (a loop that computes its "done" mask on the GPU), nothing copied or synchronised;
- * they must stay valid until the stream has passed the reset. */
+ * they must stay valid until the stream has passed the reset.
+ * Either form stamps the reset robots' episode clock with the world step of the call (cdpr_get_episode_start, below). */
 int cdpr_reset_robots(cdpr_handle_t h, const uint8_t *robot_mask, const float *pose7, const float *twist6);
 int cdpr_reset_robots_device(cdpr_handle_t h, const uint8_t *d_robot_mask, const float *d_pose7, const float *d_twist6);
+
+/* Done rules: which robots a loop should put back, decided on the device.  cdpr_reset_robots_device takes a "done" mask that lives
+ * on the GPU; these calls compute it there, from the state the handle already holds, so that a Monte-Carlo sweep, an RL-style
+ * environment batch or an MPC loop never brings the state to the host to find out who has diverged.
+ *
+ * The verdict is a pure function of what the getters return at that point of the stream: cdpr_get_raw_state[_f64] (pose and twist:
+ * the CURRENT state, not decimated by publish_period), cdpr_get_fk_state (residual), cdpr_get_td_state (infeasible),
+ * cdpr_get_limit_state, cdpr_get_episode_start and cdpr_step_count.  The residual and the two flags travel with the observables: they
+ * are those of the last PUBLISHED step, zero before the first publish and after a model reset.  That is the whole specification.
+ *   reason[b]  the OR of the rule's enabled CDPR_DONE_* bits whose condition holds for robot b; every comparison is an ordinary one
+ *              (false on NaN), only CDPR_DONE_NONFINITE reports a NaN.  On precision = 64 handles the rule's floats are promoted to
+ *              double and compared with the double rows (the residual as cdpr_get_fk_state rounds it: it has no double getter).
+ *   mask[b]    reason[b] != 0, written as exactly 0 or 1: what cdpr_reset_robots_device takes.
+ *   counts     uint32[CDPR_DONE_COUNTS]: counts[0] = robots done, counts[1 + k] = robots with reason bit k.  Zeroed on the stream in
+ *              front of the kernel: consecutive calls do not accumulate.
+ * Episode clock: every robot remembers the world step (low 32 bits of cdpr_step_count) of its last model reset - 0 after cdpr_create
+ * and cdpr_reset, the step count at the call after cdpr_reset_robots[_device] / cdpr_reset_done_device took it; uniform handles keep
+ * all zeros.  cdpr_get_episode_start reads it (uint32[B], waits for the stream).  CDPR_DONE_TIMEOUT compares
+ * (uint32_t)(step_count - start) >= max_steps, which survives the wrap of the low word.
+ * Any handle: uniform or per-robot commands, any kernel family, any cable count, both precisions (only platform and observable rows
+ * are read, never a controller record).  These are not step launches: cdpr_kernel_name keeps naming the last step's kernel.
+ * cdpr_evaluate_done_device: device buffers, stream-ordered after every update queued so far; nothing is copied back, nothing is
+ *   waited for, only rows [0, B) are written.  d_reason and d_counts may be NULL.
+ * cdpr_evaluate_done: host arrays through device scratch of the handle's own; one wait, then the copies.  Any output may be NULL.
+ * cdpr_reset_done_device: the verdict into a mask of the handle's own, then the launch of cdpr_reset_robots_device on that mask
+ *   (d_pose7 / d_twist6 as there: float[B][7] / float[B][6] or NULL = home_pose / zero), with no host wait in between.  Needs
+ *   per_robot_commands = 1, as the reset does.  d_counts may be NULL.
+ * Refusals: CDPR_ERR_INVALID for a NULL handle, a NULL rule, a NULL mask (device form) or struct_size != sizeof(cdpr_done_rule_t);
+ * CDPR_ERR_UNSUPPORTED for CDPR_DONE_FK_RESIDUAL without CDPR_STAGE_FK, CDPR_DONE_INFEASIBLE without CDPR_STAGE_TD, and for
+ * cdpr_reset_done_device on a uniform handle.  A refused call queues nothing. */
+#define CDPR_DONE_NONFINITE   0x001u  /* any of the 13 pose / twist values is not finite                                   */
+#define CDPR_DONE_WORKSPACE   0x002u  /* p[c] < pos_lo[c] or p[c] > pos_hi[c] on some axis (on the bound: inside)          */
+#define CDPR_DONE_TILT        0x004u  /* R33 < min_up,  R33 = 1 - 2 (qx^2 + qy^2) / (q . q)                                */
+#define CDPR_DONE_SPEED       0x008u  /* v . v > max_speed^2                                                               */
+#define CDPR_DONE_RATE        0x010u  /* w . w > max_rate^2                                                                */
+#define CDPR_DONE_FK_RESIDUAL 0x020u  /* fk residual > max_fk_residual              (needs CDPR_STAGE_FK)                  */
+#define CDPR_DONE_INFEASIBLE  0x040u  /* tension-distribution infeasible flag       (needs CDPR_STAGE_TD)                  */
+#define CDPR_DONE_TRAVEL      0x080u  /* any travel-limit bit                                                              */
+#define CDPR_DONE_TIMEOUT     0x100u  /* step_count - episode_start >= max_steps                                           */
+#define CDPR_DONE_COUNTS 16           /* counts[0] = robots done, counts[1 + k] = robots with reason bit k                 */
+
+typedef struct cdpr_done_rule {
+  uint32_t struct_size, enable;       /* sizeof(cdpr_done_rule_t); the CDPR_DONE_* bits this rule may raise */
+  float pos_lo[3], pos_hi[3];
+  float min_up, max_speed, max_rate, max_fk_residual;
+  uint32_t max_steps, reserved_;
+} cdpr_done_rule_t;
+
+size_t cdpr_done_rule_size(void);                    /* sizeof(cdpr_done_rule_t) as compiled */
+int cdpr_evaluate_done_device(cdpr_handle_t h, const cdpr_done_rule_t *rule, uint8_t *d_mask, uint32_t *d_reason, uint32_t *d_counts);
+int cdpr_evaluate_done(cdpr_handle_t h, const cdpr_done_rule_t *rule, uint8_t *mask, uint32_t *reason, uint32_t *counts);
+int cdpr_reset_done_device(cdpr_handle_t h, const cdpr_done_rule_t *rule, const float *d_pose7, const float *d_twist6, uint32_t *d_counts);
+int cdpr_get_episode_start(cdpr_handle_t h, uint32_t *start);   /* uint32[B] */
 
 /* Replaces cableVelocityCommandCallback / cablePositionCommandCallback
  * (PLG.cpp:67-83).  `count` = number of floats in `axes`: n*B (one Joy per
