@@ -10,7 +10,6 @@ namespace {
 thread_local std::string g_create_error;
 }  // namespace
 
-
 namespace cdpr_host {
 
 // ---------------------------------------------------------------------------------
@@ -153,27 +152,6 @@ std::vector<float> geom_pairs(const cdpr_config_t& c) {
   return g;
 }
 
-double sim_time(uint64_t step, double dt) {
-  // gazebo::common::Time keeps integer sec + nsec; Double() = sec + nsec * 1e-9 [EXT]
-  const int64_t dt_ns = (int64_t)std::llround(dt * 1e9);
-  const int64_t now_ns = (int64_t)step * dt_ns;
-  return (double)(now_ns / 1000000000LL) + (double)(now_ns % 1000000000LL) * 1e-9;
-}
-
-// Which of the next k world steps publish (bit j: world step h->step + j), PLG.cpp:236-242: strict '>' against the last
-// published stamp, which moves on with every step that does.
-uint64_t publish_mask(cdpr_engine* h, int k) {
-  uint64_t mask = 0;
-  for (int j = 0; j < k; ++j) {
-    const double now = sim_time(h->step + (uint64_t)j, h->cfg.dt);
-    if ((now - h->prev_publish) > h->cfg.publish_period) {
-      h->prev_publish = now;
-      mask |= (1ull << j);
-    }
-  }
-  return mask;
-}
-
 int set_device(cdpr_engine* h) {
   HIP_TRY(h, hipSetDevice(h->device));
   return CDPR_OK;
@@ -221,10 +199,7 @@ void free_all(cdpr_engine* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
-  for (auto& g : h->graphs) {
-    (void)hipGraphExecDestroy(g.exec);
-    (void)hipGraphDestroy(g.graph);
-  }
+  h->graphs.clear();
   for (CmdChannel& c : h->cmd)
     for (hipEvent_t ev : {c.stage_ev[0], c.stage_ev[1], c.free_ev})
       if (ev) (void)hipEventDestroy(ev);
@@ -304,69 +279,6 @@ int stage_command(cdpr_engine* h, int kind, const float* src, size_t count, bool
   return CDPR_OK;
 }
 
-// The Pid call counter only matters through calls != 0 and calls >= nbuf (<= 11 on the fast path): it saturates.  The
-// ring position does not come from it but from the world step (StepArgs::ring_slot).
-// ... of a ring of w errors: the first sample of a handle that runs without a Pid reset since Load is taken at world step 2
-
-// Weights of the ring position a launch starts at, copied into its arguments (see StepArgs::wrow).
-void set_weight_row(const cdpr_engine* h, StepArgs& a) {
-  const int slot = a.ring_slot;
-  // (per-robot handles: both Pids share one window, so the velocity Pid's table serves every lane)
-  memcpy(a.wrow, &h->wtab_host[(h->plan.per_robot || h->mode == kModeVelocity) ? 0 : 1][slot * (kWin + 2)], sizeof a.wrow);
-}
-
-// The kernel a launch uses: the routing is planned_kernel's (cdpr_select.hpp: a pure function of the handle's plan and the
-// launch's shape, the same one cdpr_plan_kernel answers from without a GPU); here its answer becomes a function pointer.
-LaunchShape launch_shape(const cdpr_engine* h, int k, bool steady) {
-  LaunchShape s;
-  s.steps = k;
-  s.first_world = h->step == 0;
-  s.scheduled = h->sched_refresh != 0;
-  s.steady = steady;
-  return s;
-}
-StepKernel step_kernel_of(const cdpr_engine* h, const PlannedKernel& pk) {
-  const uint32_t n = h->n;
-  switch (pk.id) {
-    case KernelId::StepSingle: return pick_step_kernel(true, n, h->plan.fk, h->plan.td);
-    case KernelId::StepMulti: return pick_step_kernel(false, n, h->plan.fk, h->plan.td);
-    case KernelId::Lowreg: return pick_lowreg_kernel(n, h->plan.td);
-    case KernelId::OnestepPersist: return pick_onestep_persist_kernel(n, h->plan.fk, h->plan.td);
-    case KernelId::Split: return pick_split_kernel(n);
-    case KernelId::Onestep: return pick_onestep_kernel(n, h->plan.fk, h->plan.td);
-    case KernelId::PhysStep: return pick_phys_kernel(n, h->plan.fk, h->plan.td, kPhysStep);
-    case KernelId::Rollout: return pick_rollout_kernel(n, h->plan.fk, h->plan.td);
-    case KernelId::PhysRollout: return pick_phys_kernel(n, h->plan.fk, h->plan.td, kPhysRollout);
-    case KernelId::PrSingle: return pick_pr_kernel(true, false, false, n, h->plan.fk, h->plan.td);
-    case KernelId::PrLowreg: return pick_pr_kernel(true, false, true, n, h->plan.fk, h->plan.td);
-    case KernelId::PrSplit: return pick_pr_split_kernel(n);
-    case KernelId::PrMulti: return pick_pr_kernel(false, false, false, n, h->plan.fk, h->plan.td);
-    case KernelId::PrRollout: return pick_pr_kernel(false, true, false, n, h->plan.fk, h->plan.td);
-    case KernelId::PairSingle: return pick_pair_kernel(true, n, h->plan.fk, h->plan.td);
-    case KernelId::PairMulti: return pick_pair_kernel(false, n, h->plan.fk, h->plan.td);
-    case KernelId::PairStream: return pick_pair_stream_kernel(n, h->mode == kModeVelocity);
-    case KernelId::Cable: return pick_cable_kernel(n, h->plan.fk, h->plan.td);
-    default: return nullptr;  // (general path and precision = 64: their own launch functions)
-  }
-}
-StepKernel select_step_kernel(const cdpr_engine* h, int k, bool steady) { return step_kernel_of(h, planned_kernel(h->plan, launch_shape(h, k, steady))); }
-// May a launch of k > 1 world steps with the arguments `a` (flags, pid_calls, pointers set) run on cdpr_pair_stream_kernel?
-// That kernel has no branch for anything but the steady state of a plain handle (cdpr_step_kernel_pair.hpp): every
-// condition below is one the general several-steps kernel tests per step instead (LaunchShape::steady).  CDPR_PAIR_STREAM=0: never (A/B).
-bool pair_stream_steady(const cdpr_engine* h, const StepArgs& a) {
-  return h->step != 0 && h->mode != kModeForce && a.pid_calls >= a.nbuf && h->cfg.publish_period == 0.0 && !a.dbg && !a.travel_on &&
-         !(a.vel_limit > 0.f) && !a.unilateral && a.effort >= 0.f && a.clamp_cmd && !h->sched_ready;
-}
-// May a launch of the role-split kernel with the arguments `a` take the controller wave's steady-state instantiation
-// (split_controller_wave<N, false, true, VEL>, cdpr_onestep_kernel.hpp)?  It has no code for anything the generic one tests per launch
-// and these facts decide: a uniform handle in Velocity or Position mode, past world step 0, the derivative window full, every step
-// published, no `pid` topic, no travel flags.  CDPR_SPLIT_STEADY=0: never (A/B, tests).  Same bits either way (tested).
-bool split_steady_launch(const cdpr_engine* h, const PlannedKernel& pk, const StepArgs& a) {
-  return pk.id == KernelId::Split && h->split_steady && !h->plan.per_robot && h->step != 0 && h->mode != kModeForce && a.pid_calls != 0 &&
-         a.pid_calls >= a.nbuf && h->cfg.publish_period == 0.0 && !a.dbg && !a.travel_on;
-}
-uint32_t step_block_threads(const cdpr_engine* h, int k) { return planned_kernel(h->plan, launch_shape(h, k)).block; }
-
 // cdpr_create's part of a general-path handle: the layout of the controller records, the records, the two Pids' parameter table
 // and their FIR weights by ring head.
 static int build_general(cdpr_engine* h) {
@@ -440,415 +352,6 @@ GenCtl general_ctl(const cdpr_engine* h) {
   return g;
 }
 
-// General controller path: ONE launch per `per_launch` world steps (cdpr_general_step.hpp); with `record`, the observable
-// image of step j of the call goes to record + j * n_obs * stride.
-int run_steps_general(cdpr_engine* h, int nsteps, int per_launch, float4* record) {
-  if (h->step + (uint64_t)nsteps >= (1ull << 31)) {  // world-step stamps are int32 in the controller records
-    h->err = "general controller path: world-step counter would pass 2^31";
-    return CDPR_ERR_UNSUPPORTED;
-  }
-  StepArgs a = h->base;
-  a.state = h->d_state;
-  a.obs = h->d_obs;
-  a.cmd = nullptr;
-  a.dbg = h->dbg ? h->d_dbg : nullptr;
-  a.geom = h->d_geom;
-  a.batch = h->batch;
-  a.stride = h->stride;
-  a.pid_calls = 0;
-  copy_pid(h->pid_pos, a);  // unused
-  const size_t image = (size_t)h->n_obs * h->stride;
-  a.obs_step_stride = record ? image : 0;
-  GenCtl g = general_ctl(h);
-  // where the role-split one-step kernel serves the handle, its launches beat the one-wave kernel's multi-step ones
-  // (16 384 x 8: 9.2 against 13.7 us per step, 32 768: 10.1 against 21.6; same bits): fused updates and the trajectory
-  // record then run as one-step launches
-  if (h->plan.gen_split || h->plan.gen_lean) per_launch = 1;  // (likewise where the lean kernel + one-wave kernel pair steps the handle)
-  int done = 0;
-  while (done < nsteps) {
-    const int k = std::min(per_launch, nsteps - done);
-    // one step per launch on FK + TD handles up to two workgroups per CU: the role-split form (cdpr_general_split.hpp), beyond: the
-    // lean role-split kernel (two waves per SIMD; the rare controller paths by call) - planned_kernel, cdpr_select.hpp
-    const PlannedKernel pk = planned_kernel(h->plan, launch_shape(h, k));
-    const bool gsplit = pk.id == KernelId::GenSplit, glean = pk.id == KernelId::GenLean;
-    GenKernel kern = gsplit ? pick_gen_split11(h->n) : glean ? pick_gen_lean11(h->n) : pick_gen_kernel(h->n, h->plan.fk, h->plan.td, false, h->glay.nb > 11, pk.id == KernelId::GenOne);
-    h->last_kernel = pk;
-    a.nsteps = k;
-    a.flags = (h->step == 0) ? kFlagFirstWorldStep : 0u;
-    g.now_step = (int)h->step;
-    if (record) a.obs = record + (size_t)done * image;
-    a.publish_mask = publish_mask(h, k);
-    hipLaunchKernelGGL(kern, dim3((h->batch + 63u) / 64u), dim3((gsplit || glean) ? 128 : 64), 0, h->stream, a, g);
-    HIP_TRY(h, hipGetLastError());
-    ++h->launches;
-    h->step += (uint64_t)k;
-    done += k;
-  }
-  if (record && h->cfg.publish_period == 0.0 && h->step > 1)  // keep cdpr_get_* consistent: latest image into the engine's own
-    HIP_TRY(h, hipMemcpyAsync(h->d_obs, record + (size_t)(nsteps - 1) * image, image * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
-  return CDPR_OK;
-}
-
-// cdpr_create pays the cold costs of the handle's one-step kernel (the runtime loads a kernel's code object and sets up
-// its argument buffers on the FIRST launch: measured ~1 ms), not the first cdpr_update: one launch of exactly that kernel
-// over one workgroup of home-state robots in a scratch buffer, which is then freed.  The handle's own state is not touched.
-int warm_first_launch(cdpr_engine* h) {
-  if (h->plan.general || h->plan.fp64) return CDPR_OK;
-  if (const char* w = std::getenv("CDPR_NO_WARM_LAUNCH"))
-    if (w[0] == '1') return CDPR_OK;
-  const uint32_t rows = 64;
-  const std::vector<float4> s = home_state(h, rows);
-  DevBuf st, ob, cm, mt;
-  HIP_TRY(h, mt.alloc(rows));
-  HIP_TRY(h, hipMemsetAsync(mt.p, (int)(kMetaPosition | (20u << kMetaCallShift)), rows, h->stream));
-  HIP_TRY(h, st.alloc(s.size() * sizeof(float4)));
-  HIP_TRY(h, ob.alloc((size_t)h->n_obs * rows * sizeof(float4)));
-  HIP_TRY(h, cm.alloc((size_t)rows * h->n * sizeof(float)));
-  HIP_TRY(h, hipMemcpyAsync(st.p, s.data(), s.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemsetAsync(cm.p, 0, (size_t)rows * h->n * sizeof(float), h->stream));
-  StepArgs a = h->base;
-  a.state = st.as<float4>();
-  a.obs = ob.as<float4>();
-  a.cmd = cm.as<float>();
-  a.dbg = nullptr;
-  a.geom = h->d_geom;
-  a.batch = h->plan.lane_cable ? (h->n <= 4 ? 16u : 8u) : h->plan.lane_pair ? 32u : 64u;
-  a.stride = rows;
-  a.nsteps = 1;
-  a.obs_step_stride = 0;
-  a.flags = 0u;
-  a.publish_mask = 1ull;
-  copy_pid(h->plan.per_robot ? h->pid_vel : h->pid_pos, a);
-  copy_pid_alt(h->pid_pos, a.alt);
-  a.meta = mt.as<uint8_t>();
-  a.pid_calls = kCallSat;  // steady state: every branch of the step is taken, as in the launches that follow
-  a.ring_slot = 0;
-  set_weight_row(h, a);
-  hipLaunchKernelGGL(select_step_kernel(h, 1), dim3(1), dim3(step_block_threads(h, 1)), 0, h->stream, a);
-  HIP_TRY(h, hipGetLastError());
-  // ... and of the role-split kernel's steady-state instantiations, which the launches take from the step on that fills the window
-  // (split_steady_launch): both modes' - a Joy of the other kind may arrive at any step
-  if (planned_kernel(h->plan, launch_shape(h, 1)).id == KernelId::Split && h->split_steady) {
-    for (const bool vel : {false, true}) {
-      copy_pid(vel ? h->pid_vel : h->pid_pos, a);
-      hipLaunchKernelGGL(pick_split_steady_kernel(h->n, vel), dim3(1), dim3(128), 0, h->stream, a);
-      HIP_TRY(h, hipGetLastError());
-    }
-  }
-  HIP_TRY(h, wait_stream(h));
-  return CDPR_OK;
-}
-
-// One step-kernel launch over the whole batch, or (h->plan.chunk) the same launch cut into contiguous blocks of robots issued
-// back to back on the handle's stream: every pointer that is indexed by robot moves to the block's first robot, the row
-// stride stays.  Robots are independent, so the results are bit-identical to the single launch (tested).
-void launch_step(cdpr_engine* h, StepKernel kern, uint32_t robots_per_block, dim3 block, const StepArgs& a, uint32_t max_grid = 0) {
-  const uint32_t B = a.batch;
-  const uint32_t chunk = (h->plan.chunk && B > h->plan.chunk) ? h->plan.chunk : B;
-  const uint32_t pieces = (B + chunk - 1u) / chunk;
-  const uint32_t each = (((B + pieces - 1u) / pieces) + 63u) & ~63u;  // balanced, whole wavefronts
-  for (uint32_t first = 0; first < B; first += each) {
-    StepArgs c = a;
-    c.batch = std::min(each, B - first);
-    c.state = a.state + first;
-    c.obs = a.obs + first;
-    if (a.cmd) c.cmd = a.cmd + (size_t)first * h->n;
-    if (a.dbg) c.dbg = a.dbg + (size_t)first * CDPR_PID_DEBUG_AXES;
-    if (a.meta) c.meta = a.meta + first;
-    uint32_t grid = (c.batch + robots_per_block - 1u) / robots_per_block;
-    if (max_grid && grid > max_grid) grid = max_grid;  // persistent kernel: the waves walk over the blocks
-    hipLaunchKernelGGL(kern, dim3(grid), block, 0, h->stream, c);
-    ++h->launches;
-  }
-}
-
-// the general path's hot rows back into the H slots (cdpr_gen_flush_hot_kernel) before a Pid's records are reset or latched over
-static void flush_hot(cdpr_engine* h) {
-  if (!h->d_rec || !h->plan.gen_hot) return;
-  GenFlushArgs fa{};
-  fa.rec = h->d_rec, fa.rstride = h->stride, fa.batch = h->batch, fa.lay = h->glay, fa.nbuf = std::max(h->gpid[0].nbuf, 1);
-  hipLaunchKernelGGL(cdpr_gen_flush_hot_kernel, dim3((h->batch + 255u) / 256u), dim3(256), 0, h->stream, fa);
-}
-
-// Pid::reset of one Pid of every cable (general path): its slots, its rows
-static hipError_t reset_block(cdpr_engine* h, int which) {
-  const GenLayout& L = h->glay;
-  flush_hot(h);
-  hipError_t e1 = hipMemsetAsync(h->d_rec + (size_t)L.block_a(which, 0) * h->stride * 4, 0, (size_t)L.pid_slots() * h->stride * 16, h->stream);
-  if (e1 != hipSuccess || L.pid_rows() == 0) return e1;
-  return hipMemsetAsync(h->d_rec + ((size_t)L.slots() * 4 + (size_t)L.block_b(which, 0)) * h->stride, 0, (size_t)L.pid_rows() * h->stride * 4, h->stream);
-}
-
-// precision = 64 with the hold branch: Pid::reset of one Pid of every cable (its rows behind the state)
-static hipError_t reset_block64(cdpr_engine* h, int which) {
-  for (uint32_t i = 0; i < h->n; ++i) {
-    hipError_t e1 = hipMemsetAsync(h->d_state64 + (size_t)f64_hold_row((int)h->n, (int)i, which, hold_win(h)) * h->stride, 0, (size_t)hold_pid_rows(hold_win(h)) * h->stride * sizeof(double),
-                                   h->stream);
-    if (e1 != hipSuccess) return e1;
-  }
-  return hipSuccess;
-}
-
-// Per-robot handles: every robot has its own mode, so a command of `kind` (masked or not) is latched on the device, robot by
-// robot, by the latch kernel of the handle's path: precision = 64, register-resident, general.
-static int latch_per_robot(cdpr_engine* h, int kind, const float* pending, const uint8_t* mask) {
-  const CmdKind& K = kCmdKind[kind];
-  const dim3 grid((h->batch + 255u) / 256u), block(256);
-  if (h->plan.fp64) {  // the same on the double state (integral rows 20 + 11 i + 10)
-    LatchF64Args lf{};
-    lf.mask = mask;
-    lf.meta = h->d_mode;
-    lf.pending = pending;
-    lf.target = h->d_target;
-    lf.state = h->d_state64;
-    lf.stride = h->stride;
-    lf.batch = h->batch;
-    lf.n = h->n;
-    lf.new_mode = K.meta;
-    lf.hold = h->plan.hold64 ? 1u : 0u;
-    lf.win = (uint32_t)win64(h);
-    lf.hold_win = (uint32_t)hold_win(h);
-    hipLaunchKernelGGL(cdpr_latch_f64_kernel, grid, block, 0, h->stream, lf);
-  } else if (!h->plan.general) {  // one active target row and one Pid record per robot
-    LatchFastArgs lf{};
-    lf.mask = mask;
-    lf.meta = h->d_mode;
-    lf.pending = pending;
-    lf.target = h->d_target;
-    lf.hot = h->d_state + (size_t)(plat_slots(h->plan.fk) + 5 * cable_pairs((int)h->n)) * h->stride;
-    lf.stride = h->stride;
-    lf.batch = h->batch;
-    lf.n = h->n;
-    lf.hot_rows = (uint32_t)((cable_pairs((int)h->n) + 1) / 2);
-    lf.new_mode = K.meta;
-    hipLaunchKernelGGL(cdpr_latch_fast_kernel, grid, block, 0, h->stream, lf);
-  } else {
-    flush_hot(h);
-    GenLatchArgs la{};
-    la.mask = mask;
-    la.mode = h->d_mode;
-    la.pending = pending;
-    la.latched = h->cmd[kind].d[0];
-    la.rec = h->d_rec;
-    la.rstride = h->stride;
-    la.batch = h->batch;
-    la.n = h->n;
-    la.reset_pid = K.reset_pid;  // (-1: setForce resets no Pid)
-    la.lay = h->glay;
-    la.new_mode = K.mode;
-    hipLaunchKernelGGL(cdpr_gen_latch_kernel, grid, block, 0, h->stream, la);
-  }
-  HIP_TRY(h, hipGetLastError());
-  return CDPR_OK;
-}
-
-// PLG.cpp:206-219: an update starts by latching the pending commands, velocity first, then position; force after the two
-// Joy topics ([NEW] ordering: the reference has no force callback).  `reset_pid`: the mode change of a uniform handle asks
-// the launches that follow to zero their single Pid record (register-resident path, precision = 64 without the hold branch).
-static int latch_pending(cdpr_engine* h, bool& reset_pid) {
-  for (CmdChannel& c : h->cmd) {
-    if (c.pending && c.ready_wait) {  // a host Joy batch is (or was) on its way on the copy stream
-      HIP_TRY(h, hipStreamWaitEvent(h->stream, c.ready_wait, 0));
-      c.ready_wait = nullptr;
-    }
-  }
-  bool touched[kCmdKinds] = {false, false, false};  // the engine's own pending buffer was read (latch kernel) or swapped
-  for (int k = 0; k < kCmdKinds; ++k) {
-    CmdChannel& c = h->cmd[k];
-    if (!c.pending) continue;
-    const CmdKind& K = kCmdKind[k];
-    if (h->plan.per_robot) {
-      // (a batch of a device-resident schedule, cdpr_update_scheduled_kind, is latched from the caller's buffers in place)
-      const bool in_place = c.sched_rows != nullptr;
-      if (int rc = latch_per_robot(h, k, in_place ? c.sched_rows : c.d[1].p, in_place ? c.sched_mask : (c.masked ? c.d_mask.p : nullptr))) return rc;
-      touched[k] = !in_place;
-    } else {
-      if (c.ext[1]) {  // bound caller buffer: latched by pointer, nothing copied
-        c.ext[0] = c.ext[1];
-        c.ext[1] = nullptr;
-      } else {
-        c.d[0].swap(c.d[1]);
-        c.ext[0] = nullptr;
-        touched[k] = true;  // what is pending now was the latched buffer of the launches queued so far
-      }
-      if (K.reset_pid >= 0) {  // entering a mode resets its Pid (fast path: the single record now belongs to that Pid)
-        reset_pid = (h->mode != K.mode);
-        if (h->plan.general && reset_pid) HIP_TRY(h, reset_block(h, K.reset_pid));
-        if (h->plan.hold64 && reset_pid) HIP_TRY(h, reset_block64(h, K.reset_pid));
-      }
-      h->mode = K.mode;
-    }
-    c.pending = c.masked = false;
-    c.have = true;
-  }
-  for (CmdChannel& c : h->cmd) c.sched_rows = nullptr;
-  // What is now the PENDING buffer of a touched kind was last used by the work queued on the compute stream so far: the next
-  // host batch of that kind, which travels on the copy stream, may overwrite it only once that work is through.  The event is
-  // recorded on EVERY such latch once a copy stream exists, however the latched command itself arrived (host, _device or
-  // masked): a stale event from an earlier host batch would let the copy run into launches that still read the buffer.  Bound
-  // commands swap nothing and handles that never saw a host batch have no copy stream: no event, no device time.
-  for (int k = 0; k < kCmdKinds; ++k) {
-    CmdChannel& c = h->cmd[k];
-    if (!touched[k] || !h->copy_stream) continue;
-    if (!c.free_ev) HIP_TRY(h, hipEventCreateWithFlags(&c.free_ev, hipEventDisableTiming));
-    HIP_TRY(h, hipEventRecord(c.free_ev, h->stream));
-    c.free_ev_set = true;
-  }
-  return CDPR_OK;
-}
-
-int run_steps(cdpr_engine* h, int nsteps, int per_launch, float4* record = nullptr) {
-  if (!h) return CDPR_ERR_INVALID;
-  if (nsteps < 0 || per_launch < 1 || (per_launch > 64 && !h->sched_refresh)) {
-    h->err = "nsteps must be >= 0 and steps_per_launch in 1..64";
-    return CDPR_ERR_INVALID;
-  }
-  if (nsteps == 0) return CDPR_OK;
-  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-
-  bool reset_pid = false;
-  if (int rc = latch_pending(h, reset_pid)) return rc;
-  if (h->plan.general) return run_steps_general(h, nsteps, per_launch, record);
-  if (h->plan.fp64) return run_steps_f64(h, nsteps, per_launch, reset_pid, reinterpret_cast<double*>(record));
-
-  if (reset_pid) {  // Pid::reset (Pid.cpp:100-115): zero every controller record; rare, so done outside the step kernel
-    h->pid_calls = 0;
-    const int P = plat_slots(h->plan.fk);
-    HIP_TRY(h, hipMemsetAsync(h->d_state + (size_t)P * h->stride, 0, (size_t)ctrl_slots((int)h->n) * h->stride * sizeof(float4), h->stream));
-  }
-  StepArgs a = h->base;
-  a.state = h->d_state;
-  a.obs = h->d_obs;
-  a.dbg = h->dbg ? h->d_dbg : nullptr;
-  a.geom = h->d_geom;
-  a.batch = h->batch;
-  a.stride = h->stride;
-  // trajectory record: the observable image of step j of the call goes to record + j * n_obs * stride
-  const size_t image = (size_t)h->n_obs * h->stride;
-  a.obs_step_stride = record ? image : 0;
-  if (h->plan.per_robot) {
-    copy_pid(h->pid_vel, a);
-    copy_pid_alt(h->pid_pos, a.alt);
-    a.cmd = h->d_target;
-    a.meta = h->d_mode;
-  } else {
-    copy_pid(h->mode == kModeVelocity ? h->pid_vel : h->pid_pos, a);  // (Force mode: unused, no Pid runs)
-    a.cmd = h->cmd[cmd_kind_of_mode(h->mode)].latched();  // position: all zeros until the first jointPositions message: target 0 (PLG.cpp:153-157)
-  }
-  const uint32_t robots_per_block = h->plan.lane_cable ? (h->n <= 4 ? 16u : 8u) : h->plan.lane_pair ? 32u : 64u;
-  const dim3 grid((h->batch + robots_per_block - 1u) / robots_per_block);
-
-  constexpr int kGraphChunk = 10;  // launches per captured graph = one ring period: a chain ends on the ring slot it started from.
-                                   // (Ten, not more: a caller that refreshes its Joy batch every 10 steps - bench.py, the reference's
-                                   // 100 Hz publishers against the 1 kHz world - hands over 10 steps per call.)
-  int done = 0;
-  while (done < nsteps) {
-    const int k = std::min(per_launch, nsteps - done);
-    a.nsteps = k;
-    a.flags = h->plan.per_robot ? 0u : (h->mode == kModeVelocity ? kFlagActualIsVelocity : h->mode == kModeForce ? kFlagForceMode : 0u);
-    const bool first_world = (h->step == 0);
-    if (first_world) a.flags |= kFlagFirstWorldStep;
-    // the kernel uses calls != 0 and calls >= nbuf (<= 11): the count saturates, and the ring position follows the world
-    // step, so steady-state launch sequences repeat with period 10
-    a.pid_calls = sat_pid_calls(h->pid_calls);
-    a.ring_slot = ring_slot_of(h->step);
-    set_weight_row(h, a);
-    // a launch over a command schedule always runs on the several-steps kernel, even for one step: only that one reads the
-    // schedule, its mailbox and kFlagPublishAll
-    const int kk = h->sched_refresh ? std::max(k, 2) : k;
-    const PlannedKernel pk = planned_kernel(h->plan, launch_shape(h, kk, pair_stream_steady(h, a)));
-    StepKernel kern = step_kernel_of(h, pk);
-    // the role-split kernel keeps its identity (pk, cdpr_kernel_name) whichever instantiation of its controller wave a launch takes
-    h->last_variant = split_steady_launch(h, pk, a) ? 1 : 0;
-    if (h->last_variant) kern = pick_split_steady_kernel(h->n, h->mode == kModeVelocity);
-    const dim3 block(pk.block);
-    const bool stream = pk.id == KernelId::PairStream;  // steady state of a plain lane-pair handle: the branch-free several-steps kernel
-    auto weights_for = [&](StepArgs& x) {                // ... which reads the weights by AGE from the row of ring position 0
-      const int slot = x.ring_slot;
-      if (stream) x.ring_slot = 0;
-      set_weight_row(h, x);
-      x.ring_slot = slot;
-    };
-    if (stream) weights_for(a);
-    h->last_kernel = pk;
-
-    // Steady state (every step published, derivative window full, not t = 0): the next launches are
-    // byte-identical, so replay them from a captured hipGraph instead of paying a host launch each.
-    // (measured on MI355X: 3.57 -> 3.41 us/step at 4 096 x 4 cables; at 65 536 x 8 cables the 15 us kernels already
-    // hide the host launch and the replay's fixed cost makes it 2 % slower, so only small batches use it)
-    // (the ring position advances with every step, so a captured chain is only valid from the position it was captured at:
-    //  part of the cache key; the call count must be saturated (per-robot handles keep theirs on the device))
-    if (record) a.obs = record + (size_t)done * image;
-    const bool steady = !record && !h->sched_refresh && h->use_graphs && (size_t)h->batch * h->n <= 131072u && !first_world && (h->plan.per_robot || a.pid_calls == kCallSat || h->mode == kModeForce) &&
-                        h->cfg.publish_period == 0.0 && (nsteps - done) >= kGraphChunk * k;
-    if (steady) {
-      a.publish_mask = (k >= 64) ? ~0ull : ((1ull << k) - 1ull);
-      cdpr_engine::GraphEntry* ge = nullptr;
-      for (auto& g : h->graphs)
-        if (g.kern == (void*)kern && g.cmd == a.cmd && g.steps_per_launch == k && g.flags == a.flags && g.start_slot == a.ring_slot) ge = &g;
-      if (!ge) {
-        cdpr_engine::GraphEntry g{(void*)kern, a.cmd, k, kGraphChunk, a.ring_slot, a.flags, nullptr, nullptr};
-        // any failure inside the capture: end it, drop the partial graph, stop using graphs on this handle and
-        // fall through to the eager launches below (the stream must never be left capturing)
-        bool captured = hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-        if (captured) {
-          bool launched = true;
-          for (int j = 0; j < kGraphChunk; ++j) {
-            StepArgs aj = a;  // each node carries its own ring position
-            aj.ring_slot = (a.ring_slot + j * k) % kWin;
-            weights_for(aj);
-            hipLaunchKernelGGL(kern, grid, block, 0, h->stream, aj);
-            launched = launched && (hipGetLastError() == hipSuccess);
-          }
-          captured = (hipStreamEndCapture(h->stream, &g.graph) == hipSuccess) && launched && g.graph;
-          if (captured && hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0) != hipSuccess) captured = false;
-          if (!captured && g.graph) (void)hipGraphDestroy(g.graph);
-        }
-        if (!captured) {
-          (void)hipGetLastError();
-          h->use_graphs = false;
-          continue;  // same `done`: this chunk is launched eagerly on the next pass
-        }
-        if (h->graphs.size() >= 32) {  // small cache (two Joy buffers x a few ring positions x step counts): drop the oldest
-          (void)hipGraphExecDestroy(h->graphs.front().exec);
-          (void)hipGraphDestroy(h->graphs.front().graph);
-          h->graphs.erase(h->graphs.begin());
-        }
-        h->graphs.push_back(g);
-        ge = &h->graphs.back();
-      }
-      HIP_TRY(h, hipGraphLaunch(ge->exec, h->stream));
-      const int steps = kGraphChunk * k;
-      h->launches += kGraphChunk;
-      h->step += (uint64_t)steps;
-      if (h->mode != kModeForce) h->pid_calls = sat_pid_calls(h->pid_calls + steps);  // (no Pid call in Force mode)
-      h->prev_publish = sim_time(h->step - 1, h->cfg.dt);
-      done += steps;
-      continue;
-    }
-
-    a.publish_mask = 0;
-    if (h->sched_refresh) {  // a whole schedule in one launch (publish_period == 0: every step but world step 0 is published)
-      a.flags |= kFlagPublishAll;
-      a.sched_refresh = h->sched_refresh;
-      a.sched_stride = (size_t)h->batch * h->n;
-      a.sched_ready = h->sched_ready;
-      a.fault = h->d_fault;
-      h->prev_publish = sim_time(h->step + (uint64_t)k - 1, h->cfg.dt);
-    } else {
-      a.publish_mask = publish_mask(h, k);
-    }
-    launch_step(h, kern, robots_per_block, block, a, (h->plan.persist && k == 1 && !h->plan.per_robot) ? h->persist_grid : 0u);
-    HIP_TRY(h, hipGetLastError());
-    h->step += (uint64_t)k;
-    if (h->mode != kModeForce) h->pid_calls = sat_pid_calls(h->pid_calls + k - (first_world ? 1 : 0));
-    done += k;
-  }
-  if (record && h->cfg.publish_period == 0.0 && h->step > 1)  // keep cdpr_get_* consistent: latest image into the engine's own
-    HIP_TRY(h, hipMemcpyAsync(h->d_obs, record + (size_t)(nsteps - 1) * image, image * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
-  return CDPR_OK;
-}
-
 int fetch_slots(cdpr_engine* h, const float4* dsrc, int nslots, std::vector<float4>& host) {
   host.resize((size_t)nslots * h->stride);
   HIP_TRY(h, hipMemcpyAsync(host.data(), dsrc, host.size() * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
@@ -887,6 +390,20 @@ int fetch_fields(cdpr_engine* h, const float4* rows, const std::vector<std::pair
 // pose7 = slot 0 xyzw, slot 1 xyz; twist6 = slot 1 w, slot 2 xyzw, slot 3 x
 const std::vector<std::pair<int, int>> kPoseFields = {{0, 0}, {0, 1}, {0, 2}, {0, 3}, {1, 0}, {1, 1}, {1, 2}};
 const std::vector<std::pair<int, int>> kTwistFields = {{1, 3}, {2, 0}, {2, 1}, {2, 2}, {2, 3}, {3, 0}};
+
+// (slot, component) per column of the robot-major arrays a getter hands out: joint fields [f0, f1) (0 position, 1 velocity, 2 effort)
+// of every cable, then - `platform` - pose7 and twist6
+static std::vector<std::pair<int, int>> obs_columns(uint32_t n, int f0, int f1, bool platform) {
+  std::vector<std::pair<int, int>> cols;
+  cols.reserve((size_t)(f1 - f0) * n + 13u);
+  for (int f = f0; f < f1; ++f)
+    for (uint32_t i = 0; i < n; ++i) cols.push_back(obs_joint_field((int)n, f, i));
+  if (platform) {
+    cols.insert(cols.end(), kPoseFields.begin(), kPoseFields.end());
+    cols.insert(cols.end(), kTwistFields.begin(), kTwistFields.end());
+  }
+  return cols;
+}
 
 int fetch_platform(cdpr_engine* h, const float4* rows, float* pose7, float* twist6) {
   int rc = fetch_fields(h, rows, kPoseFields, pose7);
@@ -1231,11 +748,6 @@ int cdpr_update(cdpr_handle_t h, int nsteps) { return run_steps(h, nsteps, 1); }
 
 int cdpr_update_fused(cdpr_handle_t h, int nsteps, int steps_per_launch) { return run_steps(h, nsteps, steps_per_launch); }
 
-// One observable image: fp32 handles n_obs float4 slot rows, precision = 64 handles f64_obs_rows(n) rows of doubles
-static size_t image_bytes(const cdpr_engine* h) {
-  return h->plan.fp64 ? (size_t)f64_obs_rows((int)h->n) * h->stride * sizeof(double) : (size_t)h->n_obs * h->stride * sizeof(float4);
-}
-
 int cdpr_observable_image_bytes(cdpr_handle_t h, size_t* bytes) {
   if (!h || !bytes) return CDPR_ERR_INVALID;
   *bytes = image_bytes(h);
@@ -1253,133 +765,7 @@ int cdpr_update_record(cdpr_handle_t h, int nsteps, int steps_per_launch, void* 
     h->err = "cdpr_update_record: record buffer missing or smaller than nsteps observable images";
     return CDPR_ERR_INVALID;
   }
-  return run_steps(h, nsteps, steps_per_launch, static_cast<float4*>(d_record));
-}
-
-// A command schedule resident in HBM, any kind of command, any handle.  Semantics: for j = 0 ..: the callback of `kind`
-// with batch j (for the robots of mask j), then refresh_steps x update().  Two forms serve it:
-//   * in the launch: uniform-mode handles on the register-resident path with one or two lanes per robot run the whole
-//     schedule in ONE launch of the several-steps kernel (the lanes read batch j at step j * refresh_steps themselves;
-//     state, windows and integrals stay on chip);
-//   * as a chain: every other handle (general controller path, per-robot modes with or without masks, precision = 64,
-//     one lane per cable) latches batch j from the caller's buffers in place and queues its steps, batch after batch,
-//     without a host round trip; a mailbox is honoured by a one-thread wait kernel in front of the batch's latch.
-// A command of another kind pending at the call is latched with batch 0 in update()'s usual order (velocity, position,
-// force): batch 0 then goes the chain's way, so that a mode change between batch 0 and batch 1 is what the call sequence
-// would do (the schedule's rows must never be read as targets of another mode).
-static int scheduled_update(cdpr_engine* h, uint32_t kind, int nsteps, int refresh_steps, const float* d_commands, const uint32_t* d_ready,
-                            const uint8_t* d_masks, void* d_record, size_t record_bytes) {
-  if (kind > 2u) {
-    h->err = "cdpr_update_scheduled_kind: kind must be CDPR_COMMAND_VELOCITY, _POSITION or _FORCE";
-    return CDPR_ERR_INVALID;
-  }
-  if (nsteps < 0 || refresh_steps < 1 || !d_commands) {
-    h->err = "cdpr_update_scheduled: nsteps >= 0, refresh_steps >= 1 and the command schedule are required";
-    return CDPR_ERR_INVALID;
-  }
-  if (d_masks && !h->plan.per_robot) {
-    h->err = "cdpr_update_scheduled_kind: robot masks need a handle created with per_robot_commands = 1";
-    return CDPR_ERR_UNSUPPORTED;
-  }
-  if (h->cfg.publish_period != 0.0 && d_record) {
-    h->err = "cdpr_update_scheduled: a trajectory record needs publish_period == 0 (every step published)";
-    return CDPR_ERR_UNSUPPORTED;
-  }
-  const size_t image = image_bytes(h) / sizeof(float4);  // in float4 units (both image kinds are multiples of 16 B: stride is a multiple of 64)
-  if (d_record && record_bytes < image_bytes(h) * (size_t)nsteps) {
-    h->err = "cdpr_update_scheduled: record buffer smaller than nsteps observable images";
-    return CDPR_ERR_INVALID;
-  }
-  if (nsteps == 0) return CDPR_OK;
-  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  if (d_ready && !h->h_fault) {  // the status word a mailbox that never delivers is reported through
-    HIP_TRY(h, h->h_fault.alloc(sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
-    *h->h_fault = 0u;
-    HIP_TRY(h, hipHostGetDevicePointer((void**)&h->d_fault, h->h_fault, 0));
-  }
-  float4* const record = static_cast<float4*>(d_record);
-  const size_t batch_floats = (size_t)h->batch * h->n;
-  CmdChannel& c = h->cmd[kind];
-  const int nbatches = (nsteps + refresh_steps - 1) / refresh_steps;
-  // batch j becomes the pending command of `kind`, in place
-  auto stage_batch = [&](int j) {
-    const float* rows = d_commands + (size_t)j * batch_floats;
-    if (h->plan.per_robot) {
-      c.sched_rows = rows;
-      c.sched_mask = d_masks ? d_masks + (size_t)j * h->batch : nullptr;
-    } else {
-      c.ext[1] = rows;
-    }
-    c.pending = true;
-    c.masked = false;
-  };
-  // Per-robot handles: a command of the SAME kind still pending at the call (cdpr_set_*_command[_masked] without an update since)
-  // would have to reach its robots before batch 0 reaches batch 0's - B independent plugins each keep the last message that
-  // reached THEM.  Staging batch 0 would overwrite it silently: refused, the caller latches it with cdpr_update first
-  // or leaves it out.  (Uniform handles: the later message of a kind replaces the earlier one, as in the plugin, PLG.cpp:67-83.)
-  if (h->plan.per_robot && c.pending) {
-    h->err = "cdpr_update_scheduled_kind: a command of the same kind is still pending on this per-robot handle; step it in with cdpr_update first";
-    return CDPR_ERR_INVALID;
-  }
-  // whatever way this function is left, nothing of the caller's schedule stays staged in the handle: an error return must not
-  // leave `pending` set on pointers the caller may free, nor the schedule fields set for the next plain cdpr_update
-  struct Unstage {
-    cdpr_engine* h; CmdChannel& c; bool ok = false;
-    ~Unstage() {
-      c.sched_rows = nullptr;
-      c.sched_mask = nullptr;
-      h->sched_refresh = 0;
-      h->sched_ready = nullptr;
-      if (!ok) {  // an error in between: drop the batch that was staged but not latched
-        if (c.pending && (h->plan.per_robot || c.ext[1])) c.pending = false;
-        c.ext[1] = nullptr;
-      }
-    }
-  } unstage{h, c};
-  const bool in_launch = !(h->plan.general || h->plan.fp64 || h->plan.per_robot || h->plan.lane_cable) && h->cfg.publish_period == 0.0;
-  bool others = false;
-  for (uint32_t k = 0; k < (uint32_t)kCmdKinds; ++k) others = others || (k != kind && h->cmd[k].pending);
-  int j = 0, done = 0;
-  // ---- the chain: every batch of a handle the launch form does not serve; batch 0 where another command is pending
-  const int chain_spl = ((size_t)h->batch * h->n <= 131072u) ? std::min(refresh_steps, 64) : 1;  // small batches: the hold in one launch
-  while (j < nbatches && (!in_launch || (j == 0 && others))) {
-    if (d_ready) {
-      hipLaunchKernelGGL(cdpr_mailbox_wait_kernel, dim3(1), dim3(1), 0, h->stream, d_ready + j, h->d_fault);
-      HIP_TRY(h, hipGetLastError());
-    }
-    stage_batch(j);
-    const int k = std::min(refresh_steps, nsteps - done);
-    if (int rc = run_steps(h, k, chain_spl, record ? record + (size_t)done * image : nullptr)) return rc;
-    done += k;
-    ++j;
-  }
-  while (j < nbatches) {
-    // ---- the rest in one launch: batch j is latched as any command of its kind is (entering the mode resets its Pid,
-    //      JFC.cpp:101-103,113-115), the later ones are read by the kernel.  Lane-pair handles whose derivative windows are not
-    //      full yet (world step 0, a mode just entered) take the batches that fill them in a launch of their own: from there on
-    //      the launch qualifies for the steady-state kernel (pair_stream_ok), which has no branch for a filling window.
-    stage_batch(j);
-    h->sched_refresh = refresh_steps;
-    h->sched_ready = d_ready ? d_ready + j : nullptr;
-    int rest = nsteps - done;
-    if (h->plan.lane_pair && h->plan.pair_stream && !h->plan.fk && !h->plan.td && kind != CDPR_COMMAND_FORCE) {
-      const int new_mode = (kind == CDPR_COMMAND_VELOCITY) ? kModeVelocity : kModePosition;
-      const int nbuf = (kind == CDPR_COMMAND_VELOCITY) ? h->pid_vel.nbuf : h->pid_pos.nbuf;
-      const int calls = (h->mode == new_mode) ? h->pid_calls : 0;  // (entering the mode resets the Pid)
-      const int fill = (calls >= nbuf ? 0 : nbuf - calls) + (h->step == 0 ? 1 : 0);
-      const int pre = ((fill + refresh_steps - 1) / refresh_steps) * refresh_steps;  // whole batches
-      if (pre > 0 && pre < rest) rest = pre;
-    }
-    const int rc = run_steps(h, rest, rest, record ? record + (size_t)done * image : nullptr);
-    h->sched_refresh = 0;
-    h->sched_ready = nullptr;
-    if (rc != CDPR_OK) return rc;
-    done += rest;
-    j += (rest + refresh_steps - 1) / refresh_steps;
-    if (j >= nbatches) c.ext[0] = d_commands + (size_t)(nbatches - 1) * batch_floats;  // the batch that stays latched
-  }
-  unstage.ok = true;
-  return CDPR_OK;
+  return run_steps(h, nsteps, steps_per_launch, d_record);
 }
 
 int cdpr_update_scheduled(cdpr_handle_t h, int nsteps, int refresh_steps, const float* d_commands, const uint32_t* d_ready, void* d_record,
@@ -1468,27 +854,25 @@ uint32_t cdpr_mapping(cdpr_handle_t h) {
 
 uint64_t cdpr_step_count(cdpr_handle_t h) { return h ? h->step : 0; }
 
+static int fetch_joint_states(cdpr_engine* h, float* position, float* velocity, float* effort) {
+  if (h->plan.fp64) return fetch_observables64(h, position, velocity, effort, nullptr, nullptr, true);
+  float* dst[3] = {position, velocity, effort};
+  for (int f = 0; f < 3; ++f)
+    if (int rc = fetch_fields(h, h->d_obs, obs_columns(h->n, f, f + 1, false), dst[f])) return rc;
+  return CDPR_OK;
+}
+
 int cdpr_get_joint_states(cdpr_handle_t h, float* position, float* velocity, float* effort) {
   if (!h) return CDPR_ERR_INVALID;
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  if (h->plan.fp64) return checked(h, fetch_observables64(h, position, velocity, effort, nullptr, nullptr, true));
-  float* dst[3] = {position, velocity, effort};
-  for (int f = 0; f < 3; ++f) {
-    std::vector<std::pair<int, int>> fields;
-    for (uint32_t i = 0; i < h->n; ++i) fields.push_back(obs_joint_field((int)h->n, f, i));
-    int rc = fetch_fields(h, h->d_obs, fields, dst[f]);
-    if (rc != CDPR_OK) return rc;
-  }
-  return check_fault(h);
+  return checked(h, fetch_joint_states(h, position, velocity, effort));
 }
 
 // JointState + PlatformState of the last published step in ONE device round trip (PLG.cpp:248-280 publishes both every
 // step): the gather kernel writes the five arrays into a pinned host image and then a completion word the host spins
 // on.  (cdpr_get_joint_states + cdpr_get_platform_state are five gathers, five copies and five waits.)
-int cdpr_get_observables(cdpr_handle_t h, float* position, float* velocity, float* effort, float* pose7, float* twist6) {
-  if (!h) return CDPR_ERR_INVALID;
-  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  if (h->plan.fp64) return checked(h, fetch_observables64(h, position, velocity, effort, pose7, twist6, true));
+static int fetch_observables(cdpr_engine* h, float* position, float* velocity, float* effort, float* pose7, float* twist6) {
+  if (h->plan.fp64) return fetch_observables64(h, position, velocity, effort, pose7, twist6, true);
   const uint32_t n = h->n, width = 3u * n + 13u;
   if (width > kPublishMaxWidth) {  // (the kernel argument holds kPublishMaxWidth (slot, component) pairs)
     h->err = "cdpr_get_observables: more columns than the publish kernel's field table holds";
@@ -1530,14 +914,8 @@ int cdpr_get_observables(cdpr_handle_t h, float* position, float* velocity, floa
   u.batch = h->batch;
   u.n = n;
   u.width = width;
-  uint32_t j = 0;
-  for (int f = 0; f < 3; ++f)
-    for (uint32_t i = 0; i < n; ++i, ++j) {
-      const std::pair<int, int> sc = obs_joint_field((int)n, f, i);
-      u.slot[j] = (uint8_t)sc.first, u.comp[j] = (uint8_t)sc.second;
-    }
-  for (const auto& pc : kPoseFields) u.slot[j] = (uint8_t)pc.first, u.comp[j] = (uint8_t)pc.second, ++j;
-  for (const auto& pc : kTwistFields) u.slot[j] = (uint8_t)pc.first, u.comp[j] = (uint8_t)pc.second, ++j;
+  const std::vector<std::pair<int, int>> cols = obs_columns(n, 0, 3, true);
+  for (uint32_t j = 0; j < width; ++j) u.slot[j] = (uint8_t)cols[j].first, u.comp[j] = (uint8_t)cols[j].second;
   hipLaunchKernelGGL(cdpr_publish_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, h->stream, u);
   HIP_TRY(h, hipGetLastError());
   if (direct) {
@@ -1577,15 +955,19 @@ int cdpr_get_observables(cdpr_handle_t h, float* position, float* velocity, floa
   if (effort) std::memcpy(effort, src + 2 * bn, bn * sizeof(float));
   if (pose7) std::memcpy(pose7, src + 3 * bn, (size_t)h->batch * 7 * sizeof(float));
   if (twist6) std::memcpy(twist6, src + 3 * bn + (size_t)h->batch * 7, (size_t)h->batch * 6 * sizeof(float));
-  return check_fault(h);
+  return CDPR_OK;
+}
+
+int cdpr_get_observables(cdpr_handle_t h, float* position, float* velocity, float* effort, float* pose7, float* twist6) {
+  if (!h) return CDPR_ERR_INVALID;
+  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
+  return checked(h, fetch_observables(h, position, velocity, effort, pose7, twist6));
 }
 
 int cdpr_get_platform_state(cdpr_handle_t h, float* pose7, float* twist6) {
   if (!h) return CDPR_ERR_INVALID;
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  if (h->plan.fp64) return checked(h, fetch_observables64(h, nullptr, nullptr, nullptr, pose7, twist6, true));
-  const int rc = fetch_platform(h, h->d_obs, pose7, twist6);
-  return rc != CDPR_OK ? rc : check_fault(h);
+  return checked(h, h->plan.fp64 ? fetch_observables64(h, nullptr, nullptr, nullptr, pose7, twist6, true) : fetch_platform(h, h->d_obs, pose7, twist6));
 }
 
 int cdpr_get_raw_state(cdpr_handle_t h, float* pose7, float* twist6) {
@@ -1595,8 +977,7 @@ int cdpr_get_raw_state(cdpr_handle_t h, float* pose7, float* twist6) {
     int rc = fetch_rows64(h, h->d_state64, kF64Pose, 7, pose7, true);
     return rc != CDPR_OK ? rc : checked(h, fetch_rows64(h, h->d_state64, kF64Twist, 6, twist6, true));
   }
-  const int rc = fetch_platform(h, h->d_state, pose7, twist6);
-  return rc != CDPR_OK ? rc : check_fault(h);
+  return checked(h, fetch_platform(h, h->d_state, pose7, twist6));
 }
 
 int cdpr_get_pid_debug(cdpr_handle_t h, float* axes9) {
@@ -1611,12 +992,11 @@ int cdpr_get_pid_debug(cdpr_handle_t h, float* axes9) {
     HIP_TRY(h, hipMemcpyAsync(d.data(), h->d_dbg64, d.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, wait_stream(h));
     for (size_t i = 0; i < d.size(); ++i) axes9[i] = (float)d[i];
-    return check_fault(h);
+  } else {
+    HIP_TRY(h, hipMemcpyAsync(axes9, h->d_dbg, (size_t)h->batch * CDPR_PID_DEBUG_AXES * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, wait_stream(h));
   }
-  HIP_TRY(h, hipMemcpyAsync(axes9, h->d_dbg, (size_t)h->batch * CDPR_PID_DEBUG_AXES * sizeof(float), hipMemcpyDeviceToHost,
-                            h->stream));
-  HIP_TRY(h, wait_stream(h));
-  return check_fault(h);
+  return checked(h, CDPR_OK);
 }
 
 int cdpr_get_fk_state(cdpr_handle_t h, float* pose7, float* residual, int32_t* iterations) {
@@ -1645,7 +1025,8 @@ int cdpr_get_td_state(cdpr_handle_t h, float* tension, int32_t* infeasible) {
     h->err = "CDPR_STAGE_TD not enabled";
     return CDPR_ERR_UNSUPPORTED;
   }
-  int rc = cdpr_get_joint_states(h, nullptr, nullptr, tension);  // applied force == distributed tension
+  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
+  int rc = fetch_joint_states(h, nullptr, nullptr, tension);  // applied force == distributed tension
   if (rc != CDPR_OK) return rc;
   rc = h->plan.fp64 ? fetch_int_row64(h, kF64ObsFlags, infeasible) : fetch_fields(h, h->d_obs, {{3, 3}}, infeasible, 1u);
   if (rc == CDPR_OK && infeasible)

@@ -1,5 +1,5 @@
-// cdpr_engine_f64.hip - host side of cdpr_config_t.precision = 64: the handle's set-up (build_f64), the launch chain of the fp64 step
-// kernels (cdpr_step_kernel_f64.hpp), their read-out and the rollout by composition.  Reference paths as in cdpr_engine.hip.
+// cdpr_engine_f64.hip - host side of cdpr_config_t.precision = 64: the handle's set-up (build_f64), the fp64 step kernels' path of the
+// launch chain (cdpr_step_kernel_f64.hpp), their read-out and the rollout by composition.  Reference paths as in cdpr_engine.hip.
 #include "cdpr_engine_internal.hpp"
 
 namespace cdpr_host {
@@ -132,7 +132,7 @@ static F64Kernel f64_kernel_for(const cdpr_engine* h, const PlannedKernel& q) {
 }
 
 // precision = 64: the same host logic (commands are latched by run_steps before this is reached), the fp64 kernel
-int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, double* record) {
+int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, void* record) {
   const uint32_t n = h->n;
   if (reset_pid && !h->plan.hold64) {  // Pid::reset (Pid.cpp:100-115): zero every controller row (hold branch live: the latch reset that Pid's own rows)
     h->pid_calls = 0;
@@ -143,8 +143,7 @@ int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, do
   const bool pr = h->plan.per_robot;
   const bool vel = pr || h->mode == kModeVelocity, frc = !pr && h->mode == kModeForce;
   f64_mode_args(h, vel, frc, a);
-  const size_t image64 = (size_t)f64_obs_rows((int)n) * h->stride;  // doubles per observable image
-  a.obs_step_stride = record ? image64 : 0;
+  a.obs_step_stride = record ? (size_t)f64_obs_rows((int)n) * h->stride : 0;  // doubles per observable image
   // the rings in LDS (64 KiB per wave at n = 8: two waves per CU) while the batch leaves CUs to spare
   const int ring_env = [] { const char* v = std::getenv("CDPR_F64_RING_LDS"); return v ? atoi(v) : -1; }();  // (read per call: A/B in one process)
   // ... and the structure-matrix rows too (112 KiB: one wave per CU) up to one workgroup per CU
@@ -157,29 +156,25 @@ int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, do
   LaunchShape s1 = launch_shape(h, 1), sk = launch_shape(h, 2);
   s1.f64_ring_lds = sk.f64_ring_lds = ring_env, s1.f64_jcache = sk.f64_jcache = jc_env, s1.f64_split = sk.f64_split = sp_env;
   const PlannedKernel pk1 = planned_kernel(h->plan, s1), pkk = planned_kernel(h->plan, sk);
-  auto f64_kernel_of = [&](const PlannedKernel& q) -> F64Kernel { return f64_kernel_for(h, q); };
   const bool split1 = pk1.id == KernelId::F64Split || pk1.id == KernelId::F64SplitHold;
-  F64Kernel split_kern = split1 ? f64_kernel_of(pk1) : nullptr;  // (per-robot handles: the one-wave kernel)
+  F64Kernel split_kern = split1 ? f64_kernel_for(h, pk1) : nullptr;  // (per-robot handles: the one-wave kernel)
   // up to one workgroup per CU the role-split kernel's one-step launches beat the one-wave kernel's multi-step ones
   // (14.4 against 20.8 us per step at one robot x 8, same bits): a fused update then runs as one-step launches
   const bool fused_as_single = pkk.id == KernelId::F64Split || pkk.id == KernelId::F64SplitHold;
   if (fused_as_single) per_launch = 1;
   PlannedKernel one_wave = pkk;  // the one-wave kernel of this handle (what a several-steps launch runs, or would run)
   if (fused_as_single) { LaunchShape so = sk; so.f64_split = 0; one_wave = planned_kernel(h->plan, so); }
-  F64Kernel kern = f64_kernel_of(one_wave);
-  int done = 0;
-  while (done < nsteps) {
-    const int k = std::min(per_launch, nsteps - done);
-    a.nsteps = k;
-    a.flags = pr ? 0u : (vel ? kFlagActualIsVelocity : (frc ? kFlagForceMode : 0u));
-    const bool first_world = (h->step == 0);
-    if (first_world) a.flags |= kFlagFirstWorldStep;
-    if (record) a.obs = record + (size_t)done * image64;
+  F64Kernel kern = f64_kernel_for(h, one_wave);
+  const uint32_t mode_flags = pr ? 0u : (vel ? kFlagActualIsVelocity : (frc ? kFlagForceMode : 0u));
+  return run_chain(h, nsteps, per_launch, record, h->d_obs64, [&](ChainStep& s) {
+    a.nsteps = s.k;
+    a.flags = mode_flags | s.first_flag;
+    if (s.record) a.obs = static_cast<double*>(s.record);
     a.pid_calls = sat_pid_calls(h->pid_calls);
     a.ring_slot = ring_slot_of(h->step, win64(h));
     a.step0 = (int)h->step;
-    a.publish_mask = publish_mask(h, k);
-    if (k == 1 && split_kern) {
+    a.publish_mask = s.publish_mask;
+    if (s.k == 1 && split_kern) {
       hipLaunchKernelGGL(split_kern, dim3((h->batch + 63u) / 64u), dim3(128), 0, h->stream, a);
       h->last_kernel = pk1;
     } else {
@@ -187,14 +182,8 @@ int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, do
       h->last_kernel = one_wave;
     }
     HIP_TRY(h, hipGetLastError());
-    ++h->launches;
-    h->step += (uint64_t)k;
-    if (!frc) h->pid_calls = sat_pid_calls(h->pid_calls + k - (first_world ? 1 : 0));  // (no Pid call in Force mode)
-    done += k;
-  }
-  if (record && h->cfg.publish_period == 0.0 && h->step > 1)  // keep cdpr_get_* consistent: latest image into the engine's own
-    HIP_TRY(h, hipMemcpyAsync(h->d_obs64, record + (size_t)(nsteps - 1) * image64, image64 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  return CDPR_OK;
+    return (int)CDPR_OK;
+  });
 }
 
 // rows [first_row, first_row + width) of a double row buffer -> robot-major host array (double, or float when as_float)

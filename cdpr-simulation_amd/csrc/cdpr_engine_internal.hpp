@@ -1,8 +1,9 @@
-// cdpr_engine_internal.hpp - what the translation units of the host side share: the owners of device and pinned memory (DevBuf,
-// PinnedBuf), the handle (struct cdpr_engine: its routing is h->plan and nothing else, its buffers are owner members that go with
-// it), the error macros and the helpers one unit defines and another calls.  Units: cdpr_engine.hip (create / destroy, the general
-// path's set-up, commands, the fp32 launch chains, read-out), cdpr_engine_f64.hip (precision = 64: set-up, launch chain, read-out),
-// cdpr_engine_rollout.hip (cdpr_rollout_velocity*), cdpr_engine_solvers.hip (cdpr_solve_ik / fk / td), cdpr_engine_reset.hip
+// cdpr_engine_internal.hpp - what the translation units of the host side share: the owners of device and pinned memory and of the
+// captured graphs (DevBuf, PinnedBuf, GraphCache), the handle (struct cdpr_engine: its routing is h->plan and nothing else, its
+// buffers are owner members that go with it), the error macros and the helpers one unit defines and another calls.  Units:
+// cdpr_engine.hip (create / destroy, the general path's set-up, the command setters, read-out, the extern "C" wrappers),
+// cdpr_engine_launch.hip (what turns "advance n world steps" into launches: the latch, the chain and its clock, the fp32 and
+// general paths, schedules), cdpr_engine_f64.hip (precision = 64: set-up, its path of the chain, read-out), cdpr_engine_rollout.hip (cdpr_rollout_velocity*), cdpr_engine_solvers.hip (cdpr_solve_ik / fk / td), cdpr_engine_reset.hip
 // (cdpr_reset_robots*), cdpr_engine_done.hip (cdpr_evaluate_done*, cdpr_reset_done_device, cdpr_get_episode_start).  Not installed, not part of the C-ABI (include/cdpr.h is).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -99,6 +100,52 @@ struct PinnedBuf {
   operator T*() const { return p; }
 };
 
+// ... and of the captured hipGraphs of a handle: chains of identical steady-state launches (run_steps), found again by what makes
+// two chains the same launches - kernel, command pointer, steps per launch, flags and the ring slot the chain starts from.
+struct GraphKey {
+  void* kern; const float* cmd; int steps_per_launch, start_slot; uint32_t flags;
+  bool operator==(const GraphKey& o) const { return kern == o.kern && cmd == o.cmd && steps_per_launch == o.steps_per_launch && start_slot == o.start_slot && flags == o.flags; }
+};
+struct GraphCache {
+  struct Entry { GraphKey key; hipGraph_t graph; hipGraphExec_t exec; };
+  std::vector<Entry> entries;  // oldest first; 32 at the most (two Joy buffers x a few ring positions x step counts)
+  GraphCache() = default;
+  GraphCache(const GraphCache&) = delete;
+  GraphCache& operator=(const GraphCache&) = delete;
+  ~GraphCache() { clear(); }
+  void evict(size_t count) {  // the `count` oldest
+    for (size_t i = 0; i < count; ++i) (void)hipGraphExecDestroy(entries[i].exec), (void)hipGraphDestroy(entries[i].graph);
+    entries.erase(entries.begin(), entries.begin() + count);
+  }
+  void clear() { evict(entries.size()); }
+  hipGraphExec_t find(const GraphKey& key) const {
+    for (const Entry& e : entries)
+      if (e.key == key) return e.exec;
+    return nullptr;
+  }
+  // What `launch_all` queues on `stream` (it says whether every launch took) as a graph under `key`.  The capture is ended on every
+  // path - the stream is never left capturing; a failure anywhere drops the partial graph and returns null: do not use graphs on
+  // this handle again.
+  template <typename Fn>
+  hipGraphExec_t capture(hipStream_t stream, const GraphKey& key, Fn&& launch_all) {
+    Entry e{key, nullptr, nullptr};
+    bool ok = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+    if (ok) {
+      const bool launched = launch_all();
+      ok = (hipStreamEndCapture(stream, &e.graph) == hipSuccess) && launched && e.graph;
+      if (ok && hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0) != hipSuccess) ok = false;
+      if (!ok && e.graph) (void)hipGraphDestroy(e.graph);
+    }
+    if (!ok) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    if (entries.size() >= 32) evict(1);
+    entries.push_back(e);
+    return e.exec;
+  }
+};
+
 // Everything one command kind owns.  The handle keeps one record per kind, cdpr_engine::cmd[], indexed by the ABI's
 // CDPR_COMMAND_VELOCITY / _POSITION / _FORCE (0, 1, 2); what differs between the kinds is kCmdKind below.
 struct CmdChannel {
@@ -157,8 +204,6 @@ struct cdpr_engine {
   DevBuf<float> d_geom;     // pair-interleaved cable geometry, staged in LDS by the kernel
   int pid_calls = 0;        // Pid::update calls since the last Pid reset (uniform over the batch)
   uint32_t persist_grid = 0;  // waves of a launch of the persistent one-wave kernel (plan.persist): SIMDs of the device
-  int sched_refresh = 0;            // cdpr_update_scheduled in progress: Joy batches per launch (StepArgs::sched_*)
-  const uint32_t* sched_ready = nullptr;
   PinnedBuf<uint32_t> h_fault;      // pinned, device-mapped status word: a schedule mailbox that never delivered (kernels OR bits into it)
   uint32_t* d_fault = nullptr;      // its device address
   // general controller path (hold branch, cascades, long windows): see cdpr_general_step.hpp
@@ -175,16 +220,7 @@ struct cdpr_engine {
   size_t roll64_cols = 0;
   DevBuf<float> d_roll_rec;      // MPC rollout on the general path: every trajectory's private copy of the records
   size_t roll_rec_cols = 0;      // columns d_roll_rec can hold
-  // hipGraph cache: chains of identical steady-state launches (see run_steps)
-  struct GraphEntry {
-    void* kern;
-    const float* cmd;
-    int steps_per_launch, launches, start_slot;
-    uint32_t flags;
-    hipGraph_t graph;
-    hipGraphExec_t exec;
-  };
-  std::vector<GraphEntry> graphs;
+  GraphCache graphs;          // chains of identical steady-state launches (run_steps)
   PlannedKernel last_kernel;  // what the last step launch ran on (cdpr_kernel_name)
   int last_variant = 0;       // ... and which instantiation of it (cdpr_debug_last_variant): 1 = the role-split kernel's steady-state controller wave
   bool split_steady = true;   // CDPR_SPLIT_STEADY=0: the role-split kernel always runs its generic instantiation
@@ -327,35 +363,87 @@ inline int sat_pid_calls(int calls) { return calls < kCallSat ? calls : kCallSat
 inline int ring_slot_of(uint64_t step) { return (int)((step + 8u) % (uint64_t)kWin); }
 inline int ring_slot_of(uint64_t step, int w) { return (int)((step + (uint64_t)(w - 2)) % (uint64_t)w); }
 
+// A cdpr_update_scheduled launch in progress (run_steps' last argument; null for a plain update): Joy batches `refresh` steps apart
+// read by the kernel itself (StepArgs::sched_*), their mailbox or null, the status word a mailbox that never delivers is reported to.
+struct Schedule { int refresh; const uint32_t* ready; uint32_t* fault; };
+
+// One pass of the launch chain (run_chain), as the path gets it.  The path fills its arguments, launches, and says what it queued
+// where that is not one launch of k steps (chunked launches; a graph replay consumes ten launches' worth).
+struct ChainStep {
+  int k;                  // world steps of this launch: min(per_launch, left)
+  int left;               // steps of the call not yet queued, this launch's included
+  uint32_t first_flag;    // kFlagFirstWorldStep at world step 0, else 0
+  uint64_t publish_mask;  // which of the k steps publish (bit j: world step h->step + j)
+  void* record;           // where this launch's first observable image goes, null without a record
+  int used, launches;     // out: world steps consumed, launches queued (k and 1 unless the path says otherwise)
+};
+
+// One observable image: fp32 handles n_obs float4 slot rows, precision = 64 handles f64_obs_rows(n) rows of doubles
+inline size_t image_bytes(const cdpr_engine* h) {
+  return h->plan.fp64 ? (size_t)f64_obs_rows((int)h->n) * h->stride * sizeof(double) : (size_t)h->n_obs * h->stride * sizeof(float4);
+}
+
 // cdpr_engine.hip
 int set_device(cdpr_engine* h);
 int drain_copy_stream(cdpr_engine* h);
 int check_fault(cdpr_engine* h);
 int checked(cdpr_engine* h, int rc);
 void biquad_coefficients(const cdpr_filter_params_t& f, double co[5]);  // a0 a1 a2 b1 b2
-double sim_time(uint64_t step, double dt);
-uint64_t publish_mask(cdpr_engine* h, int k);  // which of the next k world steps publish; advances prev_publish
-LaunchShape launch_shape(const cdpr_engine* h, int k, bool steady = false);
-StepKernel step_kernel_of(const cdpr_engine* h, const PlannedKernel& pk);
-StepKernel select_step_kernel(const cdpr_engine* h, int k, bool steady = false);
-uint32_t step_block_threads(const cdpr_engine* h, int k);
-void set_weight_row(const cdpr_engine* h, StepArgs& a);
+std::vector<float4> home_state(const cdpr_engine* h, uint32_t rows);
 void copy_pid(const StepArgs& src, StepArgs& dst);
 void copy_pid_alt(const StepArgs& src, PidSet& dst);
 GenCtl general_ctl(const cdpr_engine* h);
 int fetch_slots(cdpr_engine* h, const float4* dsrc, int nslots, std::vector<float4>& host);
+// cdpr_engine_launch.hip
+double sim_time(uint64_t step, double dt);
+LaunchShape launch_shape(const cdpr_engine* h, int k, bool steady = false, const Schedule* sched = nullptr);
+StepKernel step_kernel_of(const cdpr_engine* h, const PlannedKernel& pk);
+StepKernel select_step_kernel(const cdpr_engine* h, int k, bool steady = false);
+uint32_t step_block_threads(const cdpr_engine* h, int k);
+int warm_first_launch(cdpr_engine* h);
+uint64_t publish_mask(const cdpr_engine* h, int k, double& last);  // which of the next k world steps publish; `last`: the publish stamp after them
+void advance_clock(cdpr_engine* h, int k, int launches);            // k world steps were queued in `launches` launches
+int run_steps(cdpr_engine* h, int nsteps, int per_launch, void* record = nullptr, const Schedule* sched = nullptr);
+int scheduled_update(cdpr_engine* h, uint32_t kind, int nsteps, int refresh_steps, const float* d_commands, const uint32_t* d_ready, const uint8_t* d_masks,
+                     void* d_record, size_t record_bytes);
 // cdpr_engine_reset.hip
 int launch_reset(cdpr_engine* h, const uint8_t* d_mask, const float* d_pose, const float* d_twist);
 // cdpr_engine_f64.hip
 int build_f64(cdpr_engine* h);  // cdpr_create's part of a precision = 64 handle
 size_t state64_rows(const cdpr_engine* h);
 int upload_home64(cdpr_engine* h);
-int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, double* record = nullptr);
+int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, void* record);  // (its path of the chain; run_steps has latched the commands)
 int fetch_rows64(cdpr_engine* h, const double* rows, uint32_t first_row, uint32_t width, void* host_out, bool as_float);
 int fetch_observables64(cdpr_engine* h, void* position, void* velocity, void* effort, void* pose7, void* twist6, bool as_float);
 int set_platform_state64(cdpr_engine* h, const double* pose7, const double* twist6);
 int fetch_int_row64(cdpr_engine* h, uint32_t row, int32_t* out);
 void decode_image64_to_float(const cdpr_engine* h, const double* image, float* position, float* velocity, float* effort, float* pose7, float* twist6);
 int rollout_enqueue_f64(cdpr_engine* h, int samples, int horizon, const float* d_commands, const float* d_ref, float* d_cost);
+
+// The loop every path runs (fp32 and general: cdpr_engine_launch.hip, precision = 64: cdpr_engine_f64.hip): the steps of this launch,
+// the first-world-step flag, the record moved on by the images done, the publish mask; then the path fills and launches (`path`:
+// int(ChainStep&), an error code), the clock moves by what it consumed, and after the last launch the latest recorded image goes
+// into the handle's own observables (own_obs), which cdpr_get_* read.
+template <typename Path>
+int run_chain(cdpr_engine* h, int nsteps, int per_launch, void* record, void* own_obs, Path&& path) {
+  const size_t image = image_bytes(h);
+  int done = 0;
+  while (done < nsteps) {
+    ChainStep s{};
+    s.k = s.used = std::min(per_launch, nsteps - done);
+    s.left = nsteps - done;
+    s.launches = 1;
+    s.first_flag = (h->step == 0) ? kFlagFirstWorldStep : 0u;
+    s.record = record ? static_cast<char*>(record) + (size_t)done * image : nullptr;
+    double last;
+    s.publish_mask = publish_mask(h, s.k, last);
+    if (int rc = path(s)) return rc;
+    advance_clock(h, s.used, s.launches);
+    done += s.used;
+  }
+  if (record && h->cfg.publish_period == 0.0 && h->step > 1)  // keep cdpr_get_* consistent: latest image into the engine's own
+    HIP_TRY(h, hipMemcpyAsync(own_obs, static_cast<char*>(record) + (size_t)(nsteps - 1) * image, image, hipMemcpyDeviceToDevice, h->stream));
+  return CDPR_OK;
+}
 
 }  // namespace cdpr_host

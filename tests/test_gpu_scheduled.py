@@ -254,10 +254,35 @@ def test_mailbox_on_both_forms_and_a_mailbox_that_never_delivers(pkg, general):
         eng.synchronize()
     with pytest.raises(pkg.CdprError, match="mailbox timed out"):
         eng.joint_states()
+    with pytest.raises(pkg.CdprError, match="mailbox timed out"):
+        eng.observables()
     eng.reset()
     eng.update(3)
     eng.synchronize()
     assert np.isfinite(eng.platform_state()[0]).all()
+    eng.close()
+
+
+def test_a_mailbox_that_never_delivers_is_reported_by_the_large_read_out_tier(pkg):
+    """cdpr_get_observables has three tiers by image size; the largest (above 2 MiB: copies straight into the caller's arrays) reports a
+    timed-out mailbox like the other two (include/cdpr.h: every getter returns CDPR_ERR_DEVICE until cdpr_reset).  A general-path
+    handle waits in the one-thread mailbox kernel, so the wait does not grow with the batch: 21 056 robots x 4 cables hand out
+    3 * 4 + 13 = 25 floats per robot, 2 105 600 bytes, just above 2 MiB = 2 097 152."""
+    B, T, refresh = 21056, 40, 10
+    assert B * 25 * 4 > (2 << 20)
+    cfg = pkg.Config(batch=B, velocityEpsilon=0.001)
+    sched = np.random.default_rng(14).uniform(-0.03, 0.03, (T // refresh, B, 4)).astype(np.float32)
+    eng = pkg.Engine(cfg, 0)
+    eng.update(5)
+    d_sched = eng.device_upload(sched)
+    d_ready = eng.device_upload(np.array([1, 0, 1, 1], np.uint32))  # batch 1 never arrives
+    eng.update_scheduled(T, refresh, d_sched, d_ready=d_ready)
+    with pytest.raises(pkg.CdprError, match="mailbox timed out"):
+        eng.observables()
+    eng.reset()
+    eng.update(3)
+    assert all(np.isfinite(x).all() for x in eng.observables())
+    eng.device_free(d_sched), eng.device_free(d_ready)
     eng.close()
 
 
