@@ -93,13 +93,19 @@ static bool pair_stream_steady(const cdpr_engine* h, const StepArgs& a, const Sc
   return h->step != 0 && h->mode != kModeForce && a.pid_calls >= a.nbuf && h->cfg.publish_period == 0.0 && !a.dbg && !a.travel_on &&
          !(a.vel_limit > 0.f) && !a.unilateral && a.effort >= 0.f && a.clamp_cmd && !(sched && sched->ready);
 }
-// May a launch of the role-split kernel with the arguments `a` take the controller wave's steady-state instantiation
-// (split_controller_wave<N, false, true, VEL>, cdpr_onestep_kernel.hpp)?  It has no code for anything the generic one tests per launch
-// and these facts decide: a uniform handle in Velocity or Position mode, past world step 0, the derivative window full, every step
-// published, no `pid` topic, no travel flags.  CDPR_SPLIT_STEADY=0: never (A/B, tests).  Same bits either way (tested).
+// Can the handle's role-split launches ever take the steady-state kernel (cdpr_split_steady_kernel<N, VEL>, cdpr_onestep_kernel.hpp)?  What
+// does not change over the handle's life: a uniform handle, every step published, and the estimator wave's contract - its Newton stage is
+// four iterations written out without a convergence test, which is the generic loop exactly for a tolerance of 0 and 4 iterations.
+// CDPR_SPLIT_STEADY=0: never (A/B, tests).
+static bool split_steady_handle(const cdpr_engine* h) {
+  return h->split_steady && !h->plan.per_robot && h->cfg.publish_period == 0.0 && h->cfg.fk_tolerance == 0.0 && h->cfg.fk_max_iterations == 4;
+}
+// May a launch of the role-split kernel with the arguments `a` take it?  The steady kernel has no code for anything the generic one
+// tests per launch and these facts decide: such a handle in Velocity or Position mode, past world step 0, the derivative window full,
+// no `pid` topic, no travel flags.  Same bits either way (tested).
 static bool split_steady_launch(const cdpr_engine* h, const PlannedKernel& pk, const StepArgs& a) {
-  return pk.id == KernelId::Split && h->split_steady && !h->plan.per_robot && h->step != 0 && h->mode != kModeForce && a.pid_calls != 0 &&
-         a.pid_calls >= a.nbuf && h->cfg.publish_period == 0.0 && !a.dbg && !a.travel_on;
+  return pk.id == KernelId::Split && split_steady_handle(h) && h->step != 0 && h->mode != kModeForce && a.pid_calls != 0 &&
+         a.pid_calls >= a.nbuf && !a.dbg && !a.travel_on;
 }
 uint32_t step_block_threads(const cdpr_engine* h, int k) { return planned_kernel(h->plan, launch_shape(h, k)).block; }
 
@@ -180,7 +186,7 @@ int warm_first_launch(cdpr_engine* h) {
   HIP_TRY(h, hipGetLastError());
   // ... and of the role-split kernel's steady-state instantiations, which the launches take from the step on that fills the window
   // (split_steady_launch): both modes' - a Joy of the other kind may arrive at any step
-  if (planned_kernel(h->plan, launch_shape(h, 1)).id == KernelId::Split && h->split_steady) {
+  if (planned_kernel(h->plan, launch_shape(h, 1)).id == KernelId::Split && split_steady_handle(h)) {
     for (const bool vel : {false, true}) {
       copy_pid(vel ? h->pid_vel : h->pid_pos, a);
       hipLaunchKernelGGL(pick_split_steady_kernel(h->n, vel), dim3(1), dim3(128), 0, h->stream, a);

@@ -501,6 +501,13 @@ __global__ __launch_bounds__(64, 1) void cdpr_onestep_kernel(const StepArgs a_in
 #ifndef CDPR_SPLIT_PRIO
 #define CDPR_SPLIT_PRIO 1  // 1 = estimator wave at s_setprio 3 (measured 10.89 vs 11.05 us/step), 2 = controller wave at 3 (11.7), 0 = none
 #endif
+#ifndef CDPR_STEADY_SHARED_IK
+#define CDPR_STEADY_SHARED_IK 1  // 1 = the steady kernel evaluates the true-state IK once per robot (estimator wave, rows through LDS); 0 = both waves do
+#endif
+#ifndef CDPR_STEADY_NEWTON_WRITTEN_OUT
+#define CDPR_STEADY_NEWTON_WRITTEN_OUT 1  // 1 = the steady kernel's Newton stage is four iterations written out; 0 = the generic loop (A/B of the two items)
+#endif
+constexpr int kIkRows = 7;  // v2f rows per cable pair of that hand-over: L, u (3), (R b) x u (3)
 #ifdef CDPR_STAMPS
 #define CDPR_SPLIT_STAMP(i)                                                                                          \
   do {                                                                                                               \
@@ -521,9 +528,25 @@ __global__ __launch_bounds__(64, 1) void cdpr_onestep_kernel(const StepArgs a_in
 // -> tensions and estimator results back.  x_force / x_tension: v2f rows XS elements apart, x_est: float rows ES apart.
 // RAISED: this wave at raised issue priority (the fast path's kernel: its chain is the launch's; the general kernels, whose controller
 // wave is the longer one, pass their own choice)
-template <int N, int XS, int ES, bool RAISED = true>
+//
+// STEADY: the estimator half of cdpr_split_steady_kernel, for launches of which the host knows (split_steady_launch, cdpr_engine_launch.hip)
+// besides the controller wave's facts that fk_tol == 0 and fk_iters == 4.  Every floating-point operation is the generic instantiation's, in
+// its order and on its operands (same device functions, same bits: tested); two things differ.
+//  1. The Newton stage is four iterations written out.  With a tolerance of 0 the generic loop's `active && !(rm < fk_tol)` is true for every
+//     residual, NaN included: every lane moves and counts in every iteration, so the residual maximum inside the iterations, the mask
+//     around the pose update and the counter (4) are gone.  The closing evaluation and fk_res stay.
+//  2. (CDPR_STEADY_SHARED_IK) The IK rows at the true state are evaluated ONCE per robot, here: lengths, unit vectors and (R b) x u of
+//     every pair go to x_ik (kIkRows v2f rows per pair, 64 lanes each) and this wave passes workgroup barrier #0.  The controller wave
+//     issues its row loads, goes to #0 (it is there first: this wave does not wait) and reads the rows instead of calling ik_pairs; L0
+//     comes from its geometry table.  The generic kernel evaluates them in both waves (the estimator needs the lengths only, so the
+//     compiler drops its unit vectors and cross products there).
+// Static counts of both waves, before and after: scripts/split_ctl_counts.py, profiles/r11_split_est_instruction_counts.txt.
+// Measured per item (profiles/r11_headline_steady_estimator_ab.txt): 2 is the gain; 1 ALONE is no faster than the generic loop (the compiler then
+// moves the tension distribution's factor behind barrier #1) and worth 0.1 us per step on top of 2.
+template <int N, int XS, int ES, bool RAISED = true, bool STEADY = false>
 CDPR_DEV void split_estimator_wave(const StepArgs& a, float* geo, float gval, uint32_t lane, bool live, size_t st, uint32_t off, uint32_t woff,
-                                   const float4& p0, const float4& p1, const float4& p3, const v2f* x_force, v2f* x_tension, float* x_est) {
+                                   const float4& p0, const float4& p1, const float4& p3, const v2f* x_force, v2f* x_tension, float* x_est,
+                                   v2f* x_ik = nullptr) {
   constexpr int NP = cable_pairs(N);
 #if defined(CDPR_STAMPS) && defined(CDPR_STAMPS_CLOCK)  // the shader clock over this wave: s_memtime ticks between entry and stamp 3, into slot 7
   const unsigned long long clk0 = __builtin_amdgcn_s_memtime();
@@ -543,41 +566,80 @@ CDPR_DEV void split_estimator_wave(const StepArgs& a, float* geo, float gval, ui
   {
     v2f jac[NP][6], l0[NP];  // only the measured lengths L* are kept of the true-state evaluation
     ik_pairs<N, false>(geo, p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, len, jac, l0);
+    if (STEADY && CDPR_STEADY_SHARED_IK) {  // ... and the whole of it goes to the controller wave, which evaluates none itself
+#pragma unroll
+      for (int k = 0; k < NP; ++k) {
+        x_ik[(kIkRows * k) * 64 + lane] = len[k];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) x_ik[(kIkRows * k + 1 + c) * 64 + lane] = jac[k][c];
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the rows are in LDS
+      __builtin_amdgcn_s_barrier();        // #0: the controller wave is here already (it has only issued its row loads)
+    }
   }
   float fk_res = 0.f;
   int fk_it = 0;
   v2f jest[NP][6];
   {
     v2f elen[NP], unused[NP];
-    bool active = true;
-    for (int it = 0; it < a.fk_iters; ++it) {
-      ik_pairs<N, false>(geo, fkx, fky, fkz, fkqx, fkqy, fkqz, fkqw, elen, jest, unused);
-      v2f res[NP];
-      v2f rm = splat(0.f);
+    if (STEADY && CDPR_STEADY_NEWTON_WRITTEN_OUT) {
+      // fk_tol == 0 and fk_iters == 4 (split_steady_launch): `!(rm < 0)` holds for every residual, NaN included, so every lane moves
+      // and counts in every iteration - the four iterations written out, without the test, the mask and the counter
 #pragma unroll
-      for (int k = 0; k < NP; ++k) {
-        res[k] = len[k] - elen[k];
-        rm = max2(rm, abs2(res[k]));
-      }
-      active = active && !(fmaxf(rm.x, rm.y) < a.fk_tol);
-      float g[6];
-      jt_times<NP>(jest, res, g);
-      normal_solve<NP>(jest, a.fk_lambda, g);
-      if (active) {
+      for (int it = 0; it < 4; ++it) {
+        ik_pairs<N, false>(geo, fkx, fky, fkz, fkqx, fkqy, fkqz, fkqw, elen, jest, unused);
+        v2f res[NP];
+#pragma unroll
+        for (int k = 0; k < NP; ++k) res[k] = len[k] - elen[k];
+        float g[6];
+        jt_times<NP>(jest, res, g);
+        normal_solve<NP>(jest, a.fk_lambda, g);
         fkx += g[0];
         fky += g[1];
         fkz += g[2];
         quat_apply_rotvec(fkqx, fkqy, fkqz, fkqw, g[3], g[4], g[5]);
-        ++fk_it;
-      }
 #ifdef CDPR_STAMPS_ITER
-      if (it < 3) {
-        asm volatile("" ::"v"(fkqw));
-        __builtin_amdgcn_sched_barrier(0);
-        if (a.stamps && lane == 0) a.stamps[(size_t)blockIdx.x * 8 + 4 + it] = __builtin_amdgcn_s_memrealtime();
-        __builtin_amdgcn_sched_barrier(0);
-      }
+        if (it < 3) {
+          asm volatile("" ::"v"(fkqw));
+          __builtin_amdgcn_sched_barrier(0);
+          if (a.stamps && lane == 0) a.stamps[(size_t)blockIdx.x * 8 + 4 + it] = __builtin_amdgcn_s_memrealtime();
+          __builtin_amdgcn_sched_barrier(0);
+        }
 #endif
+      }
+      fk_it = 4;
+    } else {
+      bool active = true;
+      for (int it = 0; it < a.fk_iters; ++it) {
+        ik_pairs<N, false>(geo, fkx, fky, fkz, fkqx, fkqy, fkqz, fkqw, elen, jest, unused);
+        v2f res[NP];
+        v2f rm = splat(0.f);
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+          res[k] = len[k] - elen[k];
+          rm = max2(rm, abs2(res[k]));
+        }
+        active = active && !(fmaxf(rm.x, rm.y) < a.fk_tol);
+        float g[6];
+        jt_times<NP>(jest, res, g);
+        normal_solve<NP>(jest, a.fk_lambda, g);
+        if (active) {
+          fkx += g[0];
+          fky += g[1];
+          fkz += g[2];
+          quat_apply_rotvec(fkqx, fkqy, fkqz, fkqw, g[3], g[4], g[5]);
+          ++fk_it;
+        }
+#ifdef CDPR_STAMPS_ITER
+        if (it < 3) {
+          asm volatile("" ::"v"(fkqw));
+          __builtin_amdgcn_sched_barrier(0);
+          if (a.stamps && lane == 0) a.stamps[(size_t)blockIdx.x * 8 + 4 + it] = __builtin_amdgcn_s_memrealtime();
+          __builtin_amdgcn_sched_barrier(0);
+        }
+#endif
+      }
     }
     ik_pairs<N, false>(geo, fkx, fky, fkz, fkqx, fkqy, fkqz, fkqw, elen, jest, unused);
     v2f rm = splat(0.f);
@@ -652,7 +714,7 @@ CDPR_DEV void split_estimator_wave(const StepArgs& a, float* geo, float gval, ui
 template <int N, bool PR, bool STEADY, bool VEL>
 CDPR_DEV void split_controller_wave(const StepArgs& a, float* geo, float gval, uint32_t lane, uint32_t r, uint32_t rr, bool live, size_t st, uint32_t off,
                                     uint32_t woff, const float4& p0, const float4& p1, const float4& p2, const float4& p3, v2f* x_force, const v2f* x_tension,
-                                    const float* x_est) {
+                                    const float* x_est, const v2f* x_ik = nullptr) {
   static_assert(!(STEADY && PR), "the steady instantiation serves uniform handles");
   constexpr int NP = cable_pairs(N);
   constexpr int P = plat_slots(true);
@@ -704,7 +766,19 @@ CDPR_DEV void split_controller_wave(const StepArgs& a, float* geo, float gval, u
   v2f len[NP], q[NP], qd[NP], jac[NP][6];
   {
     v2f l0[NP];
-    ik_pairs<N, true>(geo, s.px, s.py, s.pz, s.qx, s.qy, s.qz, s.qw, len, jac, l0);
+    if (STEADY && CDPR_STEADY_SHARED_IK) {  // the estimator wave's rows (same function, same operands: same bits), L0 from the geometry table
+      __builtin_amdgcn_s_barrier();         // #0: reached with nothing but the row loads issued, so the estimator wave never waits here
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#pragma unroll
+      for (int k = 0; k < NP; ++k) {
+        len[k] = x_ik[(kIkRows * k) * 64 + lane];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) jac[k][c] = x_ik[(kIkRows * k + 1 + c) * 64 + lane];
+        l0[k] = *reinterpret_cast<const v2f*>(geo + k * kGeomFloatsPerPair + 12);
+      }
+    } else {
+      ik_pairs<N, true>(geo, s.px, s.py, s.pz, s.qx, s.qy, s.qz, s.qw, len, jac, l0);
+    }
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
       q[k] = l0[k] - len[k];
@@ -847,7 +921,8 @@ CDPR_DEV void split_controller_wave(const StepArgs& a, float* geo, float gval, u
 
 // PR = true: per-robot handles (StepArgs::meta, see cdpr_step_kernel.hpp): the controller wave takes mode and Pid call
 // count per lane; the estimator wave is the same.
-// (the kernel's body: cdpr_split_kernel<N, PR> and cdpr_split_steady_kernel<N, VEL> below differ in the controller wave's instantiation only)
+// (the kernel's body: cdpr_split_kernel<N, PR> and cdpr_split_steady_kernel<N, VEL> below differ in the two waves' STEADY instantiations and
+// in the LDS rows of the shared IK, which only the steady kernel has)
 template <int N, bool PR, bool STEADY, bool VEL>
 CDPR_DEV void split_kernel_body(const StepArgs& a) {
   constexpr int NP = cable_pairs(N);
@@ -855,6 +930,11 @@ CDPR_DEV void split_kernel_body(const StepArgs& a) {
   __shared__ v2f x_force[NP][64];      // controller -> estimator: raw per-cable forces
   __shared__ v2f x_tension[NP][64];    // estimator -> controller: distributed tensions (before the SetForce limits)
   __shared__ float x_est[6][64];       // estimator -> controller: fk x y z, residual, iterations, infeasible flag
+  v2f* x_ik = nullptr;                 // estimator -> controller, steady kernel only: the IK rows at the true state (14 KiB at n = 8)
+  if constexpr (STEADY && CDPR_STEADY_SHARED_IK) {
+    __shared__ v2f ik_rows_at_state[kIkRows * NP][64];
+    x_ik = &ik_rows_at_state[0][0];
+  }
 
   // which of the two waves estimates: swapped from workgroup to workgroup (bits of the workgroup index chosen by the
   // host, StepArgs::split_swap) so that the two waves a SIMD hosts tend to be one of each role
@@ -877,15 +957,15 @@ CDPR_DEV void split_kernel_body(const StepArgs& a) {
   const float4 p0 = load_slot(a.state, st, 0, off), p1 = load_slot(a.state, st, 1, off), p2 = load_slot(a.state, st, 2, off),
                p3 = load_slot(a.state, st, 3, off);
   if (wave == 0) {
-    split_estimator_wave<N, 64, 64>(a, geo, gval, lane, live, st, off, woff, p0, p1, p3, &x_force[0][0], &x_tension[0][0], &x_est[0][0]);
+    split_estimator_wave<N, 64, 64, true, STEADY>(a, geo, gval, lane, live, st, off, woff, p0, p1, p3, &x_force[0][0], &x_tension[0][0], &x_est[0][0], x_ik);
     return;
   }
-  split_controller_wave<N, PR, STEADY, VEL>(a, geo, gval, lane, r, rr, live, st, off, woff, p0, p1, p2, p3, &x_force[0][0], &x_tension[0][0], &x_est[0][0]);
+  split_controller_wave<N, PR, STEADY, VEL>(a, geo, gval, lane, r, rr, live, st, off, woff, p0, p1, p2, p3, &x_force[0][0], &x_tension[0][0], &x_est[0][0], x_ik);
 }
 template <int N, bool PR = false>
 __global__ __launch_bounds__(128, 2) void cdpr_split_kernel(const StepArgs a) { split_kernel_body<N, PR, false, false>(a); }
-// The same kernel with the controller wave's steady-state instantiation (split_controller_wave<N, false, true, VEL>): the host's choice
-// per launch (split_steady_launch, cdpr_engine.hip), reported under cdpr_split_kernel<N, false>'s name by cdpr_kernel_name.
+// The same kernel with both waves' steady-state instantiations (split_controller_wave<N, false, true, VEL>, split_estimator_wave<..., true>):
+// the host's choice per launch (split_steady_launch, cdpr_engine_launch.hip), reported under cdpr_split_kernel<N, false>'s name by cdpr_kernel_name.
 template <int N, bool VEL>
 __global__ __launch_bounds__(128, 2) void cdpr_split_steady_kernel(const StepArgs a) { split_kernel_body<N, false, true, VEL>(a); }
 
