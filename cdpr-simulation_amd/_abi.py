@@ -28,6 +28,11 @@ STAGE_PID_DEBUG = 0x4
 DONE_NONFINITE, DONE_WORKSPACE, DONE_TILT, DONE_SPEED, DONE_RATE, DONE_FK_RESIDUAL, DONE_INFEASIBLE, DONE_TRAVEL, DONE_TIMEOUT = (1 << k for k in range(9))
 DONE_COUNTS = 16  # counts[0] = robots done, counts[1 + k] = robots with reason bit k
 
+# cdpr_env_spec_t.fields / cdpr_observe_device: the columns of the observation tensor, in bit order (n = cables)
+OBS_POSE, OBS_TWIST, OBS_JOINT_POSITION, OBS_JOINT_VELOCITY, OBS_EFFORT, OBS_FK_POSE, OBS_FK_RESIDUAL, OBS_AGE = (1 << k for k in range(8))
+OBS_ALL = 0xFF
+OBS_NEED_FK = OBS_FK_POSE | OBS_FK_RESIDUAL  # fields only a STAGE_FK handle serves
+
 PLAN_FIRST_WORLD_STEP, PLAN_SCHEDULED, PLAN_ROLLOUT, PLAN_NOT_STEADY = 1, 2, 4, 8  # cdpr_plan_kernel flags
 MAP_AUTO = 0
 MAP_LANE_PER_ROBOT = 1
@@ -109,3 +114,35 @@ class DoneRuleStruct(C.Structure):
         ("max_steps", C.c_uint32),
         ("reserved_", C.c_uint32),
     ]
+
+
+class EnvSpec(C.Structure):
+    """cdpr_env_spec_t: what Engine.env_evaluate[_device] computes.  fields: OBS_* bits of the observation tensor, ld: floats per row of
+    it (0 = packed); the reward's weights, `alive` and `done_penalty` (float32); `done`: the rule of the verdict (a DoneRuleStruct, or
+    anything with to_struct() such as config.DoneRule).  struct_size is filled in."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("fields", C.c_uint32),
+        ("ld", C.c_uint32),
+        ("reserved_", C.c_uint32),
+        ("w_position", C.c_float),
+        ("w_orientation", C.c_float),
+        ("w_speed", C.c_float),
+        ("w_rate", C.c_float),
+        ("w_effort", C.c_float),
+        ("w_fk_residual", C.c_float),
+        ("alive", C.c_float),
+        ("done_penalty", C.c_float),
+        ("done", DoneRuleStruct),
+    ]
+    WEIGHTS = ("w_position", "w_orientation", "w_speed", "w_rate", "w_effort", "w_fk_residual")  # the order the reward applies them in
+
+    def __init__(self, done=None, **kw):
+        super().__init__(**kw)
+        self.struct_size = C.sizeof(EnvSpec)
+        rule = done.to_struct() if hasattr(done, "to_struct") else done
+        if rule is None:
+            rule = DoneRuleStruct()
+            rule.struct_size = C.sizeof(DoneRuleStruct)
+        self.done = rule

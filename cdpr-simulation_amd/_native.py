@@ -17,6 +17,7 @@ EXPORTS = [
     "cdpr_abi_version", "cdpr_config_size", "cdpr_device_count", "cdpr_device_pci_bus_id", "cdpr_bytes_per_state_step", "cdpr_derivative_weights",
     "cdpr_create", "cdpr_destroy", "cdpr_reset", "cdpr_last_error", "cdpr_set_platform_state", "cdpr_reset_robots", "cdpr_reset_robots_device",
     "cdpr_done_rule_size", "cdpr_evaluate_done_device", "cdpr_evaluate_done", "cdpr_reset_done_device", "cdpr_get_episode_start",
+    "cdpr_env_spec_size", "cdpr_observation_width", "cdpr_observe_device", "cdpr_env_evaluate_device",
     "cdpr_set_velocity_command", "cdpr_set_position_command", "cdpr_set_velocity_command_device",
     "cdpr_set_position_command_device", "cdpr_bind_velocity_command_device", "cdpr_bind_position_command_device",
     "cdpr_set_velocity_command_masked", "cdpr_set_position_command_masked", "cdpr_set_force_command", "cdpr_set_force_command_device",
@@ -70,6 +71,13 @@ def lib():
     L.cdpr_evaluate_done.argtypes = [H, rulep, u8p, u32p, u32p]
     L.cdpr_reset_done_device.argtypes = [H, rulep, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cdpr_get_episode_start.argtypes = [H, u32p]
+    # the environment view came after ABI 8 as new exports only: a build of ABI 8 without it (CDPR_LIB: A/B runs against an older
+    # library) still loads, and a caller finds out by the symbol
+    if hasattr(L, "cdpr_env_spec_size"):
+        L.cdpr_env_spec_size.restype = C.c_size_t
+        L.cdpr_observation_width.argtypes = [H, C.c_uint32, u32p]
+        L.cdpr_observe_device.argtypes = [H, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.cdpr_env_evaluate_device.argtypes = [H, C.POINTER(_abi.EnvSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in ("cdpr_set_velocity_command", "cdpr_set_position_command", "cdpr_set_force_command"):
         getattr(L, name).argtypes = [H, fp, C.c_size_t]
     for name in ("cdpr_set_velocity_command_device", "cdpr_set_position_command_device", "cdpr_bind_velocity_command_device",
@@ -122,5 +130,7 @@ def lib():
         raise ImportError("cdpr_config_t layout mismatch between include/cdpr.h and _abi.py")
     if L.cdpr_done_rule_size() != C.sizeof(_abi.DoneRuleStruct):
         raise ImportError("cdpr_done_rule_t layout mismatch between include/cdpr.h and _abi.py")
+    if hasattr(L, "cdpr_env_spec_size") and L.cdpr_env_spec_size() != C.sizeof(_abi.EnvSpec):
+        raise ImportError("cdpr_env_spec_t layout mismatch between include/cdpr.h and _abi.py")
     _lib = L
     return L

@@ -88,6 +88,7 @@ CDPR_DEV void done_store(const DoneOut& o, uint32_t enable, uint32_t r, bool liv
   }
 }
 
+#ifndef CDPR_DONE_NO_KERNELS  // (cdpr_env.hpp takes done_reason and done_store and leaves the two kernels to cdpr_engine_done.hip)
 // fp32 handles, both controller paths: state slots 0-3 = [x y z qx | qy qz qw vx | vy vz wx wy | wz ...], observable slot 3 =
 // [wz | fk residual | fk iterations | flags] of the last published step
 struct DoneArgs {
@@ -148,5 +149,6 @@ static __global__ __launch_bounds__(256) void cdpr_done_f64_kernel(const DoneF64
   s.age = a.step - a.episode_start[c];
   done_store(a.out, a.rule.enable, r, live, done_reason(a.rule, s));
 }
+#endif  // CDPR_DONE_NO_KERNELS
 
 }  // namespace cdpr

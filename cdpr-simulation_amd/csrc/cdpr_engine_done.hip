@@ -7,7 +7,8 @@
 
 namespace cdpr_host {
 
-static int done_checks(cdpr_engine* h, const cdpr_done_rule_t* rule, const char* what) {
+// (also what cdpr_env_evaluate_device refuses of its spec's rule: cdpr_engine_env.hip)
+int done_checks(cdpr_engine* h, const cdpr_done_rule_t* rule, const char* what) {
   if (!rule) {
     h->err = std::string(what) + ": null rule";
     return CDPR_ERR_INVALID;
@@ -32,6 +33,12 @@ struct DoneScratch {
   size_t off_reason, off_counts, bytes;
   explicit DoneScratch(size_t B) : off_reason((B + 15u) & ~(size_t)15u), off_counts(off_reason + B * sizeof(uint32_t)), bytes(off_counts + CDPR_DONE_COUNTS * sizeof(uint32_t)) {}
 };
+
+// ... allocated at its first use; its mask also serves cdpr_env_evaluate_device where the caller wants a reason or counts without one
+int ensure_done_scratch(cdpr_engine* h) {
+  if (!h->d_done) HIP_TRY(h, h->d_done.alloc(DoneScratch(h->batch).bytes));
+  return CDPR_OK;
+}
 
 // Queue the verdict behind every update queued so far: d_mask uint8[B], d_reason uint32[B] or null, d_counts uint32[CDPR_DONE_COUNTS]
 // or null (zeroed on the stream first).  The step count goes in by value, as into the step kernels.
@@ -82,7 +89,7 @@ int cdpr_evaluate_done(cdpr_handle_t h, const cdpr_done_rule_t* rule, uint8_t* m
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
   const size_t B = h->batch;
   const DoneScratch s(B);
-  if (!h->d_done) HIP_TRY(h, h->d_done.alloc(s.bytes));
+  if (int rc = ensure_done_scratch(h)) return rc;
   char* const d = h->d_done;
   if (int rc = launch_done(h, *rule, reinterpret_cast<uint8_t*>(d), reinterpret_cast<uint32_t*>(d + s.off_reason), reinterpret_cast<uint32_t*>(d + s.off_counts))) return rc;
   if (mask) HIP_TRY(h, hipMemcpyAsync(mask, d, B, hipMemcpyDeviceToHost, h->stream));
@@ -100,7 +107,7 @@ int cdpr_reset_done_device(cdpr_handle_t h, const cdpr_done_rule_t* rule, const 
     return CDPR_ERR_UNSUPPORTED;
   }
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  if (!h->d_done) HIP_TRY(h, h->d_done.alloc(DoneScratch(h->batch).bytes));
+  if (int rc = ensure_done_scratch(h)) return rc;
   uint8_t* const d_mask = reinterpret_cast<uint8_t*>(h->d_done.p);
   if (int rc = launch_done(h, *rule, d_mask, nullptr, d_counts)) return rc;
   return launch_reset(h, d_mask, d_pose7, d_twist6);  // stream-ordered behind the verdict: no host wait in between

@@ -4,7 +4,8 @@
 // cdpr_engine.hip (create / destroy, the general path's set-up, the command setters, read-out, the extern "C" wrappers),
 // cdpr_engine_launch.hip (what turns "advance n world steps" into launches: the latch, the chain and its clock, the fp32 and
 // general paths, schedules), cdpr_engine_f64.hip (precision = 64: set-up, its path of the chain, read-out), cdpr_engine_rollout.hip (cdpr_rollout_velocity*), cdpr_engine_solvers.hip (cdpr_solve_ik / fk / td), cdpr_engine_reset.hip
-// (cdpr_reset_robots*), cdpr_engine_done.hip (cdpr_evaluate_done*, cdpr_reset_done_device, cdpr_get_episode_start).  Not installed, not part of the C-ABI (include/cdpr.h is).
+// (cdpr_reset_robots*), cdpr_engine_done.hip (cdpr_evaluate_done*, cdpr_reset_done_device, cdpr_get_episode_start), cdpr_engine_env.hip (cdpr_observe_device,
+// cdpr_env_evaluate_device, cdpr_observation_width).  Not installed, not part of the C-ABI (include/cdpr.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -408,6 +409,9 @@ int scheduled_update(cdpr_engine* h, uint32_t kind, int nsteps, int refresh_step
                      void* d_record, size_t record_bytes);
 // cdpr_engine_reset.hip
 int launch_reset(cdpr_engine* h, const uint8_t* d_mask, const float* d_pose, const float* d_twist);
+// cdpr_engine_done.hip
+int done_checks(cdpr_engine* h, const cdpr_done_rule_t* rule, const char* what);  // what every call refuses of a done rule
+int ensure_done_scratch(cdpr_engine* h);                                          // h->d_done: [mask | reason | counts]
 // cdpr_engine_f64.hip
 int build_f64(cdpr_engine* h);  // cdpr_create's part of a precision = 64 handle
 size_t state64_rows(const cdpr_engine* h);

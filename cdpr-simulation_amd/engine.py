@@ -42,6 +42,14 @@ def plan_kernel(config: Config, steps_per_launch: int = 1, flags: int = 0) -> st
     return buf.value.decode()
 
 
+def observation_width(fields: int, n: int) -> int:
+    """Columns of the observation tensor for the _abi.OBS_* bits `fields` on a robot of n cables (cdpr_observation_width's arithmetic:
+    7, 6, n, n, n, 7, 1, 1 per field, in bit order)."""
+    if fields & ~_abi.OBS_ALL:
+        raise ValueError("unknown OBS_* bit")
+    return sum(w for k, w in enumerate((7, 6, n, n, n, 7, 1, 1)) if (fields >> k) & 1)
+
+
 class Engine:
     """B independent robots advanced in lock step on one GPU."""
 
@@ -144,6 +152,66 @@ class Engine:
         start = np.empty(self.B, dtype=np.uint32)
         self._check(lib().cdpr_get_episode_start(self._h, start.ctypes.data_as(C.POINTER(C.c_uint32))))
         return start
+
+    # -- the environment view: observation tensor, reward and verdict where the state is
+    def observation_width(self, fields: int) -> int:
+        """Columns of the observation tensor for the _abi.OBS_* bits `fields` on this handle (cdpr_observation_width)."""
+        w = C.c_uint32()
+        self._check(lib().cdpr_observation_width(self._h, int(fields), C.byref(w)))
+        return int(w.value)
+
+    def observe_device(self, fields: int, d_obs: int, ld: int = 0, d_row_mask: int = 0) -> None:
+        """The observation tensor float[B][ld] (ld = 0: packed) into the device buffer d_obs, queued on the engine's stream, nothing copied
+        back or waited for (cdpr_observe_device).  Column j of robot b is to the bit what the field's getter returns.  d_row_mask: device
+        uint8[B], only the rows with a non-zero byte are written (after reset_robots_device(mask): the done robots' fresh observation)."""
+        self._check(lib().cdpr_observe_device(self._h, int(fields), int(ld), C.c_void_p(d_row_mask) if d_row_mask else None, C.c_void_p(d_obs) if d_obs else None))
+
+    def env_evaluate_device(self, spec: _abi.EnvSpec, d_target7: int = 0, d_obs: int = 0, d_reward: int = 0, d_mask: int = 0, d_reason: int = 0, d_counts: int = 0) -> None:
+        """Observation (float[B][spec.ld]), tracking reward (float[B]) and the verdict of spec.done (as evaluate_done_device) in one launch
+        into device buffers; 0 = not wanted, not all of them (cdpr_env_evaluate_device).  d_target7: device float[B][7], 0 = the home pose."""
+        vp = lambda x: C.c_void_p(x) if x else None  # noqa: E731
+        self._check(lib().cdpr_env_evaluate_device(self._h, C.byref(spec), vp(d_target7), vp(d_obs), vp(d_reward), vp(d_mask), vp(d_reason), vp(d_counts)))
+
+    def _with_scratch(self, sizes, body):
+        """body(pointers) with one device buffer per entry of `sizes` (bytes; None: no buffer, 0); every buffer is freed afterwards, on an
+        exception too."""
+        ptrs = []
+        try:
+            for nbytes in sizes:
+                ptrs.append(0 if nbytes is None else self.device_alloc(nbytes))
+            return body(ptrs)
+        finally:
+            for p in ptrs:
+                if p:
+                    lib().cdpr_device_free(self._h, C.c_void_p(p))
+
+    def observe(self, fields: int) -> np.ndarray:
+        """The packed observation tensor float32[B, width] on the host: observe_device into a scratch buffer, then one download."""
+        width = self.observation_width(fields)
+
+        def body(ptrs):
+            self.observe_device(fields, ptrs[0])
+            return self.device_download(ptrs[0], (self.B, width), np.float32)
+
+        return self._with_scratch([4 * self.B * max(width, 1)], body)
+
+    def env_evaluate(self, spec: _abi.EnvSpec, target7=None):
+        """(obs float32[B, width] or None where spec.fields is 0, reward float32[B], mask uint8[B], reason uint32[B], counts
+        uint32[_abi.DONE_COUNTS]) on the host: env_evaluate_device into scratch buffers, then the downloads.  target7: [B, 7] or None."""
+        width = self.observation_width(spec.fields)
+        ld = int(spec.ld) or width
+        tgt = None if target7 is None else np.ascontiguousarray(target7, dtype=np.float32).reshape(self.B, 7)
+
+        def body(ptrs):
+            d_obs, d_reward, d_mask, d_reason, d_counts, d_target = ptrs
+            if tgt is not None:
+                self.device_upload_into(d_target, tgt)
+            self.env_evaluate_device(spec, d_target, d_obs, d_reward, d_mask, d_reason, d_counts)
+            obs = self.device_download(d_obs, (self.B, ld), np.float32)[:, :width].copy() if d_obs else None
+            return (obs, self.device_download(d_reward, self.B, np.float32), self.device_download(d_mask, self.B, np.uint8),
+                    self.device_download(d_reason, self.B, np.uint32), self.device_download(d_counts, _abi.DONE_COUNTS, np.uint32))
+
+        return self._with_scratch([4 * self.B * ld if width else None, 4 * self.B, self.B, 4 * self.B, 4 * _abi.DONE_COUNTS, None if tgt is None else tgt.nbytes], body)
 
     def _command(self, fn, fn_masked, axes, mask) -> int:
         a = np.ascontiguousarray(axes, dtype=np.float32).ravel()

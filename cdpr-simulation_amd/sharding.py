@@ -79,6 +79,22 @@ class ShardedEngine:
         parts = [e.evaluate_done(rule) for e in self.engines]
         return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]), np.sum([p[2] for p in parts], axis=0, dtype=np.uint32)
 
+    def observe(self, fields):
+        """Engine.observe over the shards: rows concatenated in shard_range order."""
+        import numpy as np
+
+        return np.concatenate([e.observe(fields) for e in self.engines])
+
+    def env_evaluate(self, spec, target7=None):
+        """Engine.env_evaluate over the shards: observation, reward, mask and reason concatenated in shard_range order, counts summed as
+        evaluate_done sums them; target7 [B, 7] is split like a batched command."""
+        import numpy as np
+
+        ts = [None] * len(self.engines) if target7 is None else self._split(np.asarray(target7, dtype=np.float32).reshape(self.B, 7), 7)
+        parts = [e.env_evaluate(spec, t) for e, t in zip(self.engines, ts)]
+        obs = None if parts[0][0] is None else np.concatenate([p[0] for p in parts])
+        return (obs,) + tuple(np.concatenate([p[k] for p in parts]) for k in (1, 2, 3)) + (np.sum([p[4] for p in parts], axis=0, dtype=np.uint32),)
+
     def reset_done_device(self, rule, d_pose7=None, d_twist6=None, d_counts=None):
         """Engine.reset_done_device on every shard.  The device buffers belong to the shards' own GPUs: one pointer per shard (a list in
         shard order, rows [0, hi - lo) of that shard's robots), or None = home pose / zero twist / no counts on every shard."""

@@ -36,6 +36,9 @@
 extern "C" {
 #endif
 
+/* The environment view (cdpr_env_spec_t, cdpr_env_spec_size, cdpr_observation_width, cdpr_observe_device, cdpr_env_evaluate_device) came
+ * after 8 as new exports only: no struct or call that existed changed, so the number stays 8.  A caller discovers the feature by those
+ * symbols and checks its cdpr_env_spec_t against cdpr_env_spec_size(). */
 #define CDPR_ABI_VERSION 8u   /* 8 = 7 + cdpr_done_rule_t, cdpr_evaluate_done, cdpr_evaluate_done_device, cdpr_reset_done_device, cdpr_get_episode_start, cdpr_done_rule_size; 7 = 6 + cdpr_reset_robots, cdpr_reset_robots_device; 6 = 5 + cdpr_plan_kernel, cdpr_kernel_name, CDPR_MAX_CABLES 8 -> 12 (cdpr_config_t's anchor arrays grow); 5 = 4 + cdpr_update_scheduled_kind, cdpr_device_pci_bus_id, cdpr_decode_observables_f64 */
 #define CDPR_MAX_CABLES 12u         /* PLG.h:20 fixes 4 (kCableCount); cube.yaml:21-29 is a free-length `points` list: the engine takes 1..12
                                       (9..12: uniform-mode fp32 handles on the lane-per-robot kernels, FK and TD included; see cdpr_create) */
@@ -281,6 +284,64 @@ int cdpr_evaluate_done_device(cdpr_handle_t h, const cdpr_done_rule_t *rule, uin
 int cdpr_evaluate_done(cdpr_handle_t h, const cdpr_done_rule_t *rule, uint8_t *mask, uint32_t *reason, uint32_t *counts);
 int cdpr_reset_done_device(cdpr_handle_t h, const cdpr_done_rule_t *rule, const float *d_pose7, const float *d_twist6, uint32_t *d_counts);
 int cdpr_get_episode_start(cdpr_handle_t h, uint32_t *start);   /* uint32[B] */
+
+/* The environment view: what a policy or a sampler consumes of the batch - the observation tensor, a tracking reward and the done
+ * verdict - computed where the state is, written to caller-owned DEVICE buffers, in ONE launch that reads the platform and observable
+ * rows once.  With the done rules, the device resets and the device command setters a loop commands, steps, judges, re-seeds and
+ * observes the batch without a host wait.  Like the done rules it reads state and observables only: no bit of any robot changes.
+ *   observation  d_obs is float[B][ld], robot-major; ld = 0 means the packed width.  The columns are the fields of `fields` in bit order;
+ *                column j of robot b is, to the bit, what the named getter returns for that robot at that point of the stream (on
+ *                precision = 64 handles what the FLOAT getters return: the double rounded once).  Only rows [0, B) and columns
+ *                [0, width) of a row are written: columns width .. ld - 1 are the caller's own (a goal, say).
+ *   verdict      d_mask, d_reason, d_counts: exactly what cdpr_evaluate_done_device(h, &spec->done, ...) writes at the same point of the
+ *                stream.  Any of the three may be NULL.
+ *   reward       d_reward is float[B], computed in the handle's precision T (float; or double, rounded to float at the store) with
+ *                explicit fma, p / q / v / w the current pose and twist, p* / t the target's position and quaternion:
+ *                  e = p - p*,  pos = fma(e2, e2, fma(e1, e1, e0 e0))
+ *                  c = fma(qw, tw, fma(qz, tz, fma(qy, ty, qx tx))),  qq and tt the same chains on q, q and t, t
+ *                  ori = 1 - (c c) / (qq tt)       (sin^2 of half the angle between the attitudes; sign-invariant, no normalisation assumed)
+ *                  vv = fma(v2, v2, fma(v1, v1, v0 v0)), ww likewise   (as the done rules form them)
+ *                  ee = the fma chain of effort_i^2 from cable 0 up    (the effort of the last PUBLISHED step)
+ *                  res = the FK residual as the done rules take it     (of the last published step, rounded to float)
+ *                  r = alive;  r = fma(-w_k, term_k, r) for position, orientation, speed, rate, effort, residual in this order;
+ *                  r = r - done_penalty where this call's reason word is non-zero.
+ *                A term whose weight is exactly 0 is skipped, not multiplied: a non-finite value behind an unused weight does not reach
+ *                the reward; one behind a used weight propagates.
+ *   d_target7    float[B][7] on the device (x y z qx qy qz qw); NULL = home_pose (rounded to float, as such a buffer would hold it) for
+ *                every robot.
+ * cdpr_observe_device: the observation alone.  d_row_mask is uint8[B] or NULL; where given, only the rows with a non-zero byte are
+ *   written - evaluate, cdpr_reset_robots_device(mask), cdpr_observe_device(mask) leaves every done robot's row at its post-reset
+ *   observation and every other row untouched.
+ * cdpr_env_evaluate_device: observation (d_obs, spec->fields, spec->ld), reward and verdict; any output may be NULL, not all.
+ * cdpr_observation_width: the packed width of `fields` on this handle (7, 6, n, n, n, 7, 1, 1 per field).
+ * Both calls are stream-ordered after every update queued so far, copy nothing and wait for nothing.  Any handle: uniform or per-robot
+ * commands, any kernel family, 1 .. 12 cables, both precisions.  They are not step launches: cdpr_kernel_name and cdpr_plan_kernel do
+ * not see them.
+ * Refusals (a refused call queues nothing): CDPR_ERR_INVALID for a NULL handle, a NULL spec, struct_size != sizeof(cdpr_env_spec_t),
+ * fields == 0 with d_obs given, an unknown field bit, ld non-zero and below the width, every output NULL; CDPR_ERR_UNSUPPORTED for
+ * CDPR_OBS_FK_* or w_fk_residual != 0 without CDPR_STAGE_FK and for whatever cdpr_evaluate_done_device refuses of spec->done. */
+#define CDPR_OBS_POSE           0x01u  /* 7: current pose,  as cdpr_get_raw_state (not decimated)             */
+#define CDPR_OBS_TWIST          0x02u  /* 6: current twist, as cdpr_get_raw_state                             */
+#define CDPR_OBS_JOINT_POSITION 0x04u  /* n: as cdpr_get_joint_states (last published step)                   */
+#define CDPR_OBS_JOINT_VELOCITY 0x08u  /* n                                                                   */
+#define CDPR_OBS_EFFORT         0x10u  /* n                                                                   */
+#define CDPR_OBS_FK_POSE        0x20u  /* 7: as cdpr_get_fk_state        (needs CDPR_STAGE_FK)                */
+#define CDPR_OBS_FK_RESIDUAL    0x40u  /* 1: as cdpr_get_fk_state        (needs CDPR_STAGE_FK)                */
+#define CDPR_OBS_AGE            0x80u  /* 1: (float)(uint32_t)(step_count - episode_start)                    */
+
+typedef struct cdpr_env_spec {
+  uint32_t struct_size, fields;        /* sizeof(cdpr_env_spec_t); CDPR_OBS_* bits, columns in bit order      */
+  uint32_t ld, reserved_;              /* floats per row of d_obs; 0 = the packed width                       */
+  float w_position, w_orientation, w_speed, w_rate, w_effort, w_fk_residual;
+  float alive, done_penalty;
+  cdpr_done_rule_t done;               /* as cdpr_evaluate_done_device takes it                               */
+} cdpr_env_spec_t;
+
+size_t cdpr_env_spec_size(void);                     /* sizeof(cdpr_env_spec_t) as compiled */
+int cdpr_observation_width(cdpr_handle_t h, uint32_t fields, uint32_t *width);
+int cdpr_observe_device(cdpr_handle_t h, uint32_t fields, uint32_t ld, const uint8_t *d_row_mask, float *d_obs);
+int cdpr_env_evaluate_device(cdpr_handle_t h, const cdpr_env_spec_t *spec, const float *d_target7,
+                             float *d_obs, float *d_reward, uint8_t *d_mask, uint32_t *d_reason, uint32_t *d_counts);
 
 /* Replaces cableVelocityCommandCallback / cablePositionCommandCallback
  * (PLG.cpp:67-83).  `count` = number of floats in `axes`: n*B (one Joy per

@@ -1,0 +1,429 @@
+"""cdpr_observe_device / cdpr_env_evaluate_device: the observation tensor, the tracking reward and the done verdict of the batch in one
+launch, into device buffers.  The view is specified as a function of what the getters return, so: every observation column is
+compared - equal, not close, NaN and Inf included - with the getter it names (tests/env_view.py's observation_reference), the verdict
+with Engine.evaluate_done on the same state, the reward with reward_reference at the bound tests/test_env_view_inputs.py establishes
+(64 * 2^-24 * M on fp32 handles, 2^-24 |r| + 64 * 2^-53 * M on precision = 64 handles).
+
+Handle kinds and batch are those of tests/test_gpu_done.py: fast_n8, general_lean_hot, fp64_hold_n8 (per-robot commands), uniform_n8,
+uniform_n4_pair, uniform_n12; B = 130 (two full wavefronts and a ragged one - one 128-robot workgroup and two robots of a second);
+on fast_n8 also B = 1 and B = 321.
+
+  1  observation = getters, 3 verdict = evaluate_done, 4 reward within the bound: on the static scenario and after real steps, at
+     publishPeriod 0 and 0.0025 (test_view_static_and_after_steps, test_batch_edges)
+  2  row mask   5  outputs optional   6  changes nothing   7  the closed loop without a host read   8  refusals   9  sharded
+"""
+import ctypes as C
+from dataclasses import replace
+
+import numpy as np
+import pytest
+
+import done_rules as dr
+import env_view as ev
+import test_gpu_done as gd
+import test_gpu_reset_robots as rr
+import test_reset_robots_inputs as ri
+
+pytestmark = pytest.mark.gpu
+
+B, STRIDE, KINDS, LAYOUTS = gd.B, gd.STRIDE, gd.KINDS, gd.LAYOUTS
+SENTINEL = np.float32(-77.25)
+
+
+@pytest.fixture(autouse=True)
+def clean_env(monkeypatch):
+    for k in ("CDPR_GEN_SPLIT", "CDPR_GEN_LEAN", "CDPR_GEN_HOT", "CDPR_MAPPING", "CDPR_NO_GRAPH"):
+        monkeypatch.delenv(k, raising=False)
+
+
+class Buffers:
+    """device buffers of a test, freed together"""
+
+    def __init__(self, eng):
+        self.eng, self.ptrs = eng, []
+
+    def upload(self, array):
+        self.ptrs.append(self.eng.device_upload(array))
+        return self.ptrs[-1]
+
+    def free(self):
+        self.eng.synchronize()
+        for p in self.ptrs:
+            self.eng.device_free(p)
+        self.ptrs = []
+
+
+def observe_padded(eng, bufs, fields, ld, batch, d_row_mask=0, rows=None):
+    """observe_device into a sentinel-filled float[rows][ld] (rows > B): the whole buffer back"""
+    rows = rows or batch + 7
+    d = bufs.upload(np.full((rows, ld), SENTINEL, np.float32))
+    eng.observe_device(fields, d, ld, d_row_mask)
+    return eng.device_download(d, (rows, ld), np.float32)
+
+
+def check_observation(eng, cfg, bufs, where, batch=B):
+    """case 1 at the engine's present state: every single field and all fields, ld = width and width + 3"""
+    g = ev.view_getters(eng, cfg)
+    every = ev.fields_of(cfg)
+    for fields in [1 << k for k in range(8) if (every >> k) & 1] + [every]:
+        want = ev.observation_reference(fields, **g)
+        width = want.shape[1]
+        assert eng.observation_width(fields) == width == ev.observation_reference(fields, **g).shape[1]
+        for ld in (width, width + 3):
+            got = observe_padded(eng, bufs, fields, ld, batch)
+            assert np.array_equal(got[:batch, :width], want, equal_nan=True), f"{where}, fields {fields:#x}, ld {ld}: columns differ from the getters at {np.argwhere(~((got[:batch, :width] == want) | (np.isnan(want) & np.isnan(got[:batch, :width]))))[:6].tolist()}"
+            assert (got[batch:] == SENTINEL).all() and (got[:, width:] == SENTINEL).all(), f"{where}, fields {fields:#x}, ld {ld}: written past row B or past the width"
+    assert np.array_equal(eng.observe(every), ev.observation_reference(every, **g), equal_nan=True), f"{where}: Engine.observe"
+    return g
+
+
+def check_reward_and_verdict(pkg, eng, cfg, rule, weights, target, where, nan_robots=(), batch=B):
+    """cases 3 and 4 at the engine's present state; returns the reward"""
+    f64 = cfg.precision == 64
+    every = ev.fields_of(cfg)
+    spec = ev.spec_of(pkg, cfg, rule, weights, fields=every)
+    want_verdict = eng.evaluate_done(rule)
+    obs, reward, mask, reason, counts = eng.env_evaluate(spec, target)
+    gd.assert_verdict((mask, reason, counts), want_verdict, f"{where}, verdict")
+    assert np.array_equal(obs, eng.observe(every), equal_nan=True), f"{where}: the observation of env_evaluate"
+    rg = ev.reward_getters(eng, cfg)
+    home = cfg.model.home_pose()
+    r, M = ev.reward_reference(spec, reason=reason, target7=target, home=home, **rg)
+    finite = np.isfinite(r)
+    with np.errstate(all="ignore"):
+        worst = float((np.abs(reward.astype(np.float64) - r)[finite] / ev.reward_bound(r, M, f64)[finite]).max())
+    print(f"env view, {where}: reward within {worst:.3f} of the bound, {int((reason != 0).sum())} robots done")
+    assert reward.dtype == np.float32 and ev.inside(reward, r, M, f64)[finite].all(), f"{where}: the reward leaves the bound ({worst:.2f} x) for robots {np.nonzero(finite & ~ev.inside(reward, r, M, f64))[0][:8]}"
+    assert np.array_equal(np.nonzero(~finite)[0], np.sort(np.asarray(nan_robots, dtype=np.int64))), f"{where}: the reference is not finite for robots {np.nonzero(~finite)[0]}"
+    assert np.array_equal(reward[~finite].astype(np.float64), r[~finite], equal_nan=True), f"{where}: NaN / Inf rewards differ from the reference's"
+    # the bound separates this formula from a wrong one on these very inputs (both weights are live here)
+    swapped = ev.spec_of(pkg, cfg, rule, dict(weights, w_position=weights["w_orientation"], w_orientation=weights["w_position"]))
+    assert (~ev.inside(reward, *ev.reward_reference(swapped, reason=reason, target7=target, home=home, **rg), f64)[finite]).sum() >= batch // 2, where
+    # the penalty is visible on exactly the done robots
+    free = eng.env_evaluate(ev.spec_of(pkg, cfg, rule, weights, done_penalty=0.0), target)[1]
+    with np.errstate(all="ignore"):
+        assert np.array_equal((free != reward)[finite], (reason != 0)[finite]) and np.allclose((free - reward)[finite & (reason != 0)], weights["done_penalty"], rtol=0, atol=1e-3), where
+    return spec, reward, reason
+
+
+# ---- 1, 3, 4 -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("period", [0.0, 0.0025], ids=["every_step", "decimated"])
+@pytest.mark.parametrize("kind", KINDS)
+def test_view_static_and_after_steps(pkg, monkeypatch, kind, period):
+    n = gd.UNIFORM[kind][0] if kind in gd.UNIFORM else 8
+    extra = dict(publishPeriod=period)
+    if n >= 6:
+        extra.update(tdFMin=1.0, tdFMax=12.0, fkMaxIterations=1)
+    cfg = gd.config_of(pkg, kind, monkeypatch, gd.limited, **extra)
+    f64 = cfg.precision == 64
+    rule, weights, pose, twist, target = ev.scenario(pkg, cfg.model, f64)
+    eng = pkg.Engine(cfg, 0)
+    bufs = Buffers(eng)
+    # the static scenario: NaN and Inf robots, robots on and past the workspace box, nothing published yet
+    gd.put(eng, cfg, pose, twist)
+    where = f"{kind}, period {period}, static"
+    g = check_observation(eng, cfg, bufs, where)
+    assert np.isnan(g["pose"][dr.NAN_POSITION, 1]) and np.isinf(g["twist"][dr.INF_TWIST, 0])
+    spec, reward, reason = check_reward_and_verdict(pkg, eng, cfg, rule, weights, target, where, nan_robots=dr.NONFINITE_ROBOTS)
+    assert reason[dr.NAN_POSITION] == dr.NONFINITE and 0 < (reason != 0).sum() < B
+    # a zero weight hides the NaN robots' NaN terms (pose and twist are NaN / Inf there, efforts and residual are not) ...
+    quiet = ev.spec_of(pkg, cfg, rule, dict(weights, w_position=0.0, w_orientation=0.0, w_speed=0.0, w_rate=0.0))
+    assert np.isfinite(eng.env_evaluate(quiet, target)[1]).all(), f"{kind}: a NaN behind a zero weight reaches the reward"
+    # ... and one that is not zero shows NaN there and nowhere else: robot INF_TWIST has an infinite vx only
+    speed_only = ev.spec_of(pkg, cfg, rule, dict(weights, w_position=0.0, w_orientation=0.0, w_rate=0.0))
+    bad = ~np.isfinite(eng.env_evaluate(speed_only, target)[1])
+    assert np.array_equal(np.nonzero(bad)[0], [dr.INF_TWIST]), kind
+    bufs.free()
+    # real steps (the non-finite robots leave first: no step runs on them)
+    eng.reset()
+    h = ri.history_inputs(cfg.model, 301)
+    gd.put(eng, cfg, h["pose"])
+    gd.drive([eng], cfg, h, ri.HISTORY)
+    enable = dr.TRAVEL | dr.WORKSPACE | ((dr.FK_RESIDUAL | dr.INFEASIBLE) if n >= 6 else 0)
+    thr = float(np.median(eng.fk_state()[1])) if n >= 6 else 0.0
+    stepped = replace(rule, enable=enable, max_fk_residual=thr)
+    quiet = 0  # steps that did not publish: the view then shows the pose moved on beside the joints of the last published step
+    for later in range(1 + (3 if period > 0.0 else 0)):
+        where = f"{kind}, period {period}, after {ri.HISTORY + later} steps"
+        g = check_observation(eng, cfg, bufs, where)
+        assert g["effort"].any() and np.isfinite(g["pose"]).all()
+        _, _, reason = check_reward_and_verdict(pkg, eng, cfg, stepped, weights, target, where)
+        assert 0 < (reason != 0).sum() < B, where
+        bufs.free()
+        if period > 0.0:
+            eng.update(1)
+            quiet += int(np.array_equal(eng.joint_states()[0], g["joint_position"]) and not np.array_equal(eng.raw_state()[0], g["pose"]))
+    assert quiet >= 1 or period == 0.0, f"{kind}: of three consecutive steps at period {period} none was left unpublished"
+    eng.close()
+
+
+@pytest.mark.parametrize("batch", [1, 321])
+def test_batch_edges(pkg, monkeypatch, batch):
+    """one robot; one robot past two 128-robot workgroups and a full wavefront"""
+    cfg = replace(gd.config_of(pkg, "fast_n8", monkeypatch), batch=batch)
+    h = ri.history_inputs(cfg.model, 311, batch=batch)
+    rng = np.random.default_rng(312)
+    target = (h["pose"] + rng.uniform(-0.01, 0.01, (batch, 7))).astype(np.float32)
+    weights = ev.scenario(pkg, cfg.model, False)[1]
+    rule = replace(dr.loop_rule(pkg, cfg.model), max_steps=5)
+    eng = pkg.Engine(cfg, 0)
+    bufs = Buffers(eng)
+    eng.set_platform_state(pose7=h["pose"])
+    eng.set_velocity_command(h["v"])
+    for steps in (4, 1):  # the timeout fires at the second point
+        eng.update(steps)
+        check_observation(eng, cfg, bufs, f"B = {batch}", batch)
+        check_reward_and_verdict(pkg, eng, cfg, rule, weights, target, f"B = {batch}", batch=batch)
+        bufs.free()
+    assert eng.evaluate_done(rule)[2][0] == batch
+    eng.close()
+
+
+# ---- 2 -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", KINDS)
+def test_row_mask(pkg, monkeypatch, kind):
+    cfg = gd.config_of(pkg, kind, monkeypatch)
+    every = ev.fields_of(cfg)
+    h, respawn = dr.loop_inputs(cfg.model)
+    rule = dr.loop_rule(pkg, cfg.model)
+    eng = pkg.Engine(cfg, 0)
+    bufs = Buffers(eng)
+    gd.put(eng, cfg, h["pose"])
+    gd.drive([eng], cfg, h, 10)
+    before = eng.observe(every)
+    width = before.shape[1]
+    # only the selected rows change: a tensor of sentinels, any non-zero byte selects
+    chosen = ri.reset_mask() * np.uint8(3)
+    got = observe_padded(eng, bufs, every, width + 2, B, bufs.upload(chosen))
+    sel = np.zeros(len(got), bool)
+    sel[:B] = chosen != 0
+    assert np.array_equal(got[sel, :width], before[chosen != 0]) and (got[~sel] == SENTINEL).all() and (got[:, width:] == SENTINEL).all(), kind
+    if cfg.perRobotCommands:
+        # the auto-reset sequence: evaluate, reset the done robots, observe them - no host read in between
+        d_obs, d_mask, d_pose = bufs.upload(before), bufs.upload(np.zeros(B, np.uint8)), bufs.upload(respawn[0])
+        eng.env_evaluate_device(ev.spec_of(pkg, cfg, rule, {}), d_mask=d_mask)
+        eng.reset_robots_device(d_mask, d_pose)
+        eng.observe_device(every, d_obs, 0, d_mask)
+        after, done = eng.device_download(d_obs, (B, width), np.float32), eng.device_download(d_mask, B, np.uint8).astype(bool)
+        fresh = eng.observe(every)
+        assert 0 < done.sum() < B and not np.array_equal(fresh[done], before[done])
+        assert np.array_equal(after[done], fresh[done]), f"{kind}: a done robot's row is not its observation after the reset"
+        assert np.array_equal(after[~done], before[~done]), f"{kind}: a row outside the mask changed"
+    bufs.free()
+    eng.close()
+
+
+# ---- 5 -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["fast_n8", "fp64_hold_n8", "uniform_n4_pair"])
+def test_outputs_are_optional(pkg, monkeypatch, kind):
+    cfg = gd.config_of(pkg, kind, monkeypatch)
+    every = ev.fields_of(cfg)
+    rule, weights, pose, twist, target = ev.scenario(pkg, cfg.model, cfg.precision == 64)
+    eng = pkg.Engine(cfg, 0)
+    bufs = Buffers(eng)
+    gd.put(eng, cfg, pose, twist)
+    spec = ev.spec_of(pkg, cfg, rule, weights, fields=every)
+    obs, reward, mask, reason, counts = eng.env_evaluate(spec, target)
+    width = obs.shape[1]
+    canary = dict(d_obs=np.full((STRIDE, width), SENTINEL, np.float32), d_reward=np.full(STRIDE, SENTINEL, np.float32), d_mask=np.full(STRIDE, 0xA5, np.uint8),
+                  d_reason=np.full(STRIDE, 0xDEADBEEF, np.uint32), d_counts=np.full(2 * dr.COUNTS, 0xDEADBEEF, np.uint32))
+    full = dict(d_obs=np.concatenate([obs, canary["d_obs"][B:]]), d_reward=np.concatenate([reward, canary["d_reward"][B:]]), d_mask=np.concatenate([mask, canary["d_mask"][B:]]),
+                d_reason=np.concatenate([reason, canary["d_reason"][B:]]), d_counts=np.concatenate([counts, canary["d_counts"][dr.COUNTS:]]))
+    dev = {k: bufs.upload(v) for k, v in canary.items()}
+    d_target = bufs.upload(target)
+    for wanted in (("d_obs",), ("d_reward",), ("d_mask",), ("d_reason",), ("d_counts",), ("d_reward", "d_counts"), tuple(canary)):
+        for k, v in canary.items():
+            eng.device_upload_into(dev[k], v)
+        eng.env_evaluate_device(spec, d_target, **{k: dev[k] for k in wanted})
+        for k, v in canary.items():
+            got = eng.device_download(dev[k], v.shape, v.dtype)
+            assert np.array_equal(got, full[k] if k in wanted else v, equal_nan=got.dtype == np.float32), f"{kind}: outputs {wanted}: {k}"
+    # a NULL target is the home pose, as a float buffer holds it
+    home = np.tile(np.asarray(cfg.model.home_pose(), dtype=np.float32), (B, 1))
+    assert np.array_equal(eng.env_evaluate(spec)[1], eng.env_evaluate(spec, home)[1], equal_nan=True) and not np.array_equal(eng.env_evaluate(spec)[1], reward, equal_nan=True)
+    bufs.free()
+    eng.reset()  # (the non-finite robots leave before the handle goes)
+    eng.close()
+
+
+# ---- 6 -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", KINDS)
+def test_the_view_changes_nothing(pkg, monkeypatch, kind):
+    cfg = gd.config_of(pkg, kind, monkeypatch)
+    every = ev.fields_of(cfg)
+    h = ri.history_inputs(cfg.model, 401)
+    rule, weights = dr.loop_rule(pkg, cfg.model), ev.scenario(pkg, cfg.model, False)[1]
+    spec = ev.spec_of(pkg, cfg, rule, weights, fields=every)
+    width = pkg.observation_width(every, cfg.n_cables)
+    eng, twin = pkg.Engine(cfg, 0), pkg.Engine(cfg, 0)
+    for e in (eng, twin):
+        gd.put(e, cfg, h["pose"])
+    gd.drive([eng, twin], cfg, h, 20)
+    name = eng.kernel_name
+    bufs = Buffers(eng)
+    d_obs, d_reward, d_mask, d_reason, d_counts = (bufs.upload(np.zeros(k, np.uint8)) for k in (4 * B * width, 4 * B, B, 4 * B, 4 * dr.COUNTS))
+    eng.env_evaluate_device(spec, 0, d_obs, d_reward, d_mask, d_reason, d_counts)
+    eng.observe_device(every, d_obs, 0, d_mask)
+    assert eng.kernel_name == name == twin.kernel_name and eng.step_count == twin.step_count == 20, f"{kind}: the view changed kernel_name or the step count"
+    assert eng.device_download(d_counts, dr.COUNTS, np.uint32)[0] > 0  # (the rule decides something: 20 steps against max_steps = 15)
+    for x, y in zip(rr.state_of(eng, cfg), rr.state_of(twin, cfg)):
+        assert np.array_equal(x, y), f"{kind}: the view changed the engine's state"
+    assert not eng.episode_start().any()
+    for step in range(20):
+        eng.update(1), twin.update(1)
+        eng.env_evaluate_device(spec, 0, d_obs, d_reward, d_mask, d_reason, d_counts)
+        eng.observe_device(every, d_obs, 0, d_mask if step % 2 else 0)
+    assert eng.kernel_name == twin.kernel_name and eng.step_count == twin.step_count == 40
+    for x, y in zip(rr.state_of(eng, cfg), rr.state_of(twin, cfg)):
+        assert np.array_equal(x, y), f"{kind}: an engine viewed every step drifts from its twin"
+    assert np.array_equal(eng.episode_start(), twin.episode_start())
+    bufs.free()
+    eng.close(), twin.close()
+
+
+# ---- 7 -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", LAYOUTS)
+def test_the_closed_loop_without_a_host_read(pkg, monkeypatch, kind):
+    """40 iterations of command (device buffer), update(1), env_evaluate_device, reset_robots_device, observe_device(mask) on one engine;
+    the same loop through the host getters, evaluate_done and reset_robots on another: final state, counts and tensor are equal."""
+    cfg = gd.config_of(pkg, kind, monkeypatch)
+    every, n, iterations = ev.fields_of(cfg), cfg.n_cables, 40
+    h, respawn = dr.loop_inputs(cfg.model)
+    rule, weights = dr.loop_rule(pkg, cfg.model), ev.scenario(pkg, cfg.model, False)[1]
+    spec = ev.spec_of(pkg, cfg, rule, weights, fields=every)
+    rng = np.random.default_rng(701)
+    joys = rng.uniform(-0.03, 0.03, (4, B, n)).astype(np.float32)
+    dev, host = pkg.Engine(cfg, 0), pkg.Engine(cfg, 0)
+    for e in (dev, host):
+        gd.put(e, cfg, h["pose"])
+    bufs = Buffers(dev)
+    width = dev.observation_width(every)
+    d_joys = [bufs.upload(j) for j in joys]
+    d_obs, d_reward, d_mask = bufs.upload(np.full((B, width), SENTINEL, np.float32)), bufs.upload(np.zeros(B, np.float32)), bufs.upload(np.zeros(B, np.uint8))
+    d_counts, d_pose = bufs.upload(np.zeros((iterations, dr.COUNTS), np.uint32)), bufs.upload(respawn[0])
+    for j in range(iterations):
+        assert dev.set_velocity_command_device(d_joys[j % 4], B * n) == 0
+        dev.update(1)
+        dev.env_evaluate_device(spec, 0, d_obs, d_reward, d_mask, 0, d_counts + 4 * dr.COUNTS * j)
+        dev.reset_robots_device(d_mask, d_pose)
+        dev.observe_device(every, d_obs, 0, d_mask)
+    counts = np.zeros(dr.COUNTS, np.uint64)
+    for j in range(iterations):
+        assert host.set_velocity_command(joys[j % 4]) == 0
+        host.update(1)
+        mask, _, c = host.evaluate_done(rule)
+        tensor = ev.observation_reference(every, **ev.view_getters(host, cfg))
+        host.reset_robots(mask, respawn[0])
+        tensor[mask != 0] = ev.observation_reference(every, **ev.view_getters(host, cfg))[mask != 0]
+        counts += c
+    got_counts = dev.device_download(d_counts, (iterations, dr.COUNTS), np.uint32)
+    print(f"env view, closed loop, {kind}: robots reset per iteration {got_counts[:, 0].tolist()}")
+    assert np.array_equal(got_counts.sum(axis=0, dtype=np.uint64), counts) and (got_counts[:, 0] > 0).sum() >= 3 and got_counts[:, 0].max() < B
+    assert np.array_equal(dev.device_download(d_obs, (B, width), np.float32), tensor), f"{kind}: the final observation tensor differs"
+    for x, y in zip(rr.state_of(dev, cfg), rr.state_of(host, cfg)):
+        assert np.array_equal(x, y), f"{kind}: the device loop's final state differs from the host loop's"
+    assert np.array_equal(dev.episode_start(), host.episode_start()) and dev.step_count == host.step_count == iterations
+    bufs.free()
+    dev.close(), host.close()
+
+
+# ---- 8 -------------------------------------------------------------------------------------------------------------------------
+def test_refusals(pkg, monkeypatch):
+    from cdpr_simulation_amd._native import lib
+
+    L = lib()
+    INVALID, UNSUPPORTED = pkg._abi.ERR_INVALID, pkg._abi.ERR_UNSUPPORTED
+    cfg = gd.config_of(pkg, "fast_n8", monkeypatch)
+    eng, twin = pkg.Engine(cfg, 0), pkg.Engine(cfg, 0)
+    bufs = Buffers(eng)
+    width = eng.observation_width(ev.ALL)
+    canary = dict(obs=np.full((B, width), SENTINEL, np.float32), reward=np.full(B, SENTINEL, np.float32), mask=np.full(B, 7, np.uint8), reason=np.full(B, 0xDEADBEEF, np.uint32),
+                  counts=np.full(dr.COUNTS, 0xDEADBEEF, np.uint32))
+    d = {k: C.c_void_p(bufs.upload(v)) for k, v in canary.items()}
+    outs = (d["obs"], d["reward"], d["mask"], d["reason"], d["counts"])
+    good = pkg.EnvSpec(done=pkg.DoneRule(enable=dr.TIMEOUT, max_steps=0), fields=ev.ALL, w_position=1.0)
+
+    def refused(rc, code, word):
+        assert rc == code and word in L.cdpr_last_error(eng._h), (rc, L.cdpr_last_error(eng._h))
+
+    def spec(**kw):
+        s = pkg.EnvSpec(done=pkg.DoneRule(enable=dr.TIMEOUT, max_steps=0), **dict(dict(fields=ev.ALL, w_position=1.0), **kw))
+        return C.byref(s)
+
+    # a NULL handle, a NULL spec, a struct of another size
+    assert L.cdpr_env_evaluate_device(None, C.byref(good), None, *outs) == INVALID and L.cdpr_observe_device(None, ev.ALL, 0, None, d["obs"]) == INVALID
+    w = C.c_uint32(77)
+    assert L.cdpr_observation_width(None, ev.ALL, C.byref(w)) == INVALID and w.value == 77
+    refused(L.cdpr_env_evaluate_device(eng._h, None, None, *outs), INVALID, b"null spec")
+    bad = pkg.EnvSpec(done=pkg.DoneRule(), fields=ev.ALL)
+    bad.struct_size = 100
+    refused(L.cdpr_env_evaluate_device(eng._h, C.byref(bad), None, *outs), INVALID, b"struct_size")
+    # fields == 0 with a tensor, an unknown field bit, ld below the width, every output NULL
+    refused(L.cdpr_env_evaluate_device(eng._h, spec(fields=0), None, *outs), INVALID, b"no fields")
+    refused(L.cdpr_observe_device(eng._h, 0, 0, None, d["obs"]), INVALID, b"no fields")
+    refused(L.cdpr_env_evaluate_device(eng._h, spec(fields=0x100 | ev.POSE), None, *outs), INVALID, b"unknown")
+    refused(L.cdpr_observe_device(eng._h, 0x200, 0, None, d["obs"]), INVALID, b"unknown")
+    refused(L.cdpr_observation_width(eng._h, 0x100, C.byref(w)), INVALID, b"unknown")
+    refused(L.cdpr_observation_width(eng._h, ev.ALL, None), INVALID, b"null width")
+    refused(L.cdpr_env_evaluate_device(eng._h, spec(ld=width - 1), None, *outs), INVALID, b"ld is below")
+    refused(L.cdpr_observe_device(eng._h, ev.ALL, width - 1, None, d["obs"]), INVALID, b"ld is below")
+    refused(L.cdpr_env_evaluate_device(eng._h, C.byref(good), None, None, None, None, None, None), INVALID, b"every output is null")
+    refused(L.cdpr_observe_device(eng._h, ev.ALL, 0, None, None), INVALID, b"null observation tensor")
+    # whatever cdpr_evaluate_done_device refuses of spec.done
+    wrong_rule = pkg.EnvSpec(done=pkg.DoneRule(), fields=ev.ALL)
+    wrong_rule.done.struct_size = 52
+    refused(L.cdpr_env_evaluate_device(eng._h, C.byref(wrong_rule), None, *outs), INVALID, b"rule.struct_size")
+    with pytest.raises(pkg.CdprError) as ei:
+        eng.env_evaluate_device(good)
+    assert ei.value.code == INVALID
+    # nothing was queued or written by a refused call
+    for k, v in canary.items():
+        assert np.array_equal(eng.device_download(d[k].value, v.shape, v.dtype), v), k
+    for x, y in zip(rr.state_of(eng, cfg), rr.state_of(twin, cfg)):
+        assert np.array_equal(x, y)
+    assert w.value == 77
+    assert L.cdpr_env_evaluate_device(eng._h, C.byref(good), None, *outs) == 0 and eng.device_download(d["counts"].value, dr.COUNTS, np.uint32)[0] == B  # (the same buffers, accepted)
+    bufs.free()
+    eng.close(), twin.close()
+    # CDPR_OBS_FK_* or w_fk_residual without CDPR_STAGE_FK; FK_RESIDUAL / INFEASIBLE in the rule without their stage
+    for stages in (2, 0):
+        eng = pkg.Engine(pkg.Config(model=ri.model_of(pkg, 8), batch=B, stages=stages), 0)
+        bufs = Buffers(eng)
+        d_obs, d_reward = bufs.upload(np.full((B, 64), SENTINEL, np.float32)), bufs.upload(np.full(B, SENTINEL, np.float32))
+        for fields in (ev.FK_POSE, ev.FK_RESIDUAL | ev.POSE):
+            for call in (lambda: eng.observe_device(fields, d_obs), lambda: eng.env_evaluate_device(pkg.EnvSpec(fields=fields), 0, d_obs), lambda: eng.observe(fields)):
+                with pytest.raises(pkg.CdprError) as ei:
+                    call()
+                assert ei.value.code == UNSUPPORTED and "CDPR_STAGE_FK" in str(ei.value), (stages, fields)
+        for s, word in ((pkg.EnvSpec(w_fk_residual=0.5), "w_fk_residual"), (pkg.EnvSpec(done=pkg.DoneRule(enable=dr.FK_RESIDUAL)), "CDPR_DONE_FK_RESIDUAL"),
+                        (pkg.EnvSpec(done=pkg.DoneRule(enable=dr.INFEASIBLE)), "CDPR_DONE_INFEASIBLE")):
+            if stages == 2 and "INFEASIBLE" in word:
+                continue
+            with pytest.raises(pkg.CdprError) as ei:
+                eng.env_evaluate_device(s, 0, 0, d_reward)
+            assert ei.value.code == UNSUPPORTED and word in str(ei.value), (stages, word)
+        assert (eng.device_download(d_obs, (B, 64), np.float32) == SENTINEL).all() and (eng.device_download(d_reward, B, np.float32) == SENTINEL).all()
+        assert eng.observation_width(ev.ALL) == 46  # (the arithmetic needs no stage)
+        ok = eng.observe(ev.ALL & ~ev.NEED_FK)  # what the handle has may be asked for
+        assert ok.shape == (B, 38) and np.array_equal(ok[:, :7], eng.raw_state()[0])
+        bufs.free()
+        eng.close()
+
+
+# ---- 9 -------------------------------------------------------------------------------------------------------------------------
+def test_sharded(pkg, monkeypatch):
+    cfg = gd.config_of(pkg, "fast_n8", monkeypatch)
+    rule, weights, pose, twist, target = ev.scenario(pkg, cfg.model, False)
+    spec = ev.spec_of(pkg, cfg, rule, weights, fields=ev.ALL)
+    one = pkg.Engine(cfg, 0)
+    sh = pkg.ShardedEngine(cfg, devices=[0, 0])
+    one.set_platform_state(pose, twist), sh.set_platform_state(pose, twist)
+    assert [hi - lo for lo, hi in sh.spans] == [65, 65]
+    assert np.array_equal(sh.observe(ev.ALL), one.observe(ev.ALL), equal_nan=True)
+    want, got = one.env_evaluate(spec, target), sh.env_evaluate(spec, target)
+    for name, g, w in zip(("obs", "reward", "mask", "reason", "counts"), got, want):
+        assert g.dtype == w.dtype and np.array_equal(g, w, equal_nan=g.dtype == np.float32), f"two shards on one device: {name}"
+    assert got[4][0] == want[2].sum() > 0
+    for e in sh.engines + [one]:
+        e.reset()
+    sh.close(), one.close()
