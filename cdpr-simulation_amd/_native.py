@@ -18,6 +18,7 @@ EXPORTS = [
     "cdpr_create", "cdpr_destroy", "cdpr_reset", "cdpr_last_error", "cdpr_set_platform_state", "cdpr_reset_robots", "cdpr_reset_robots_device",
     "cdpr_done_rule_size", "cdpr_evaluate_done_device", "cdpr_evaluate_done", "cdpr_reset_done_device", "cdpr_get_episode_start",
     "cdpr_env_spec_size", "cdpr_observation_width", "cdpr_observe_device", "cdpr_env_evaluate_device",
+    "cdpr_copy_robots", "cdpr_copy_robots_device",
     "cdpr_set_velocity_command", "cdpr_set_position_command", "cdpr_set_velocity_command_device",
     "cdpr_set_position_command_device", "cdpr_bind_velocity_command_device", "cdpr_bind_position_command_device",
     "cdpr_set_velocity_command_masked", "cdpr_set_position_command_masked", "cdpr_set_force_command", "cdpr_set_force_command_device",
@@ -78,6 +79,10 @@ def lib():
         L.cdpr_observation_width.argtypes = [H, C.c_uint32, u32p]
         L.cdpr_observe_device.argtypes = [H, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.cdpr_env_evaluate_device.argtypes = [H, C.POINTER(_abi.EnvSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    # ... and so did the fork of robots onto others
+    if hasattr(L, "cdpr_copy_robots"):
+        L.cdpr_copy_robots.argtypes = [H, ip]
+        L.cdpr_copy_robots_device.argtypes = [H, C.c_void_p, C.c_void_p]
     for name in ("cdpr_set_velocity_command", "cdpr_set_position_command", "cdpr_set_force_command"):
         getattr(L, name).argtypes = [H, fp, C.c_size_t]
     for name in ("cdpr_set_velocity_command_device", "cdpr_set_position_command_device", "cdpr_bind_velocity_command_device",

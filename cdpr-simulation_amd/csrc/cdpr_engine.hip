@@ -203,7 +203,7 @@ void free_all(cdpr_engine* h) {
   for (CmdChannel& c : h->cmd)
     for (hipEvent_t ev : {c.stage_ev[0], c.stage_ev[1], c.free_ev})
       if (ev) (void)hipEventDestroy(ev);
-  for (hipEvent_t ev : {h->ev0, h->ev1, h->reset_ev[0], h->reset_ev[1]})
+  for (hipEvent_t ev : {h->ev0, h->ev1, h->reset_ev[0], h->reset_ev[1], h->copy_ev[0], h->copy_ev[1]})
     if (ev) (void)hipEventDestroy(ev);
   for (hipStream_t st : {h->copy_stream, h->stream})
     if (st) (void)hipStreamDestroy(st);

@@ -4,7 +4,7 @@
 // cdpr_engine.hip (create / destroy, the general path's set-up, the command setters, read-out, the extern "C" wrappers),
 // cdpr_engine_launch.hip (what turns "advance n world steps" into launches: the latch, the chain and its clock, the fp32 and
 // general paths, schedules), cdpr_engine_f64.hip (precision = 64: set-up, its path of the chain, read-out), cdpr_engine_rollout.hip (cdpr_rollout_velocity*), cdpr_engine_solvers.hip (cdpr_solve_ik / fk / td), cdpr_engine_reset.hip
-// (cdpr_reset_robots*), cdpr_engine_done.hip (cdpr_evaluate_done*, cdpr_reset_done_device, cdpr_get_episode_start), cdpr_engine_env.hip (cdpr_observe_device,
+// (cdpr_reset_robots*), cdpr_engine_copy.hip (cdpr_copy_robots*), cdpr_engine_done.hip (cdpr_evaluate_done*, cdpr_reset_done_device, cdpr_get_episode_start), cdpr_engine_env.hip (cdpr_observe_device,
 // cdpr_env_evaluate_device, cdpr_observation_width).  Not installed, not part of the C-ABI (include/cdpr.h is).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -258,6 +258,12 @@ struct cdpr_engine {
   hipEvent_t reset_ev[2] = {nullptr, nullptr};  // the copy out of that staging block has completed
   bool reset_ev_set[2] = {false, false};
   int reset_idx = 0;
+  // cdpr_copy_robots (host form): the caller's source map, staged the same way (int32[B], sized once)
+  DevBuf<int32_t> d_copy_map;
+  PinnedBuf<int32_t> h_copy_stage[2];
+  hipEvent_t copy_ev[2] = {nullptr, nullptr};
+  bool copy_ev_set[2] = {false, false};
+  int copy_idx = 0;
   // episode clock: uint32[stride], the world step (low word) of every robot's last model reset; zero after create / cdpr_reset and
   // on uniform handles.  d_done: scratch of cdpr_evaluate_done's host form and the mask of cdpr_reset_done_device
   // ([uint8 mask[B], padded to 16 B | uint32 reason[B] | uint32 counts[CDPR_DONE_COUNTS]], sized once)

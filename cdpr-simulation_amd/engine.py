@@ -116,6 +116,21 @@ class Engine:
         self._check(lib().cdpr_reset_robots_device(self._h, C.c_void_p(d_mask) if d_mask else None, C.c_void_p(d_pose7) if d_pose7 else None,
                                                    C.c_void_p(d_twist6) if d_twist6 else None))
 
+    def copy_robots(self, source) -> None:
+        """Fork robots (cdpr_copy_robots): robot r with 0 <= source[r] < B, source[r] != r continues from where robot source[r] is now -
+        every getter returns for r what it returns for its source, to the bit, and the two advance identically while they get the same
+        commands.  A negative entry or r itself leaves r untouched; a source must itself be untouched and in range (else
+        CdprError ERR_INVALID, nothing changed).  Pending commands stay with their index.  Needs Config.perRobotCommands.  Queued on the
+        engine's stream; the array may be reused at once."""
+        s = np.ascontiguousarray(source, dtype=np.int32).reshape(self.B)
+        self._check(lib().cdpr_copy_robots(self._h, s.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    def copy_robots_device(self, d_source: int, d_status: int = 0) -> None:
+        """The same from a device map int32[B]: nothing is copied or synchronised (cdpr_copy_robots_device).  A destination whose source
+        is out of range or is itself a destination is skipped; d_status (device uint32[2], 0 = no counting) receives
+        [robots copied, destinations skipped]."""
+        self._check(lib().cdpr_copy_robots_device(self._h, C.c_void_p(d_source) if d_source else None, C.c_void_p(d_status) if d_status else None))
+
     # -- done rules: who should be put back, decided on the device
     @staticmethod
     def _rule(rule):

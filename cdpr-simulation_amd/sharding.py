@@ -72,6 +72,29 @@ class ShardedEngine:
         for e, (lo, hi), p, t in zip(self.engines, self.spans, ps, ts):
             e.reset_robots(m[lo:hi], p, t)
 
+    def copy_robots(self, source):
+        """Engine.copy_robots over the shards: the map sliced by shard_range and re-based to each shard's own indices.  There is no
+        cross-GPU data path: a destination whose source lies in another shard raises ValueError before any shard is touched, and so
+        does what a single engine refuses (a source out of range, or itself a destination)."""
+        import numpy as np
+
+        s = np.asarray(source, dtype=np.int64).reshape(self.B)
+        dest = (s >= 0) & (s != np.arange(self.B))
+        if (s[dest] >= self.B).any():
+            raise ValueError("copy_robots: a source index is not a robot of this batch")
+        if dest[s[dest]].any():
+            raise ValueError("copy_robots: a source is itself a destination")
+        parts = []
+        for lo, hi in self.spans:
+            part, d = s[lo:hi], dest[lo:hi]
+            away = d & ((part < lo) | (part >= hi))
+            if away.any():
+                r = lo + int(np.flatnonzero(away)[0])
+                raise ValueError(f"copy_robots: robot {r} (shard [{lo}, {hi})) takes robot {int(s[r])} of another shard; there is no cross-GPU copy")
+            parts.append(np.where(d, part - lo, -1).astype(np.int32))  # ("leave me" in either spelling becomes -1)
+        for e, part in zip(self.engines, parts):
+            e.copy_robots(part)
+
     def evaluate_done(self, rule):
         """Engine.evaluate_done over the shards: masks and reasons concatenated in shard_range order, counts summed."""
         import numpy as np

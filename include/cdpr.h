@@ -232,6 +232,32 @@ int cdpr_set_platform_state(cdpr_handle_t h, const float *pose7, const float *tw
 int cdpr_reset_robots(cdpr_handle_t h, const uint8_t *robot_mask, const float *pose7, const float *twist6);
 int cdpr_reset_robots_device(cdpr_handle_t h, const uint8_t *d_robot_mask, const float *d_pose7, const float *d_twist6);
 
+/* Fork robots: robot r continues from where robot s = source[r] is NOW (particle-filter resampling, MPPI / CEM with a stateful plant,
+ * population search, restart-from-the-best).  New exports after ABI 8, no struct changes.
+ *   the map    int32[B].  Robot r with 0 <= source[r] < B and source[r] != r is a DESTINATION; every other robot - a negative entry or
+ *              r itself means "leave me" - is untouched: to the bit, never written, read only as somebody's source.  A source must
+ *              itself be untouched (source[s] < 0 or source[s] == s): sources are only read, destinations only written, so one launch
+ *              needs no scratch copy.  In-place resampling has this shape (survivors keep their index); one source may feed many.
+ *   a copy     after the call every getter returns for r, to the bit, what it returns for s - cdpr_get_raw_state[_f64], the joint-state,
+ *              observable, FK, TD, limit and `pid` debug getters, cdpr_get_episode_start, the environment view - and from then on r and
+ *              s advance identically for as long as they receive the same commands, through every launch form.  Everything
+ *              robot-indexed the handle owns moves: platform, FK estimate, observable image, `pid` row, both Pids' records with
+ *              their rings, integrals, stamps and hot rows, mode and call count, the active target / latched command rows, the
+ *              episode clock.
+ *   untouched  the world-step counter and the publish clock, the status word, caller-bound buffers, and every PENDING command: it is
+ *              addressed to an index and is latched onto whoever sits there at the next cdpr_update, exactly as after a reset.
+ * Source and destination share the world step, so nothing is rebased: a fork at one instant, not a checkpoint across time.
+ * Stream-ordered after every update queued so far, before every later one; no host wait, no step launch: cdpr_kernel_name and
+ * cdpr_plan_kernel do not see it.  Needs per_robot_commands = 1 (the handles cdpr_reset_robots_device serves, every record layout,
+ * precision = 64 included), else CDPR_ERR_UNSUPPORTED with nothing changed.  NULL handle or map: CDPR_ERR_INVALID.
+ * cdpr_copy_robots_device: d_source on the device, nothing copied or synchronised; it must stay valid until the stream has passed
+ *   the copy.  A destination whose source is out of range (>= B) or is itself a destination is SKIPPED - left as it was - and counted:
+ *   d_status is uint32[2] = [robots copied, destinations skipped], zeroed on the stream in front of the kernel, or NULL (no counting).
+ * cdpr_copy_robots: a host map, validated first - any entry the device form would skip returns CDPR_ERR_INVALID with nothing changed -
+ *   then copied before the call returns and queued; the stream is not waited for. */
+int cdpr_copy_robots_device(cdpr_handle_t h, const int32_t *d_source, uint32_t *d_status);
+int cdpr_copy_robots(cdpr_handle_t h, const int32_t *source);
+
 /* Done rules: which robots a loop should put back, decided on the device.  cdpr_reset_robots_device takes a "done" mask that lives
  * on the GPU; these calls compute it there, from the state the handle already holds, so that a Monte-Carlo sweep, an RL-style
  * environment batch or an MPC loop never brings the state to the host to find out who has diverged.
