@@ -6,7 +6,7 @@
 // the platform in slots 0-3 and the flags in observable slot 3) and the double rows of the precision = 64 handles.  No controller
 // record is read, so hot rows, record layouts and the cable count do not matter here.
 //
-// As the latch and reset kernels (cdpr_latch.hpp, cdpr_reset.hpp): one thread per robot, 256 per block, every load row * stride + r
+// As the latch, reset and copy kernels (cdpr_robot_records.hpp): one thread per robot, 256 per block, every load row * stride + r
 // (a wave reads whole rows: 80 B per robot in float, 136 B in double, 4 B of episode start), no LDS, no scratch.  Straight-line: a
 // test the rule leaves disabled is computed and masked out by the wave-uniform `enable` word; the lanes past the batch read robot
 // B - 1 and contribute nothing.  Counts: one ballot and one popcount per enabled reason, lane 0 of each wave adds the non-zero ones
@@ -77,15 +77,9 @@ CDPR_DEV void done_store(const DoneOut& o, uint32_t enable, uint32_t r, bool liv
     if (o.reason) o.reason[r] = reason;
   }
   if (!o.counts) return;  // (wave-uniform, as `enable` below)
-  const bool lane0 = (threadIdx.x & 63u) == 0u;
-  const uint32_t any = (uint32_t)__popcll(__ballot(reason != 0u));
-  if (lane0 && any) atomicAdd(o.counts, any);
-  if (!any) return;
-  for (uint32_t k = 0; k + 1u < (uint32_t)CDPR_DONE_COUNTS; ++k) {
-    if (!((enable >> k) & 1u)) continue;
-    const uint32_t c = (uint32_t)__popcll(__ballot((reason >> k) & 1u));
-    if (lane0 && c) atomicAdd(o.counts + 1u + k, c);
-  }
+  if (!wave_count_add(o.counts, reason != 0u)) return;
+  for (uint32_t k = 0; k + 1u < (uint32_t)CDPR_DONE_COUNTS; ++k)
+    if ((enable >> k) & 1u) wave_count_add(o.counts + 1u + k, (reason >> k) & 1u);
 }
 
 #ifndef CDPR_DONE_NO_KERNELS  // (cdpr_env.hpp takes done_reason and done_store and leaves the two kernels to cdpr_engine_done.hip)

@@ -200,10 +200,12 @@ void free_all(cdpr_engine* h) {
   (void)hipSetDevice(h->device);
   if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
   h->graphs.clear();
-  for (CmdChannel& c : h->cmd)
-    for (hipEvent_t ev : {c.stage_ev[0], c.stage_ev[1], c.free_ev})
-      if (ev) (void)hipEventDestroy(ev);
-  for (hipEvent_t ev : {h->ev0, h->ev1, h->reset_ev[0], h->reset_ev[1], h->copy_ev[0], h->copy_ev[1]})
+  for (CmdChannel& c : h->cmd) {
+    c.stage.clear();
+    if (c.free_ev) (void)hipEventDestroy(c.free_ev);
+  }
+  h->reset_stage.clear(), h->copy_stage.clear();
+  for (hipEvent_t ev : {h->ev0, h->ev1})
     if (ev) (void)hipEventDestroy(ev);
   for (hipStream_t st : {h->copy_stream, h->stream})
     if (st) (void)hipStreamDestroy(st);
@@ -258,24 +260,14 @@ int stage_command(cdpr_engine* h, int kind, const float* src, size_t count, bool
   }
   // host source: rows -> pinned staging -> pending device buffer on the copy stream, no wait for the launches in flight
   if (!h->copy_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-  const int idx = (c.stage_idx ^= 1);
-  if (!c.h_stage[idx]) {
-    HIP_TRY(h, c.h_stage[idx].alloc(bytes, hipHostMallocDefault));
-    HIP_TRY(h, hipEventCreateWithFlags(&c.stage_ev[idx], hipEventDisableTiming));
-  }
   if (!c.free_ev) HIP_TRY(h, hipEventCreateWithFlags(&c.free_ev, hipEventDisableTiming));
-  if (c.stage_ev_set[idx]) HIP_TRY(h, hipEventSynchronize(c.stage_ev[idx]));  // two commands back: long done
-  float* stage = c.h_stage[idx];
-  if (count == n * B) {
-    memcpy(stage, src, bytes);  // the caller may reuse its buffer on return
-  } else {
-    for (size_t b = 0; b < B; ++b) memcpy(stage + b * n, src, n * sizeof(float));
-  }
-  if (c.free_ev_set) HIP_TRY(h, hipStreamWaitEvent(h->copy_stream, c.free_ev, 0));
-  HIP_TRY(h, hipMemcpyAsync(dst, stage, bytes, hipMemcpyHostToDevice, h->copy_stream));
-  HIP_TRY(h, hipEventRecord(c.stage_ev[idx], h->copy_stream));
-  c.stage_ev_set[idx] = true;
-  c.ready_wait = c.stage_ev[idx];
+  const auto fill = [&](char* stage) {  // the whole batch, or one row for every robot
+    if (count == n * B) memcpy(stage, src, bytes);
+    else
+      for (size_t b = 0; b < B; ++b) memcpy(stage + b * n * sizeof(float), src, n * sizeof(float));
+  };
+  HIP_TRY(h, c.stage.send(dst, bytes, h->copy_stream, fill, c.free_ev_set ? c.free_ev : nullptr));  // (behind every launch that read this buffer)
+  c.ready_wait = c.stage.sent();
   return CDPR_OK;
 }
 

@@ -43,8 +43,8 @@ int ensure_done_scratch(cdpr_engine* h) {
 // Queue the verdict behind every update queued so far: d_mask uint8[B], d_reason uint32[B] or null, d_counts uint32[CDPR_DONE_COUNTS]
 // or null (zeroed on the stream first).  The step count goes in by value, as into the step kernels.
 static int launch_done(cdpr_engine* h, const cdpr_done_rule_t& rule, uint8_t* d_mask, uint32_t* d_reason, uint32_t* d_counts) {
-  if (d_counts) HIP_TRY(h, hipMemsetAsync(d_counts, 0, CDPR_DONE_COUNTS * sizeof(uint32_t), h->stream));
-  const dim3 grid((h->batch + 255u) / 256u), block(256);
+  if (int rc = zero_counts(h, d_counts, CDPR_DONE_COUNTS)) return rc;
+  const dim3 grid = robot_grid(h), block(kRobotBlock);
   DoneOut out{};
   out.mask = d_mask, out.reason = d_reason, out.counts = d_counts;
   if (h->plan.fp64) {
@@ -102,10 +102,7 @@ int cdpr_evaluate_done(cdpr_handle_t h, const cdpr_done_rule_t* rule, uint8_t* m
 int cdpr_reset_done_device(cdpr_handle_t h, const cdpr_done_rule_t* rule, const float* d_pose7, const float* d_twist6, uint32_t* d_counts) {
   if (!h) return CDPR_ERR_INVALID;
   if (int rc = done_checks(h, rule, "cdpr_reset_done_device")) return rc;
-  if (!h->plan.per_robot) {  // (as cdpr_reset_robots_device)
-    h->err = "cdpr_reset_done_device needs a handle created with per_robot_commands = 1";
-    return CDPR_ERR_UNSUPPORTED;
-  }
+  if (int rc = per_robot_checks(h, "cdpr_reset_done_device")) return rc;
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
   if (int rc = ensure_done_scratch(h)) return rc;
   uint8_t* const d_mask = reinterpret_cast<uint8_t*>(h->d_done.p);

@@ -43,7 +43,7 @@ static int obs_checks(cdpr_engine* h, uint32_t fields, uint32_t& ld, bool wanted
 // Queue the view behind every update queued so far.  v: rule, weights, target and outputs as the caller gave them; the rest is filled
 // here.  The step count goes in by value, as into the step kernels.
 static int launch_env(cdpr_engine* h, EnvView v, uint32_t fields, uint32_t ld) {
-  if (v.out.counts) HIP_TRY(h, hipMemsetAsync(v.out.counts, 0, CDPR_DONE_COUNTS * sizeof(uint32_t), h->stream));
+  if (int rc = zero_counts(h, v.out.counts, CDPR_DONE_COUNTS)) return rc;
   v.fields = v.obs ? fields : 0u;
   v.width = env_columns(v.fields, h->n, v.col);
   v.ld = ld;

@@ -1,5 +1,6 @@
 // cdpr_engine_internal.hpp - what the translation units of the host side share: the owners of device and pinned memory and of the
-// captured graphs (DevBuf, PinnedBuf, GraphCache), the handle (struct cdpr_engine: its routing is h->plan and nothing else, its
+// captured graphs (DevBuf, PinnedBuf, StagePair, GraphCache), the views of a per-robot handle's records with the one launch helper
+// of the kernels over chosen robots (fast_records / gen_records / f64_records, launch_per_robot), the handle (struct cdpr_engine: its routing is h->plan and nothing else, its
 // buffers are owner members that go with it), the error macros and the helpers one unit defines and another calls.  Units:
 // cdpr_engine.hip (create / destroy, the general path's set-up, the command setters, read-out, the extern "C" wrappers),
 // cdpr_engine_launch.hip (what turns "advance n world steps" into launches: the latch, the chain and its clock, the fp32 and
@@ -23,7 +24,7 @@
 #include "../../include/cdpr.h"
 #include "cdpr_kernels.hpp"
 #include "cdpr_select.hpp"
-#include "cdpr_latch.hpp"
+#include "cdpr_robot_records.hpp"
 #include "cdpr_solvers.hpp"
 
 using namespace cdpr;
@@ -101,6 +102,43 @@ struct PinnedBuf {
   operator T*() const { return p; }
 };
 
+// ... and of two pinned blocks that take turns on the way to the device, each with the event of its last copy: what a host-form call
+// hands over goes into the free block (the caller's arrays are its own again on return) and from there to the device on a stream.
+// The call that fills a block waits only for the copy of two calls back, never for the stream.  Allocated at first use (every use of
+// one StagePair sends the same number of bytes).
+struct StagePair {
+  PinnedBuf<char> block[2];
+  hipEvent_t ev[2] = {nullptr, nullptr};  // the copy out of that block has completed
+  bool ev_set[2] = {false, false};
+  int idx = 0;
+  StagePair() = default;
+  StagePair(const StagePair&) = delete;
+  StagePair& operator=(const StagePair&) = delete;
+  ~StagePair() { clear(); }
+  void clear() {  // (before the streams go: free_all)
+    for (int i = 0; i < 2; ++i) {
+      if (ev[i]) (void)hipEventDestroy(ev[i]);
+      ev[i] = nullptr, ev_set[i] = false;
+    }
+  }
+  // fill(char*) writes `bytes` into the free block, which then travels to d_dst on `stream` - behind `after`, if one is given (queued
+  // right in front of the copy, so that the two reach the stream together)
+  template <typename Fill>
+  hipError_t send(void* d_dst, size_t bytes, hipStream_t stream, Fill&& fill, hipEvent_t after = nullptr) {
+    idx ^= 1;
+    hipError_t e = block[idx] ? hipSuccess : block[idx].alloc(bytes, hipHostMallocDefault);
+    if (e == hipSuccess && !ev[idx]) e = hipEventCreateWithFlags(&ev[idx], hipEventDisableTiming);
+    if (e == hipSuccess && ev_set[idx]) e = hipEventSynchronize(ev[idx]);  // two calls back: long done
+    if (e != hipSuccess) return e;
+    fill(block[idx].p);
+    if (after && (e = hipStreamWaitEvent(stream, after, 0)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(d_dst, block[idx], bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+    if ((e = hipEventRecord(ev[idx], stream)) == hipSuccess) ev_set[idx] = true;
+    return e;
+  }
+  hipEvent_t sent() const { return ev[idx]; }  // the copy of the last send() has completed
+};
+
 // ... and of the captured hipGraphs of a handle: chains of identical steady-state launches (run_steps), found again by what makes
 // two chains the same launches - kernel, command pointer, steps per launch, flags and the ring slot the chain starts from.
 struct GraphKey {
@@ -160,10 +198,7 @@ struct CmdChannel {
   // Host-side Joy batches travel on their own stream (cdpr_set_*_command with a host pointer): the caller's rows go into
   // one of two pinned staging buffers and from there to the PENDING device buffer while earlier launches still
   // run; the call returns without waiting.
-  PinnedBuf<float> h_stage[2];
-  hipEvent_t stage_ev[2] = {nullptr, nullptr};  // the copy out of that staging buffer has completed
-  bool stage_ev_set[2] = {false, false};
-  int stage_idx = 0;
+  StagePair stage;
   hipEvent_t ready_wait = nullptr;  // event the compute stream has to pass before it touches the pending buffer
   hipEvent_t free_ev = nullptr;     // every launch that read what is now the pending buffer has completed
   bool free_ev_set = false;
@@ -232,7 +267,7 @@ struct cdpr_engine {
   DevBuf<uint8_t> d_mode;           // uint8[B]: 1 = Position, 2 = Velocity; on the register-resident path also the robot's
                                     // Pid call count in bits 2-7 (StepArgs::meta)
   DevBuf<float> d_target;           // per-robot handles on the register-resident path: float[B][n], every robot's ACTIVE target row
-  hipStream_t copy_stream = nullptr;  // host-side Joy batches travel on their own stream (CmdChannel::h_stage)
+  hipStream_t copy_stream = nullptr;  // host-side Joy batches travel on their own stream (CmdChannel::stage)
   int mode = kModePosition;
   uint64_t step = 0;
   double prev_publish = 0.0;
@@ -251,19 +286,13 @@ struct cdpr_engine {
   DevBuf<float> d_roll_ref;      // float[B][3]
   DevBuf<float> d_roll_cost;     // float[B][samples]
   uint64_t roll_pending = 0;     // trajectories of the launched, not yet fetched rollout
-  // cdpr_reset_robots (host form): the caller's mask, poses and twists go through one of two pinned staging blocks into persistent
-  // device scratch on the handle's stream ([uint8 mask[B], padded to 16 B | float pose[B][7] | float twist[B][6]], sized once: B is fixed)
+  // cdpr_reset_robots (host form): the caller's mask, poses and twists go through a pinned staging pair into persistent device
+  // scratch on the handle's stream ([uint8 mask[B], padded to 16 B | float pose[B][7] | float twist[B][6]], sized once: B is fixed)
   DevBuf<char> d_reset_args;
-  PinnedBuf<char> h_reset_stage[2];
-  hipEvent_t reset_ev[2] = {nullptr, nullptr};  // the copy out of that staging block has completed
-  bool reset_ev_set[2] = {false, false};
-  int reset_idx = 0;
+  StagePair reset_stage;
   // cdpr_copy_robots (host form): the caller's source map, staged the same way (int32[B], sized once)
   DevBuf<int32_t> d_copy_map;
-  PinnedBuf<int32_t> h_copy_stage[2];
-  hipEvent_t copy_ev[2] = {nullptr, nullptr};
-  bool copy_ev_set[2] = {false, false};
-  int copy_idx = 0;
+  StagePair copy_stage;
   // episode clock: uint32[stride], the world step (low word) of every robot's last model reset; zero after create / cdpr_reset and
   // on uniform handles.  d_done: scratch of cdpr_evaluate_done's host form and the mask of cdpr_reset_done_device
   // ([uint8 mask[B], padded to 16 B | uint32 reason[B] | uint32 counts[CDPR_DONE_COUNTS]], sized once)
@@ -429,6 +458,83 @@ int set_platform_state64(cdpr_engine* h, const double* pose7, const double* twis
 int fetch_int_row64(cdpr_engine* h, uint32_t row, int32_t* out);
 void decode_image64_to_float(const cdpr_engine* h, const double* image, float* position, float* velocity, float* effort, float* pose7, float* twist6);
 int rollout_enqueue_f64(cdpr_engine* h, int samples, int horizon, const float* d_commands, const float* d_ref, float* d_cost);
+
+// The handle as the kernels that act on chosen robots see it (cdpr_robot_records.hpp), one builder per record layout: the only
+// places that say where a robot's records are.
+inline PlatRows plat_rows(const cdpr_engine* h) {
+  return PlatRows{h->d_state, h->d_obs, h->dbg ? h->d_dbg.p : nullptr, h->stride, (uint32_t)h->n_state, (uint32_t)h->n_obs, h->plan.fk ? 1u : 0u};
+}
+inline FastRecords fast_records(const cdpr_engine* h) {
+  FastRecords v{};
+  v.plat = plat_rows(h);
+  v.integral = h->d_state + (size_t)(plat_slots(h->plan.fk) + 5 * cable_pairs((int)h->n)) * h->stride;
+  v.integral_rows = (uint32_t)((cable_pairs((int)h->n) + 1) / 2);
+  v.meta = h->d_mode, v.target = h->d_target, v.episode_start = h->d_episode;
+  v.batch = h->batch, v.n = h->n;
+  return v;
+}
+inline GenRecords gen_records(const cdpr_engine* h) {
+  GenRecords v{};
+  v.plat = plat_rows(h);
+  v.rec = h->d_rec, v.lay = h->glay;
+  v.mode = h->d_mode, v.episode_start = h->d_episode;
+  for (int k = 0; k < kCmdKinds; ++k) v.latched[k] = h->cmd[k].d[0];
+  v.batch = h->batch, v.n = h->n;
+  return v;
+}
+inline F64Records f64_records(const cdpr_engine* h) {
+  F64Records v{};
+  v.state = h->d_state64, v.obs = h->d_obs64, v.dbg = h->d_dbg64;
+  v.meta = h->d_mode, v.target = h->d_target, v.episode_start = h->d_episode;
+  v.stride = h->stride, v.state_rows = (uint32_t)state64_rows(h), v.obs_rows = (uint32_t)f64_obs_rows((int)h->n);
+  v.batch = h->batch, v.n = h->n;
+  v.hold = h->plan.hold64 ? 1u : 0u, v.hold_win = (uint32_t)hold_win(h), v.win = (uint32_t)win64(h);
+  for (int c = 0; c < 7; ++c) v.home[c] = h->cfg.home_pose[c];
+  return v;
+}
+
+// one thread per robot, 256 per block (the latch, reset, copy and verdict kernels)
+constexpr uint32_t kRobotBlock = 256u;
+inline dim3 robot_grid(const cdpr_engine* h) { return dim3((h->batch + kRobotBlock - 1u) / kRobotBlock); }
+
+// `who` over the robots of a per-robot handle, on the handle's stream: one launch of the kernel of the handle's record layout.
+// settle_commands: the launch writes rows of the general path's LATCHED command buffers from outside a latch (a model reset, a
+// copy): whatever the copy stream still carries has landed first, as in front of the masked setters.
+template <typename Who, typename KFast, typename KGen, typename KF64>
+int launch_per_robot(cdpr_engine* h, const Who& who, KFast fast, KGen gen, KF64 f64, bool settle_commands) {
+  const dim3 grid = robot_grid(h), block(kRobotBlock);
+  if (h->plan.fp64) {
+    hipLaunchKernelGGL(f64, grid, block, 0, h->stream, who, f64_records(h));
+  } else if (!h->plan.general) {
+    hipLaunchKernelGGL(fast, grid, block, 0, h->stream, who, fast_records(h));
+  } else {
+    if (settle_commands)
+      if (int rc = drain_copy_stream(h)) return rc;
+    hipLaunchKernelGGL(gen, grid, block, 0, h->stream, who, gen_records(h));
+  }
+  HIP_TRY(h, hipGetLastError());
+  return CDPR_OK;
+}
+
+// counts a verdict kernel adds to (cdpr_done.hpp, copy_verdict): zeroed on the stream in front of the launch; null: none wanted
+inline int zero_counts(cdpr_engine* h, uint32_t* d_counts, size_t count) {
+  if (d_counts) HIP_TRY(h, hipMemsetAsync(d_counts, 0, count * sizeof(uint32_t), h->stream));
+  return CDPR_OK;
+}
+
+// What every call that acts on chosen robots refuses: a uniform handle (it keeps ONE mode and one Pid call count for the whole
+// batch), and `missing`, the name of a required argument that came as null.
+inline int per_robot_checks(cdpr_engine* h, const char* what, const char* missing = nullptr) {
+  if (!h->plan.per_robot) {
+    h->err = std::string(what) + " needs a handle created with per_robot_commands = 1";
+    return CDPR_ERR_UNSUPPORTED;
+  }
+  if (missing) {
+    h->err = std::string(what) + ": null " + missing;
+    return CDPR_ERR_INVALID;
+  }
+  return CDPR_OK;
+}
 
 // The loop every path runs (fp32 and general: cdpr_engine_launch.hip, precision = 64: cdpr_engine_f64.hip): the steps of this launch,
 // the first-world-step flag, the record moved on by the images done, the publish mask; then the path fills and launches (`path`:

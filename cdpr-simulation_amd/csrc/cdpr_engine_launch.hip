@@ -4,6 +4,30 @@
 // schedules (scheduled_update).  Reference paths as in cdpr_engine.hip.
 #include "cdpr_engine_internal.hpp"
 
+namespace cdpr {
+
+// Per-robot command arrival (latch_robot, cdpr_robot_records.hpp): one thread per robot, one kernel per record layout
+template <typename View>
+CDPR_DEV void latch_thread(const LatchWho& who, const View& v) {
+  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+  if (latch_wanted(who, v.batch, r)) latch_robot(who, v, r);
+}
+static __global__ __launch_bounds__(256) void cdpr_latch_fast_kernel(const LatchWho who, const FastRecords v) { latch_thread(who, v); }
+static __global__ __launch_bounds__(256) void cdpr_gen_latch_kernel(const LatchWho who, const GenRecords v) { latch_thread(who, v); }
+static __global__ __launch_bounds__(256) void cdpr_latch_f64_kernel(const LatchWho who, const F64Records v) { latch_thread(who, v); }
+
+// ... and the general path's hot rows back into the H slots, every robot's
+static __global__ __launch_bounds__(256) void cdpr_gen_flush_hot_kernel(const int nbuf, const GenRecords v) {
+  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+  if (r < v.batch) flush_hot_robot(v, nbuf, r);
+}
+
+// cdpr_update_scheduled_kind served as a chain of launches: one thread waits for the mailbox word of the next batch in front
+// of the batch's latch (what sched_wait does inside a launch that carries the schedule itself).
+static __global__ void cdpr_mailbox_wait_kernel(const uint32_t* word, uint32_t* fault) { mailbox_wait(word, fault); }
+
+}  // namespace cdpr
+
 namespace cdpr_host {
 
 double sim_time(uint64_t step, double dt) {
@@ -224,9 +248,7 @@ static int launch_step(cdpr_engine* h, StepKernel kern, uint32_t robots_per_bloc
 // the general path's hot rows back into the H slots (cdpr_gen_flush_hot_kernel) before a Pid's records are reset or latched over
 static void flush_hot(cdpr_engine* h) {
   if (!h->d_rec || !h->plan.gen_hot) return;
-  GenFlushArgs fa{};
-  fa.rec = h->d_rec, fa.rstride = h->stride, fa.batch = h->batch, fa.lay = h->glay, fa.nbuf = std::max(h->gpid[0].nbuf, 1);
-  hipLaunchKernelGGL(cdpr_gen_flush_hot_kernel, dim3((h->batch + 255u) / 256u), dim3(256), 0, h->stream, fa);
+  hipLaunchKernelGGL(cdpr_gen_flush_hot_kernel, robot_grid(h), dim3(kRobotBlock), 0, h->stream, std::max(h->gpid[0].nbuf, 1), gen_records(h));
 }
 
 // Pid::reset of one Pid of every cable (general path): its slots, its rows
@@ -249,56 +271,12 @@ static hipError_t reset_block64(cdpr_engine* h, int which) {
 }
 
 // Per-robot handles: every robot has its own mode, so a command of `kind` (masked or not) is latched on the device, robot by
-// robot, by the latch kernel of the handle's path: precision = 64, register-resident, general.
+// robot, by the latch kernel of the handle's record layout.  (The general path's latch zeroes a Pid's records for many robots at
+// once: its hot rows are flushed first.  Nothing is drained: what the latch reads has passed ready_wait, latch_pending.)
 static int latch_per_robot(cdpr_engine* h, int kind, const float* pending, const uint8_t* mask) {
   const CmdKind& K = kCmdKind[kind];
-  const dim3 grid((h->batch + 255u) / 256u), block(256);
-  if (h->plan.fp64) {  // the same on the double state (integral rows 20 + 11 i + 10)
-    LatchF64Args lf{};
-    lf.mask = mask;
-    lf.meta = h->d_mode;
-    lf.pending = pending;
-    lf.target = h->d_target;
-    lf.state = h->d_state64;
-    lf.stride = h->stride;
-    lf.batch = h->batch;
-    lf.n = h->n;
-    lf.new_mode = K.meta;
-    lf.hold = h->plan.hold64 ? 1u : 0u;
-    lf.win = (uint32_t)win64(h);
-    lf.hold_win = (uint32_t)hold_win(h);
-    hipLaunchKernelGGL(cdpr_latch_f64_kernel, grid, block, 0, h->stream, lf);
-  } else if (!h->plan.general) {  // one active target row and one Pid record per robot
-    LatchFastArgs lf{};
-    lf.mask = mask;
-    lf.meta = h->d_mode;
-    lf.pending = pending;
-    lf.target = h->d_target;
-    lf.hot = h->d_state + (size_t)(plat_slots(h->plan.fk) + 5 * cable_pairs((int)h->n)) * h->stride;
-    lf.stride = h->stride;
-    lf.batch = h->batch;
-    lf.n = h->n;
-    lf.hot_rows = (uint32_t)((cable_pairs((int)h->n) + 1) / 2);
-    lf.new_mode = K.meta;
-    hipLaunchKernelGGL(cdpr_latch_fast_kernel, grid, block, 0, h->stream, lf);
-  } else {
-    flush_hot(h);
-    GenLatchArgs la{};
-    la.mask = mask;
-    la.mode = h->d_mode;
-    la.pending = pending;
-    la.latched = h->cmd[kind].d[0];
-    la.rec = h->d_rec;
-    la.rstride = h->stride;
-    la.batch = h->batch;
-    la.n = h->n;
-    la.reset_pid = K.reset_pid;  // (-1: setForce resets no Pid)
-    la.lay = h->glay;
-    la.new_mode = K.mode;
-    hipLaunchKernelGGL(cdpr_gen_latch_kernel, grid, block, 0, h->stream, la);
-  }
-  HIP_TRY(h, hipGetLastError());
-  return CDPR_OK;
+  if (h->plan.general) flush_hot(h);
+  return launch_per_robot(h, LatchWho{mask, pending, (uint32_t)kind, K.meta, K.reset_pid}, cdpr_latch_fast_kernel, cdpr_gen_latch_kernel, cdpr_latch_f64_kernel, false);
 }
 
 // PLG.cpp:206-219: an update starts by latching the pending commands, velocity first, then position; force after the two

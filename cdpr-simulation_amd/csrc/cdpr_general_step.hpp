@@ -1675,61 +1675,4 @@ __global__ __launch_bounds__(64, 1) void cdpr_gen_step_kernel(const StepArgs a, 
   CDPR_STAMP(7);
 }
 
-// Per-robot command arrival on the general path (cdpr_set_*_command_masked; PLG.cpp:206-219 per model): one thread per
-// robot copies the Joy's row into the latched buffer of its kind, and entering the mode from another one resets that
-// mode's Pid (JFC.cpp:101-103,113-115) = zero the robot's column of the Pid's slots and rows.  setForce resets nothing.
-struct GenLatchArgs {
-  const uint8_t* mask;   // uint8[B], or nullptr = every robot
-  uint8_t* mode;         // per-robot mode
-  const float* pending;  // float[B][n]
-  float* latched;        // float[B][n]
-  float* rec;
-  uint32_t rstride, batch, n;
-  int reset_pid;         // 0 / 1: the Pid whose records this mode owns; -1: none (setForce)
-  GenLayout lay;
-  int new_mode;
-};
-
-// The hot rows (GenHot) written back: every robot with a valid word gets the H slots of its word's Pids as they stand and
-// its word cleared.  Runs in front of anything that resets a Pid's records from outside the step kernels (a mode change),
-// so that those see - and zero - plain records.
-struct GenFlushArgs {
-  float* rec;
-  uint32_t rstride, batch;
-  GenLayout lay;
-  int nbuf;
-};
-static __global__ __launch_bounds__(256) void cdpr_gen_flush_hot_kernel(const GenFlushArgs a) {
-  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  if (r >= a.batch) return;
-  uint32_t* const c = reinterpret_cast<uint32_t*>(a.rec) + ((size_t)a.lay.slots() * 4 + (size_t)a.lay.rows()) * a.rstride + r;
-  const uint32_t step1 = c[0];
-  if (step1 == 0u) return;
-  const uint32_t mask = c[a.rstride];
-  const int step = (int)step1 - 1;
-  const uint32_t meta = kGmWasLast | ((uint32_t)a.nbuf << kGmCountShift) | ((uint32_t)(step % a.nbuf) << kGmHeadShift) | (kGmField << kGmRunShift);
-  float4* const slots = reinterpret_cast<float4*>(a.rec);
-  for (int i = 0; i < a.lay.n; ++i) {
-    const float ierr = __uint_as_float(c[(size_t)(2 + i) * a.rstride]);
-    slots[(size_t)(a.lay.block_a((int)((mask >> i) & 1u), i) + a.lay.nv()) * a.rstride + r] = make_float4(__uint_as_float(meta), __int_as_float(step), ierr, 0.f);
-  }
-  c[0] = 0u;
-}
-
-static __global__ __launch_bounds__(256) void cdpr_gen_latch_kernel(const GenLatchArgs a) {
-  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  if (r >= a.batch) return;
-  if (a.mask && !a.mask[r]) return;
-  for (uint32_t i = 0; i < a.n; ++i) a.latched[(size_t)r * a.n + i] = a.pending[(size_t)r * a.n + i];
-  if ((int)a.mode[r] != a.new_mode) {
-    if (a.reset_pid >= 0) {
-      float4* sa = reinterpret_cast<float4*>(a.rec) + (size_t)a.lay.block_a(a.reset_pid, 0) * a.rstride + r;
-      for (int sl = 0; sl < a.lay.pid_slots(); ++sl) sa[(size_t)sl * a.rstride] = make_float4(0.f, 0.f, 0.f, 0.f);
-      float* rb = a.rec + (size_t)a.lay.slots() * a.rstride * 4 + (size_t)a.lay.block_b(a.reset_pid, 0) * a.rstride + r;
-      for (int row = 0; row < a.lay.pid_rows(); ++row) rb[(size_t)row * a.rstride] = 0.f;
-    }
-    a.mode[r] = (uint8_t)a.new_mode;
-  }
-}
-
 }  // namespace cdpr

@@ -171,6 +171,13 @@ CDPR_DEV void mailbox_wait(const uint32_t* word, uint32_t* fault) {
 CDPR_DEV void sched_wait(const StepArgs& a, int j) {
   if (a.sched_ready) mailbox_wait(a.sched_ready + j, a.fault);
 }
+// The wave's lanes where `pred` holds, counted into *counter: one ballot and one popcount, lane 0 adds a non-zero count with an
+// ordinary atomicAdd.  Every lane of the wave comes through here.  Returns the count.  (Verdict kernels: cdpr_done.hpp, copy_verdict.)
+CDPR_DEV uint32_t wave_count_add(uint32_t* counter, bool pred) {
+  const uint32_t count = (uint32_t)__popcll(__ballot(pred));
+  if ((threadIdx.x & 63u) == 0u && count) atomicAdd(counter, count);
+  return count;
+}
 
 
 // Diagnostic build only (-DCDPR_STAMPS, scripts/stamp_probe.py): per-wave s_memrealtime stamps (100 MHz) at the

@@ -1033,43 +1033,6 @@ __global__ __launch_bounds__(64) void cdpr_step_kernel_f64(const F64Args a) {
   if (PR) a.meta[r] = (uint8_t)((meta & kMetaModeMask) | ((uint32_t)calls << kMetaCallShift));
 }
 
-// Per-robot command arrival on a precision = 64 handle (cdpr_set_*_command_masked; PLG.cpp:206-219 per model): what
-// cdpr_latch_fast_kernel does on the fp32 state - the Joy's row becomes the robot's active target, entering the mode from
-// another one resets its Pid (JFC.cpp:101-103,113-115: integral 0, call count 0), setForce resets nothing.
-struct LatchF64Args {
-  const uint8_t* mask;   // uint8[B], or nullptr = every robot
-  uint8_t* meta;
-  const float* pending;  // float[B][n]
-  float* target;         // float[B][n]
-  double* state;
-  size_t stride;
-  uint32_t batch, n;
-  uint32_t new_mode;     // kMetaForce / kMetaPosition / kMetaVelocity
-  uint32_t hold;         // HOLD handles: both Pids of every cable live in their own rows (f64_hold_row); entering a mode clears THAT Pid's
-  uint32_t hold_win;     // ... samples such a record's window holds (kHoldWin | kHoldWinLong)
-  uint32_t win;          // prior errors kept per cable (kWin, or kWinLong on handles with windows of 12 .. 32 samples): the integral is row 20 + (win + 1) i + win
-};
-static __global__ __launch_bounds__(256) void cdpr_latch_f64_kernel(const LatchF64Args a) {
-  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  if (r >= a.batch) return;
-  if (a.mask && !a.mask[r]) return;
-  for (uint32_t i = 0; i < a.n; ++i) a.target[(size_t)r * a.n + i] = a.pending[(size_t)r * a.n + i];
-  uint32_t m = a.meta[r];
-  if (a.new_mode == kMetaForce) {
-    m = (m & ~kMetaModeMask) | kMetaForce;
-  } else if ((m & kMetaModeMask) != a.new_mode) {
-    if (a.hold) {  // Pid::reset of the Pid of the mode entered (JFC.cpp:101-103,113-115), every cable: word, integral, window, stamps
-      const int pid = (a.new_mode == kMetaVelocity) ? 1 : 0;
-      for (uint32_t i = 0; i < a.n; ++i)
-        for (int row = 0; row < hold_pid_rows((int)a.hold_win); ++row) a.state[(size_t)(f64_hold_row((int)a.n, (int)i, pid, (int)a.hold_win) + row) * a.stride + r] = 0.0;
-    } else {
-      for (uint32_t i = 0; i < a.n; ++i) a.state[(size_t)(20 + (a.win + 1u) * i + a.win) * a.stride + r] = 0.0;
-    }
-    m = a.new_mode;  // call count 0
-  }
-  a.meta[r] = (uint8_t)m;
-}
-
 // cdpr_split_kernel_f64 - one step per launch with TWO waves per 64 robots, split by role like cdpr_split_kernel: FK + TD
 // handles, up to one workgroup per CU (117 KiB of LDS).  The step in double is one dependent chain of ~6 500 vector
 // instructions, 60 % of them the Newton stage: here the estimator wave (measured lengths, Newton-Raphson FK, the

@@ -68,7 +68,8 @@ def functions(text):
             l = l.split(";")[0].strip()
             if not l or l.startswith(".") or l.endswith(":"):
                 continue
-            ins.append(re.sub(r"\s+", " ", l))
+            # (.LBB<i>_<j>: block j of the unit's i-th function - i moves when a function in front of this one comes or goes)
+            ins.append(re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s+", " ", l)))
         occ = re.search(r"; Occupancy: (\d+)", tail)
         out[name] = (ins, int(occ.group(1)) if occ else -1)
     return out

@@ -66,6 +66,7 @@ def main():
                 continue
             dn = re.sub(r"^void cdpr::", "", dn).replace("cdpr::", "")
             dn = re.sub(r"\((StepArgs|F64Args|GenCtl|SolveArgs|[A-Za-z0-9_]+Args)(, GenCtl)?\)$", "", dn)
+            dn = re.sub(r"\((LatchWho|ResetWhere|CopyWho|int), (Fast|Gen|F64)Records\)$", "", dn)  # (the kernels over chosen robots: {who, view})
             print(f"{unit:13s} {dn[:84]:84s} S{r['sgpr']:<4d} V{r['vgpr']:<4d} A{r['agpr']:<4d} scratch {r['scratch']:<5d} occ {r['occ']} spillS {r['spill_s']:<4d} spillV {r['spill_v']:<4d} lds {r['lds']}")
             shown += 1
         print(f"# {unit}: {len(rows)} kernels, {shown} listed", file=sys.stderr)

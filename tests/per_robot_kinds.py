@@ -1,0 +1,62 @@
+"""The nine kinds of per-robot handle the tests of the calls over chosen robots run on (reset_robots, copy_robots, the done rules, the
+environment view): three per record layout - register-resident per-robot records, the general path's record buffer, the
+precision = 64 rows - with the Config that makes each, the environment switches it needs and what kernel_name must then hold.
+
+B = 130: two full wavefronts and a ragged one, stride 192.
+"""
+import pytest
+
+import test_reset_robots_inputs as ri
+
+B = ri.B
+EPS = ri.EPS
+
+# handle kind: (cables, Config arguments, environment switches, what kernel_name must hold)
+HANDLES = {
+    "fast_n8": (8, dict(stages=3), {}, ("cdpr_split_kernel<8, true>",)),  # the role-split per-robot kernel
+    "fast_n4": (4, dict(stages=0), {}, ("cdpr_step_kernel<4,", "PR")),
+    "fast_n7": (7, dict(stages=3), {}, ("cdpr_split_kernel<7, true>",)),  # the padding cable and the odd integral row
+    "general_n8": (8, dict(stages=3, velocityEpsilon=EPS), {}, ("cdpr_gen_split_kernel<8>",)),
+    "general_lean_hot": (8, dict(stages=3, velocityEpsilon=EPS), {"CDPR_GEN_SPLIT": "0", "CDPR_GEN_LEAN": "1"}, ("cdpr_gen_lean_kernel<8>", "hot rows")),
+    "general_long": (8, dict(stages=3), {}, ("cdpr_gen_step_kernel<8,", ", 32")),
+    "fp64_n8": (8, dict(stages=3, precision=64), {}, ("cdpr_step_kernel_f64<8, PR",)),
+    "fp64_hold_n8": (8, dict(stages=3, precision=64, velocityEpsilon=EPS), {}, ("cdpr_step_kernel_f64<8, PR, HOLD = 1",)),
+    "fp64_hold_long": (8, dict(stages=3, precision=64, velocityEpsilon=EPS), {}, ("cdpr_step_kernel_f64<8, PR, HOLD = 2, HW = 32",)),
+}
+ALL = list(HANDLES)
+LAYOUTS = ["fast_n8", "general_lean_hot", "fp64_hold_n8"]  # one handle per record layout
+
+
+@pytest.fixture(autouse=True)
+def clean_env(monkeypatch):
+    """(autouse in every module that imports it)"""
+    for k in ("CDPR_GEN_SPLIT", "CDPR_GEN_LEAN", "CDPR_GEN_HOT", "CDPR_MAPPING", "CDPR_NO_GRAPH"):
+        monkeypatch.delenv(k, raising=False)
+
+
+def config_of(pkg, kind, monkeypatch, per_robot=True, more_stages=0):
+    n, kw, env, _ = HANDLES[kind]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    kw = dict(kw, stages=kw["stages"] | more_stages)
+    cfg = pkg.Config(model=ri.model_of(pkg, n), batch=B, perRobotCommands=per_robot, **kw)
+    if kind.endswith("_long"):  # 32-sample derivative windows ...
+        for p in (cfg.velocityController, cfg.positionController):
+            p.dBufferLength, p.dDegree = 32, 2
+    if kind == "general_long":  # ... and a gentle loop through a biquad on the P and the D input of the velocity Pid (test_gpu_general_matrix.cascade_config)
+        for f in (cfg.velocityController.pFilter, cfg.velocityController.dFilter):
+            f.cascade, f.relCutoff, f.quality = 1, 0.05, 0.5
+        cfg.velocityController.pGain, cfg.velocityController.iGain, cfg.velocityController.dGain = 4.0, 40.0, 0.01
+    return cfg
+
+
+def named(eng, kind):
+    name = eng.kernel_name
+    assert all(part in name for part in HANDLES[kind][3]), (kind, name)
+
+
+def state_of(eng, cfg):
+    """raw_state, joint_states and observables (the doubles of a precision = 64 handle)"""
+    if cfg.precision == 64:
+        return eng.raw_state_f64() + eng.observables_f64()
+    return eng.raw_state() + eng.joint_states() + eng.observables()

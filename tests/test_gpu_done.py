@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import done_rules as dr
+import per_robot_kinds as prk
 import test_gpu_reset_robots as rr
 import test_reset_robots_inputs as ri
 
@@ -27,7 +28,7 @@ pytestmark = pytest.mark.gpu
 
 B = dr.B
 STRIDE = 192
-LAYOUTS = rr.LAYOUTS  # fast_n8, general_lean_hot, fp64_hold_n8
+LAYOUTS = prk.LAYOUTS  # fast_n8, general_lean_hot, fp64_hold_n8
 UNIFORM = {  # kind: (cables, Config arguments)
     "uniform_n8": (8, dict(stages=3)),
     "uniform_n4_pair": (4, dict(stages=0, mapping=2)),  # _abi.MAP_LANE_PAIR
@@ -36,10 +37,7 @@ UNIFORM = {  # kind: (cables, Config arguments)
 KINDS = LAYOUTS + list(UNIFORM)
 
 
-@pytest.fixture(autouse=True)
-def clean_env(monkeypatch):
-    for k in ("CDPR_GEN_SPLIT", "CDPR_GEN_LEAN", "CDPR_GEN_HOT", "CDPR_MAPPING", "CDPR_NO_GRAPH"):
-        monkeypatch.delenv(k, raising=False)
+clean_env = prk.clean_env  # (autouse here too)
 
 
 def config_of(pkg, kind, monkeypatch, model_edit=None, **extra):
@@ -48,7 +46,7 @@ def config_of(pkg, kind, monkeypatch, model_edit=None, **extra):
         n, kw = UNIFORM[kind]
         per_robot = False
     else:
-        n, kw, env, _ = rr.HANDLES[kind]
+        n, kw, env, _ = prk.HANDLES[kind]
         per_robot = True
         for k, v in env.items():
             monkeypatch.setenv(k, v)
@@ -260,7 +258,7 @@ def test_evaluation_changes_nothing(pkg, monkeypatch, kind):
     eng.evaluate_done_device(rule, d_mask, d_reason, d_counts)
     assert eng.kernel_name == name == twin.kernel_name, f"{kind}: an evaluation changed kernel_name"
     assert first[2][0] > 0  # (the rule decides something here: 20 steps against max_steps = 15)
-    for x, y in zip(rr.state_of(eng, cfg), rr.state_of(twin, cfg)):
+    for x, y in zip(prk.state_of(eng, cfg), prk.state_of(twin, cfg)):
         assert np.array_equal(x, y), f"{kind}: an evaluation changed the engine's state"
     assert not eng.episode_start().any()
     for step in range(20):
@@ -269,7 +267,7 @@ def test_evaluation_changes_nothing(pkg, monkeypatch, kind):
         if step % 7 == 0:
             eng.evaluate_done(rule)
     assert eng.kernel_name == twin.kernel_name and eng.step_count == twin.step_count == 40
-    for x, y in zip(rr.state_of(eng, cfg), rr.state_of(twin, cfg)):
+    for x, y in zip(prk.state_of(eng, cfg), prk.state_of(twin, cfg)):
         assert np.array_equal(x, y), f"{kind}: an engine evaluated every step drifts from its twin"
     eng.synchronize()
     for x in (d_mask, d_reason, d_counts):
@@ -353,7 +351,7 @@ def test_reset_done_device_is_evaluate_then_reset(pkg, monkeypatch, kind):
             assert np.array_equal(p[done], respawn[0][done]) and np.array_equal(t[done], twist[done]), kind
         for e in (one, two):
             e.update(5)
-        for x, y in zip(rr.state_of(one, cfg), rr.state_of(two, cfg)):
+        for x, y in zip(prk.state_of(one, cfg), prk.state_of(two, cfg)):
             assert np.array_equal(x, y), f"{kind}, round {rnd}: reset_done_device differs from evaluate_done_device + reset_robots_device"
     for e, *ptrs in bufs:
         e.synchronize()
@@ -429,7 +427,7 @@ def test_refusals(pkg, monkeypatch):
     assert L.cdpr_reset_done_device(None, C.byref(good), None, None, None) == INVALID
     # nothing was queued or written by a refused call
     assert (mask == 7).all() and (eng.device_download(d_mask, B, np.uint8) == 7).all() and not eng.episode_start().any()
-    for x, y in zip(rr.state_of(eng, cfg), rr.state_of(twin, cfg)):
+    for x, y in zip(prk.state_of(eng, cfg), prk.state_of(twin, cfg)):
         assert np.array_equal(x, y)
     eng.device_free(d_mask)
     eng.close(), twin.close()

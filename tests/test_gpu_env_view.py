@@ -20,8 +20,8 @@ import pytest
 
 import done_rules as dr
 import env_view as ev
+import per_robot_kinds as prk
 import test_gpu_done as gd
-import test_gpu_reset_robots as rr
 import test_reset_robots_inputs as ri
 
 pytestmark = pytest.mark.gpu
@@ -30,10 +30,7 @@ B, STRIDE, KINDS, LAYOUTS = gd.B, gd.STRIDE, gd.KINDS, gd.LAYOUTS
 SENTINEL = np.float32(-77.25)
 
 
-@pytest.fixture(autouse=True)
-def clean_env(monkeypatch):
-    for k in ("CDPR_GEN_SPLIT", "CDPR_GEN_LEAN", "CDPR_GEN_HOT", "CDPR_MAPPING", "CDPR_NO_GRAPH"):
-        monkeypatch.delenv(k, raising=False)
+clean_env = prk.clean_env  # (autouse here too)
 
 
 class Buffers:
@@ -266,7 +263,7 @@ def test_the_view_changes_nothing(pkg, monkeypatch, kind):
     eng.observe_device(every, d_obs, 0, d_mask)
     assert eng.kernel_name == name == twin.kernel_name and eng.step_count == twin.step_count == 20, f"{kind}: the view changed kernel_name or the step count"
     assert eng.device_download(d_counts, dr.COUNTS, np.uint32)[0] > 0  # (the rule decides something: 20 steps against max_steps = 15)
-    for x, y in zip(rr.state_of(eng, cfg), rr.state_of(twin, cfg)):
+    for x, y in zip(prk.state_of(eng, cfg), prk.state_of(twin, cfg)):
         assert np.array_equal(x, y), f"{kind}: the view changed the engine's state"
     assert not eng.episode_start().any()
     for step in range(20):
@@ -274,7 +271,7 @@ def test_the_view_changes_nothing(pkg, monkeypatch, kind):
         eng.env_evaluate_device(spec, 0, d_obs, d_reward, d_mask, d_reason, d_counts)
         eng.observe_device(every, d_obs, 0, d_mask if step % 2 else 0)
     assert eng.kernel_name == twin.kernel_name and eng.step_count == twin.step_count == 40
-    for x, y in zip(rr.state_of(eng, cfg), rr.state_of(twin, cfg)):
+    for x, y in zip(prk.state_of(eng, cfg), prk.state_of(twin, cfg)):
         assert np.array_equal(x, y), f"{kind}: an engine viewed every step drifts from its twin"
     assert np.array_equal(eng.episode_start(), twin.episode_start())
     bufs.free()
@@ -320,7 +317,7 @@ def test_the_closed_loop_without_a_host_read(pkg, monkeypatch, kind):
     print(f"env view, closed loop, {kind}: robots reset per iteration {got_counts[:, 0].tolist()}")
     assert np.array_equal(got_counts.sum(axis=0, dtype=np.uint64), counts) and (got_counts[:, 0] > 0).sum() >= 3 and got_counts[:, 0].max() < B
     assert np.array_equal(dev.device_download(d_obs, (B, width), np.float32), tensor), f"{kind}: the final observation tensor differs"
-    for x, y in zip(rr.state_of(dev, cfg), rr.state_of(host, cfg)):
+    for x, y in zip(prk.state_of(dev, cfg), prk.state_of(host, cfg)):
         assert np.array_equal(x, y), f"{kind}: the device loop's final state differs from the host loop's"
     assert np.array_equal(dev.episode_start(), host.episode_start()) and dev.step_count == host.step_count == iterations
     bufs.free()
@@ -379,7 +376,7 @@ def test_refusals(pkg, monkeypatch):
     # nothing was queued or written by a refused call
     for k, v in canary.items():
         assert np.array_equal(eng.device_download(d[k].value, v.shape, v.dtype), v), k
-    for x, y in zip(rr.state_of(eng, cfg), rr.state_of(twin, cfg)):
+    for x, y in zip(prk.state_of(eng, cfg), prk.state_of(twin, cfg)):
         assert np.array_equal(x, y)
     assert w.value == 77
     assert L.cdpr_env_evaluate_device(eng._h, C.byref(good), None, *outs) == 0 and eng.device_download(d["counts"].value, dr.COUNTS, np.uint32)[0] == B  # (the same buffers, accepted)
