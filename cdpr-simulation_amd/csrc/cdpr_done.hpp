@@ -139,7 +139,7 @@ static __global__ __launch_bounds__(256) void cdpr_done_f64_kernel(const DoneF64
   // (the residual has no double getter: it is taken as cdpr_get_fk_state hands it out, rounded to float, so that the verdict stays
   // a function of the getters' outputs)
   s.fk_residual = (double)(float)O[(size_t)kF64ObsResidual * st];
-  s.flags = (uint32_t)(int32_t)O[(size_t)kF64ObsFlags * st];  // (as fetch_int_row64 reads the row)
+  s.flags = (uint32_t)(int32_t)O[(size_t)kF64ObsFlags * st];  // (as the flags getters read the row)
   s.age = a.step - a.episode_start[c];
   done_store(a.out, a.rule.enable, r, live, done_reason(a.rule, s));
 }

@@ -344,67 +344,6 @@ GenCtl general_ctl(const cdpr_engine* h) {
   return g;
 }
 
-int fetch_slots(cdpr_engine* h, const float4* dsrc, int nslots, std::vector<float4>& host) {
-  host.resize((size_t)nslots * h->stride);
-  HIP_TRY(h, hipMemcpyAsync(host.data(), dsrc, host.size() * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, wait_stream(h));
-  return CDPR_OK;
-}
-
-// One field group of every robot out of a slot-row buffer into a caller's robot-major host array: a device-side gather
-// into the read-out scratch, then one contiguous copy.  fields = (slot, component) per output column.
-int fetch_fields(cdpr_engine* h, const float4* rows, const std::vector<std::pair<int, int>>& fields, void* host_out, uint32_t as_int = 0) {
-  if (!host_out) return CDPR_OK;
-  if (fields.size() > kUnpackMaxWidth) {  // (the kernel argument holds kUnpackMaxWidth (slot, component) pairs)
-    h->err = "fetch_fields: more columns than the gather's field table holds";
-    return CDPR_ERR_INVALID;
-  }
-  const size_t count = (size_t)h->batch * fields.size();
-  HIP_TRY(h, h->d_unpack.ensure(h, count * sizeof(float)));
-  UnpackArgs u{};
-  u.rows = rows;
-  u.out = h->d_unpack;
-  u.stride = h->stride;
-  u.batch = h->batch;
-  u.width = (uint32_t)fields.size();
-  u.as_int = as_int;
-  for (size_t j = 0; j < fields.size(); ++j) {
-    u.slot[j] = (uint8_t)fields[j].first;
-    u.comp[j] = (uint8_t)fields[j].second;
-  }
-  hipLaunchKernelGGL(cdpr_unpack_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, h->stream, u);
-  HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipMemcpyAsync(host_out, h->d_unpack, count * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, wait_stream(h));  // the scratch is reused by the next call
-  return CDPR_OK;
-}
-
-// pose7 = slot 0 xyzw, slot 1 xyz; twist6 = slot 1 w, slot 2 xyzw, slot 3 x
-const std::vector<std::pair<int, int>> kPoseFields = {{0, 0}, {0, 1}, {0, 2}, {0, 3}, {1, 0}, {1, 1}, {1, 2}};
-const std::vector<std::pair<int, int>> kTwistFields = {{1, 3}, {2, 0}, {2, 1}, {2, 2}, {2, 3}, {3, 0}};
-
-// (slot, component) per column of the robot-major arrays a getter hands out: joint fields [f0, f1) (0 position, 1 velocity, 2 effort)
-// of every cable, then - `platform` - pose7 and twist6
-static std::vector<std::pair<int, int>> obs_columns(uint32_t n, int f0, int f1, bool platform) {
-  std::vector<std::pair<int, int>> cols;
-  cols.reserve((size_t)(f1 - f0) * n + 13u);
-  for (int f = f0; f < f1; ++f)
-    for (uint32_t i = 0; i < n; ++i) cols.push_back(obs_joint_field((int)n, f, i));
-  if (platform) {
-    cols.insert(cols.end(), kPoseFields.begin(), kPoseFields.end());
-    cols.insert(cols.end(), kTwistFields.begin(), kTwistFields.end());
-  }
-  return cols;
-}
-
-int fetch_platform(cdpr_engine* h, const float4* rows, float* pose7, float* twist6) {
-  int rc = fetch_fields(h, rows, kPoseFields, pose7);
-  if (rc != CDPR_OK) return rc;
-  return fetch_fields(h, rows, kTwistFields, twist6);
-}
-
-inline float comp(const float4& v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : (k == 2 ? v.z : v.w)); }
-
 // Wait for the handle's stream with the host in the loop in mind (update -> synchronize -> read observables, every
 // step): poll hipStreamQuery for the first kSpinUs microseconds (the blocking wait's wake-up costs 15-25 us, which is two
 // step kernels; measured by scripts/short_run_probe.py), then hand over to the blocking hipStreamSynchronize so that long
@@ -604,39 +543,6 @@ int cdpr_reset(cdpr_handle_t h) {
   return upload_home(h);
 }
 
-int cdpr_set_platform_state(cdpr_handle_t h, const float* pose7, const float* twist6) {
-  if (!h) return CDPR_ERR_INVALID;
-  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  if (h->plan.fp64) {
-    std::vector<double> p, t;
-    if (pose7) p.assign(pose7, pose7 + (size_t)h->batch * 7);
-    if (twist6) t.assign(twist6, twist6 + (size_t)h->batch * 6);
-    return set_platform_state64(h, pose7 ? p.data() : nullptr, twist6 ? t.data() : nullptr);
-  }
-  const int P = plat_slots(h->plan.fk);
-  std::vector<float4> s;
-  int rc = fetch_slots(h, h->d_state, P, s);
-  if (rc != CDPR_OK) return rc;
-  const size_t st = h->stride;
-  for (uint32_t r = 0; r < h->batch; ++r) {
-    float4 &a = s[0 * st + r], &b = s[1 * st + r], &c = s[2 * st + r], &d = s[3 * st + r];
-    if (pose7) {
-      const float* p = pose7 + (size_t)r * 7;
-      a = make_float4(p[0], p[1], p[2], p[3]);
-      b.x = p[4]; b.y = p[5]; b.z = p[6];
-      d.y = p[0]; d.z = p[1]; d.w = p[2];  // the FK seed follows the spawn pose
-      if (h->plan.fk) s[4 * st + r] = make_float4(p[3], p[4], p[5], p[6]);
-    }
-    if (twist6) {
-      const float* t = twist6 + (size_t)r * 6;
-      b.w = t[0]; c.x = t[1]; c.y = t[2]; c.z = t[3]; c.w = t[4]; d.x = t[5];
-    }
-  }
-  HIP_TRY(h, hipMemcpyAsync(h->d_state, s.data(), s.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, wait_stream(h));
-  return CDPR_OK;
-}
-
 // A pending command replaces the one before it (PLG.cpp:69,78: the callback overwrites the stored message); on a
 // per-robot handle an UNMASKED command after a masked one would have to merge with it, which the callbacks of
 // independent plugins never need: the later call wins for the robots it addresses, the earlier one keeps the rest.
@@ -772,43 +678,11 @@ int cdpr_update_scheduled_kind(cdpr_handle_t h, uint32_t kind, int nsteps, int r
   return scheduled_update(h, kind, nsteps, refresh_steps, d_commands, d_ready, d_robot_masks, d_record, record_bytes);
 }
 
-int cdpr_decode_observables(cdpr_handle_t h, const void* image, float* position, float* velocity, float* effort,
-                            float* pose7, float* twist6) {
-  if (!h || !image) return CDPR_ERR_INVALID;
-  if (h->plan.fp64) {  // (the float getters of a precision = 64 handle round)
-    decode_image64_to_float(h, static_cast<const double*>(image), position, velocity, effort, pose7, twist6);
-    return CDPR_OK;
-  }
-  const float4* o = static_cast<const float4*>(image);
-  const size_t st = h->stride;
-  float* dst[3] = {position, velocity, effort};
-  for (int f = 0; f < 3; ++f) {
-    if (!dst[f]) continue;
-    for (uint32_t r = 0; r < h->batch; ++r)
-      for (uint32_t i = 0; i < h->n; ++i) {
-        const std::pair<int, int> sc = obs_joint_field((int)h->n, f, i);
-        dst[f][(size_t)r * h->n + i] = comp(o[(size_t)sc.first * st + r], sc.second);
-      }
-  }
-  for (uint32_t r = 0; r < h->batch; ++r) {
-    const float4 a = o[0 * st + r], b = o[1 * st + r], c = o[2 * st + r], d = o[3 * st + r];
-    if (pose7) {
-      float* p = pose7 + (size_t)r * 7;
-      p[0] = a.x; p[1] = a.y; p[2] = a.z; p[3] = a.w; p[4] = b.x; p[5] = b.y; p[6] = b.z;
-    }
-    if (twist6) {
-      float* t = twist6 + (size_t)r * 6;
-      t[0] = b.w; t[1] = c.x; t[2] = c.y; t[3] = c.z; t[4] = c.w; t[5] = d.x;
-    }
-  }
-  return CDPR_OK;
-}
-
 int cdpr_synchronize(cdpr_handle_t h) {
   if (!h) return CDPR_ERR_INVALID;
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
   HIP_TRY(h, wait_stream(h));
-  return check_fault(h);
+  return checked(h, CDPR_OK);
 }
 
 static int copy_name(const std::string& text, char* name, size_t len) {
@@ -845,195 +719,6 @@ uint32_t cdpr_mapping(cdpr_handle_t h) {
 }
 
 uint64_t cdpr_step_count(cdpr_handle_t h) { return h ? h->step : 0; }
-
-static int fetch_joint_states(cdpr_engine* h, float* position, float* velocity, float* effort) {
-  if (h->plan.fp64) return fetch_observables64(h, position, velocity, effort, nullptr, nullptr, true);
-  float* dst[3] = {position, velocity, effort};
-  for (int f = 0; f < 3; ++f)
-    if (int rc = fetch_fields(h, h->d_obs, obs_columns(h->n, f, f + 1, false), dst[f])) return rc;
-  return CDPR_OK;
-}
-
-int cdpr_get_joint_states(cdpr_handle_t h, float* position, float* velocity, float* effort) {
-  if (!h) return CDPR_ERR_INVALID;
-  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  return checked(h, fetch_joint_states(h, position, velocity, effort));
-}
-
-// JointState + PlatformState of the last published step in ONE device round trip (PLG.cpp:248-280 publishes both every
-// step): the gather kernel writes the five arrays into a pinned host image and then a completion word the host spins
-// on.  (cdpr_get_joint_states + cdpr_get_platform_state are five gathers, five copies and five waits.)
-static int fetch_observables(cdpr_engine* h, float* position, float* velocity, float* effort, float* pose7, float* twist6) {
-  if (h->plan.fp64) return fetch_observables64(h, position, velocity, effort, pose7, twist6, true);
-  const uint32_t n = h->n, width = 3u * n + 13u;
-  if (width > kPublishMaxWidth) {  // (the kernel argument holds kPublishMaxWidth (slot, component) pairs)
-    h->err = "cdpr_get_observables: more columns than the publish kernel's field table holds";
-    return CDPR_ERR_INVALID;
-  }
-  const size_t count = (size_t)h->batch * width;
-  // lazy set-up, every allocation guarded on its own pointer (a failure half way leaves nothing to leak or to skip next
-  // time).  Coherent host memory: the host spins on the completion word while the kernel is still running.
-  if (!h->h_pub && count * sizeof(float) <= (2u << 20))  // the pinned image serves the two small tiers only
-    HIP_TRY(h, h->h_pub.alloc(count * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
-  if (!h->h_pub_done) {
-    HIP_TRY(h, h->h_pub_done.alloc(sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent));
-    *h->h_pub_done = 0;
-  }
-  if (!h->d_pub_arrivals) {
-    HIP_TRY(h, h->d_pub_arrivals.alloc(sizeof(uint32_t)));
-    hipError_t me = hipMemsetAsync(h->d_pub_arrivals, 0, sizeof(uint32_t), h->stream);
-    if (me != hipSuccess) {  // never launch the publish kernel on an uninitialised arrival counter
-      h->d_pub_arrivals.release();
-      HIP_TRY(h, me);
-    }
-  }
-  // small images go straight to host memory from the gather kernel (a per-step caller of a few robots: ~5 us); large
-  // ones through device scratch and the copy engine (kernel stores over PCIe reach ~7 GB/s, the copy engine ~30)
-  const bool direct = count * sizeof(float) <= (256u << 10);
-  if (!direct) HIP_TRY(h, h->d_unpack.ensure(h, count * sizeof(float)));
-  PublishArgs u{};
-  u.rows = h->d_obs;
-  if (direct) {
-    HIP_TRY(h, hipHostGetDevicePointer((void**)&u.out, h->h_pub, 0));
-    HIP_TRY(h, hipHostGetDevicePointer((void**)&u.done, h->h_pub_done, 0));
-  } else {
-    u.out = h->d_unpack;
-    u.done = nullptr;
-  }
-  u.arrivals = h->d_pub_arrivals;
-  u.epoch = ++h->pub_epoch;
-  u.stride = h->stride;
-  u.batch = h->batch;
-  u.n = n;
-  u.width = width;
-  const std::vector<std::pair<int, int>> cols = obs_columns(n, 0, 3, true);
-  for (uint32_t j = 0; j < width; ++j) u.slot[j] = (uint8_t)cols[j].first, u.comp[j] = (uint8_t)cols[j].second;
-  hipLaunchKernelGGL(cdpr_publish_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, h->stream, u);
-  HIP_TRY(h, hipGetLastError());
-  if (direct) {
-    // wait on the completion word: plain host memory, no runtime call; past the spin budget fall back to the stream wait
-    // (which also surfaces a device fault instead of spinning on a word that will never come)
-    volatile uint64_t* done = h->h_pub_done;
-    const auto t0 = std::chrono::steady_clock::now();
-    uint32_t spins = 0;
-    while (*done != u.epoch) {
-      if ((++spins & 0x3FFu) == 0 && std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count() >= 20) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (*done != u.epoch) {
-          h->err = "cdpr_get_observables: the publish kernel finished without its completion word";
-          return CDPR_ERR_DEVICE;
-        }
-        break;
-      }
-    }
-  } else if (count * sizeof(float) <= (2u << 20)) {  // one copy into the pinned image, split up on the host below
-    HIP_TRY(h, hipMemcpyAsync(h->h_pub, h->d_unpack, count * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, wait_stream(h));
-  } else {  // straight into the caller's arrays (reading a large pinned image back on the host costs more than the DMA)
-    const size_t bnl = (size_t)h->batch * n;
-    float* dst[5] = {position, velocity, effort, pose7, twist6};
-    const size_t off[5] = {0, bnl, 2 * bnl, 3 * bnl, 3 * bnl + (size_t)h->batch * 7};
-    const size_t len[5] = {bnl, bnl, bnl, (size_t)h->batch * 7, (size_t)h->batch * 6};
-    for (int k = 0; k < 5; ++k)
-      if (dst[k]) HIP_TRY(h, hipMemcpyAsync(dst[k], h->d_unpack + off[k], len[k] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, wait_stream(h));
-    return CDPR_OK;
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  const size_t bn = (size_t)h->batch * n;
-  const float* src = h->h_pub;
-  if (position) std::memcpy(position, src, bn * sizeof(float));
-  if (velocity) std::memcpy(velocity, src + bn, bn * sizeof(float));
-  if (effort) std::memcpy(effort, src + 2 * bn, bn * sizeof(float));
-  if (pose7) std::memcpy(pose7, src + 3 * bn, (size_t)h->batch * 7 * sizeof(float));
-  if (twist6) std::memcpy(twist6, src + 3 * bn + (size_t)h->batch * 7, (size_t)h->batch * 6 * sizeof(float));
-  return CDPR_OK;
-}
-
-int cdpr_get_observables(cdpr_handle_t h, float* position, float* velocity, float* effort, float* pose7, float* twist6) {
-  if (!h) return CDPR_ERR_INVALID;
-  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  return checked(h, fetch_observables(h, position, velocity, effort, pose7, twist6));
-}
-
-int cdpr_get_platform_state(cdpr_handle_t h, float* pose7, float* twist6) {
-  if (!h) return CDPR_ERR_INVALID;
-  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  return checked(h, h->plan.fp64 ? fetch_observables64(h, nullptr, nullptr, nullptr, pose7, twist6, true) : fetch_platform(h, h->d_obs, pose7, twist6));
-}
-
-int cdpr_get_raw_state(cdpr_handle_t h, float* pose7, float* twist6) {
-  if (!h) return CDPR_ERR_INVALID;
-  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  if (h->plan.fp64) {
-    int rc = fetch_rows64(h, h->d_state64, kF64Pose, 7, pose7, true);
-    return rc != CDPR_OK ? rc : checked(h, fetch_rows64(h, h->d_state64, kF64Twist, 6, twist6, true));
-  }
-  return checked(h, fetch_platform(h, h->d_state, pose7, twist6));
-}
-
-int cdpr_get_pid_debug(cdpr_handle_t h, float* axes9) {
-  if (!h || !axes9) return CDPR_ERR_INVALID;
-  if (!h->dbg) {
-    h->err = "CDPR_STAGE_PID_DEBUG not enabled";
-    return CDPR_ERR_UNSUPPORTED;
-  }
-  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  if (h->plan.fp64) {
-    std::vector<double> d((size_t)h->batch * CDPR_PID_DEBUG_AXES);
-    HIP_TRY(h, hipMemcpyAsync(d.data(), h->d_dbg64, d.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, wait_stream(h));
-    for (size_t i = 0; i < d.size(); ++i) axes9[i] = (float)d[i];
-  } else {
-    HIP_TRY(h, hipMemcpyAsync(axes9, h->d_dbg, (size_t)h->batch * CDPR_PID_DEBUG_AXES * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, wait_stream(h));
-  }
-  return checked(h, CDPR_OK);
-}
-
-int cdpr_get_fk_state(cdpr_handle_t h, float* pose7, float* residual, int32_t* iterations) {
-  if (!h) return CDPR_ERR_INVALID;
-  if (!h->plan.fk) {
-    h->err = "CDPR_STAGE_FK not enabled";
-    return CDPR_ERR_UNSUPPORTED;
-  }
-  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  if (h->plan.fp64) {
-    int rc = fetch_rows64(h, h->d_state64, kF64StateFk, 7, pose7, true);
-    if (rc == CDPR_OK) rc = fetch_rows64(h, h->d_obs64, kF64ObsResidual, 1, residual, true);
-    return rc != CDPR_OK ? rc : checked(h, fetch_int_row64(h, kF64ObsIterations, iterations));
-  }
-  // estimate: state slot 3 yzw + slot 4 xyzw; residual / iteration count: observable slot 3 y, z
-  int rc = fetch_fields(h, h->d_state, {{3, 1}, {3, 2}, {3, 3}, {4, 0}, {4, 1}, {4, 2}, {4, 3}}, pose7);
-  if (rc != CDPR_OK) return rc;
-  rc = fetch_fields(h, h->d_obs, {{3, 1}}, residual);
-  if (rc != CDPR_OK) return rc;
-  return checked(h, fetch_fields(h, h->d_obs, {{3, 2}}, iterations, 1u));
-}
-
-int cdpr_get_td_state(cdpr_handle_t h, float* tension, int32_t* infeasible) {
-  if (!h) return CDPR_ERR_INVALID;
-  if (!h->plan.td) {
-    h->err = "CDPR_STAGE_TD not enabled";
-    return CDPR_ERR_UNSUPPORTED;
-  }
-  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  int rc = fetch_joint_states(h, nullptr, nullptr, tension);  // applied force == distributed tension
-  if (rc != CDPR_OK) return rc;
-  rc = h->plan.fp64 ? fetch_int_row64(h, kF64ObsFlags, infeasible) : fetch_fields(h, h->d_obs, {{3, 3}}, infeasible, 1u);
-  if (rc == CDPR_OK && infeasible)
-    for (uint32_t b = 0; b < h->batch; ++b) infeasible[b] &= 1;  // the travel-limit mask shares the component (pack_flags)
-  return checked(h, rc);
-}
-
-int cdpr_get_limit_state(cdpr_handle_t h, uint32_t* cable_mask) {
-  if (!h || !cable_mask) return CDPR_ERR_INVALID;
-  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  int rc = h->plan.fp64 ? fetch_int_row64(h, kF64ObsFlags, reinterpret_cast<int32_t*>(cable_mask)) : fetch_fields(h, h->d_obs, {{3, 3}}, cable_mask, 1u);
-  if (rc == CDPR_OK)
-    for (uint32_t b = 0; b < h->batch; ++b) cable_mask[b] >>= 1;  // bit 0 is the tension-distribution flag
-  return checked(h, rc);
-}
 
 // Which instantiation the last step launch of run_steps took: 0 = the planned kernel as cdpr_kernel_name gives it, 1 = the role-split
 // kernel's steady-state controller wave (split_steady_launch).  Host-side state; for tests and A/B scripts, not part of the C-ABI header.
@@ -1075,7 +760,7 @@ int cdpr_device_download(cdpr_handle_t h, void* dst, const void* src, size_t byt
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
   HIP_TRY(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, wait_stream(h));
-  return check_fault(h);  // (a trajectory record of a schedule whose mailbox timed out is not the scheduled one)
+  return checked(h, CDPR_OK);  // (a trajectory record of a schedule whose mailbox timed out is not the scheduled one)
 }
 
 int cdpr_profile_begin(cdpr_handle_t h) {

@@ -1,5 +1,5 @@
 // cdpr_engine_f64.hip - host side of cdpr_config_t.precision = 64: the handle's set-up (build_f64), the fp64 step kernels' path of the
-// launch chain (cdpr_step_kernel_f64.hpp), their read-out and the rollout by composition.  Reference paths as in cdpr_engine.hip.
+// launch chain (cdpr_step_kernel_f64.hpp), and the rollout by composition.  Reference paths as in cdpr_engine.hip.
 #include "cdpr_engine_internal.hpp"
 
 namespace cdpr_host {
@@ -184,168 +184,6 @@ int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, vo
     HIP_TRY(h, hipGetLastError());
     return (int)CDPR_OK;
   });
-}
-
-// rows [first_row, first_row + width) of a double row buffer -> robot-major host array (double, or float when as_float)
-int fetch_rows64(cdpr_engine* h, const double* rows, uint32_t first_row, uint32_t width, void* host_out, bool as_float) {
-  if (!host_out) return CDPR_OK;
-  const size_t count = (size_t)h->batch * width, bytes = count * (as_float ? sizeof(float) : sizeof(double));
-  HIP_TRY(h, h->d_unpack64.ensure(h, bytes));
-  Unpack64Args u{};
-  u.rows = rows;
-  u.out = h->d_unpack64;
-  u.stride = h->stride;
-  u.batch = h->batch;
-  u.width = width;
-  u.first_row = first_row;
-  u.as_float = as_float ? 1 : 0;
-  hipLaunchKernelGGL(cdpr_unpack64_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, h->stream, u);
-  HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipMemcpyAsync(host_out, h->d_unpack64, bytes, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, wait_stream(h));
-  return CDPR_OK;
-}
-
-// the five observable arrays of an fp64 handle (any may be null), double or rounded to float
-// The five observable arrays of a precision = 64 handle in ONE device round trip (round 6; five unpack launches, five copies and
-// five waits before: 88 us per world step for one robot with the host in the loop): one gather launch writes them - small
-// batches straight into a mapped pinned host image, larger ones into device scratch followed by one copy each - one wait.
-int fetch_observables64(cdpr_engine* h, void* position, void* velocity, void* effort, void* pose7, void* twist6, bool as_float) {
-  const uint32_t n = h->n;
-  void* dst[5] = {position, velocity, effort, pose7, twist6};
-  const uint32_t first[5] = {kF64ObsJoint, kF64ObsJoint + n, kF64ObsJoint + 2u * n, kF64Pose, kF64Twist}, width[5] = {n, n, n, 7u, 6u};
-  Unpack64MultiArgs u{};
-  u.rows = h->d_obs64;
-  u.stride = h->stride;
-  u.batch = h->batch;
-  u.as_float = as_float ? 1 : 0;
-  void* want[5];
-  uint32_t cum = 0;
-  size_t off = 0;
-  for (int i = 0; i < 5; ++i) {
-    if (!dst[i]) continue;
-    const uint32_t k = u.nseg++;
-    u.first_row[k] = first[i], u.width[k] = width[i], u.cum[k] = cum, u.off[k] = (uint32_t)off;
-    want[k] = dst[i];
-    cum += width[i];
-    off += (size_t)h->batch * width[i];
-  }
-  if (u.nseg == 0) return CDPR_OK;
-  u.total_width = cum;
-  const size_t esz = as_float ? sizeof(float) : sizeof(double), bytes = off * esz;
-  if (off >= (1ull << 32)) {  // element offsets are 32-bit
-    int rc = CDPR_OK;
-    for (int i = 0; i < 5 && rc == CDPR_OK; ++i) rc = fetch_rows64(h, h->d_obs64, first[i], width[i], dst[i], as_float);
-    return rc;
-  }
-  const bool pinned = bytes <= (2u << 20);
-  if (pinned) {
-    if (!h->h_pub64) HIP_TRY(h, h->h_pub64.alloc(2u << 20, hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(h, hipHostGetDevicePointer(&u.out, h->h_pub64, 0));
-  } else {
-    HIP_TRY(h, h->d_unpack64.ensure(h, bytes));
-    u.out = h->d_unpack64;
-  }
-  hipLaunchKernelGGL(cdpr_unpack64_multi_kernel, dim3((uint32_t)(((size_t)h->batch * cum + 255) / 256)), dim3(256), 0, h->stream, u);
-  HIP_TRY(h, hipGetLastError());
-  if (!pinned)
-    for (uint32_t k = 0; k < u.nseg; ++k)
-      HIP_TRY(h, hipMemcpyAsync(want[k], h->d_unpack64 + (size_t)u.off[k] * esz, (size_t)h->batch * u.width[k] * esz, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, wait_stream(h));
-  if (pinned)
-    for (uint32_t k = 0; k < u.nseg; ++k) memcpy(want[k], h->h_pub64 + (size_t)u.off[k] * esz, (size_t)h->batch * u.width[k] * esz);
-  return CDPR_OK;
-}
-
-int set_platform_state64(cdpr_engine* h, const double* pose7, const double* twist6) {
-  const size_t st = h->stride;
-  std::vector<double> s((size_t)kF64StateCtrl * st);
-  HIP_TRY(h, hipMemcpyAsync(s.data(), h->d_state64, s.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, wait_stream(h));
-  for (uint32_t r = 0; r < h->batch; ++r) {
-    if (pose7)
-      for (int c = 0; c < 7; ++c) s[(size_t)(kF64Pose + c) * st + r] = s[(size_t)(kF64StateFk + c) * st + r] = pose7[(size_t)r * 7 + c];  // the FK seed follows the spawn pose
-    if (twist6)
-      for (int c = 0; c < 6; ++c) s[(size_t)(kF64Twist + c) * st + r] = twist6[(size_t)r * 6 + c];
-  }
-  HIP_TRY(h, hipMemcpyAsync(h->d_state64, s.data(), s.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, wait_stream(h));
-  return CDPR_OK;
-}
-
-// image of a precision = 64 handle -> robot-major arrays, as double or rounded to float
-template <typename T>
-void decode_image64(const cdpr_engine* h, const double* o, T* position, T* velocity, T* effort, T* pose7, T* twist6) {
-  const size_t st = h->stride;
-  const uint32_t n = h->n;
-  T* dst[3] = {position, velocity, effort};
-  for (int f = 0; f < 3; ++f) {
-    if (!dst[f]) continue;
-    for (uint32_t r = 0; r < h->batch; ++r)
-      for (uint32_t i = 0; i < n; ++i) dst[f][(size_t)r * n + i] = (T)o[(size_t)(kF64ObsJoint + f * n + i) * st + r];
-  }
-  for (uint32_t r = 0; r < h->batch; ++r) {
-    if (pose7)
-      for (int c = 0; c < 7; ++c) pose7[(size_t)r * 7 + c] = (T)o[(size_t)(kF64Pose + c) * st + r];
-    if (twist6)
-      for (int c = 0; c < 6; ++c) twist6[(size_t)r * 6 + c] = (T)o[(size_t)(kF64Twist + c) * st + r];
-  }
-}
-void decode_image64_to_float(const cdpr_engine* h, const double* image, float* position, float* velocity, float* effort, float* pose7, float* twist6) {
-  decode_image64(h, image, position, velocity, effort, pose7, twist6);
-}
-
-}  // namespace cdpr_host
-
-int cdpr_decode_observables_f64(cdpr_handle_t h, const void* image, double* position, double* velocity, double* effort, double* pose7, double* twist6) {
-  if (!h || !image) return CDPR_ERR_INVALID;
-  if (!h->plan.fp64) {
-    h->err = "cdpr_decode_observables_f64: the handle was not created with precision = 64";
-    return CDPR_ERR_UNSUPPORTED;
-  }
-  decode_image64(h, static_cast<const double*>(image), position, velocity, effort, pose7, twist6);
-  return CDPR_OK;
-}
-namespace cdpr_host {
-
-static int need_fp64(cdpr_engine* h, const char* what) {
-  if (h->plan.fp64) return CDPR_OK;
-  h->err = std::string(what) + ": the handle was not created with precision = 64";
-  return CDPR_ERR_UNSUPPORTED;
-}
-}  // namespace cdpr_host
-
-int cdpr_get_observables_f64(cdpr_handle_t h, double* position, double* velocity, double* effort, double* pose7, double* twist6) {
-  if (!h) return CDPR_ERR_INVALID;
-  if (int rc = need_fp64(h, "cdpr_get_observables_f64")) return rc;
-  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  return checked(h, fetch_observables64(h, position, velocity, effort, pose7, twist6, false));
-}
-
-int cdpr_get_raw_state_f64(cdpr_handle_t h, double* pose7, double* twist6) {
-  if (!h) return CDPR_ERR_INVALID;
-  if (int rc = need_fp64(h, "cdpr_get_raw_state_f64")) return rc;
-  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  int rc = fetch_rows64(h, h->d_state64, kF64Pose, 7, pose7, false);
-  return rc != CDPR_OK ? rc : checked(h, fetch_rows64(h, h->d_state64, kF64Twist, 6, twist6, false));
-}
-
-int cdpr_set_platform_state_f64(cdpr_handle_t h, const double* pose7, const double* twist6) {
-  if (!h) return CDPR_ERR_INVALID;
-  if (int rc = need_fp64(h, "cdpr_set_platform_state_f64")) return rc;
-  if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
-  return set_platform_state64(h, pose7, twist6);
-}
-namespace cdpr_host {
-
-// fp64 handles: one observable row of doubles as int32 per robot (iteration count, flags)
-int fetch_int_row64(cdpr_engine* h, uint32_t row, int32_t* out) {
-  if (!out) return CDPR_OK;
-  std::vector<double> d(h->batch);
-  int rc = fetch_rows64(h, h->d_obs64, row, 1, d.data(), false);
-  if (rc == CDPR_OK)
-    for (uint32_t b = 0; b < h->batch; ++b) out[b] = (int32_t)d[b];
-  return rc;
 }
 
 // Queue one rollout on the handle's stream: trajectories = batch * samples, reference positions and costs in

@@ -2,9 +2,10 @@
 // captured graphs (DevBuf, PinnedBuf, StagePair, GraphCache), the views of a per-robot handle's records with the one launch helper
 // of the kernels over chosen robots (fast_records / gen_records / f64_records, launch_per_robot), the handle (struct cdpr_engine: its routing is h->plan and nothing else, its
 // buffers are owner members that go with it), the error macros and the helpers one unit defines and another calls.  Units:
-// cdpr_engine.hip (create / destroy, the general path's set-up, the command setters, read-out, the extern "C" wrappers),
+// cdpr_engine.hip (create / destroy, the general path's set-up, the command setters, the extern "C" wrappers), cdpr_engine_readout.hip (the getters,
+// the image decoders and cdpr_set_platform_state* on the column table of cdpr_readout.hpp: one gather kernel, read_blocks),
 // cdpr_engine_launch.hip (what turns "advance n world steps" into launches: the latch, the chain and its clock, the fp32 and
-// general paths, schedules), cdpr_engine_f64.hip (precision = 64: set-up, its path of the chain, read-out), cdpr_engine_rollout.hip (cdpr_rollout_velocity*), cdpr_engine_solvers.hip (cdpr_solve_ik / fk / td), cdpr_engine_reset.hip
+// general paths, schedules), cdpr_engine_f64.hip (precision = 64: set-up, its path of the chain), cdpr_engine_rollout.hip (cdpr_rollout_velocity*), cdpr_engine_solvers.hip (cdpr_solve_ik / fk / td), cdpr_engine_reset.hip
 // (cdpr_reset_robots*), cdpr_engine_copy.hip (cdpr_copy_robots*), cdpr_engine_done.hip (cdpr_evaluate_done*, cdpr_reset_done_device, cdpr_get_episode_start), cdpr_engine_env.hip (cdpr_observe_device,
 // cdpr_env_evaluate_device, cdpr_observation_width).  Not installed, not part of the C-ABI (include/cdpr.h is).
 #pragma once
@@ -26,6 +27,7 @@
 #include "cdpr_select.hpp"
 #include "cdpr_robot_records.hpp"
 #include "cdpr_solvers.hpp"
+#include "cdpr_readout.hpp"
 
 using namespace cdpr;
 
@@ -277,8 +279,10 @@ struct cdpr_engine {
   float wtab_host[2][kWin * (kWin + 2)]{};  // the same tables on the host: one-step launches take their row by value
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   uint64_t launches = 0, launches_mark = 0;
-  // cdpr_get_observables: pinned, device-mapped host image of one published step + completion word
-  PinnedBuf<float> h_pub;
+  // read-out (read_blocks, cdpr_engine_readout.hip): device scratch the gather writes where it does not store to the host itself
+  // (grow-only), the pinned, device-mapped host image of the small tiers, the completion word with its arrival counter and epoch
+  DevBuf<char> d_unpack;
+  PinnedBuf<char> h_pub;
   PinnedBuf<uint64_t> h_pub_done;
   DevBuf<uint32_t> d_pub_arrivals;
   uint64_t pub_epoch = 0;
@@ -303,10 +307,7 @@ struct cdpr_engine {
   DevBuf<double> d_geom64;       // [n][7]
   DevBuf<double> d_wtab64;       // [velocity | position] x [10][12]
   DevBuf<double> d_dbg64;
-  DevBuf<char> d_unpack64;       // read-out scratch of the fp64 getters, grow-only
-  PinnedBuf<char> h_pub64;       // mapped pinned image the fp64 getters of small batches are gathered into (2 MiB)
   F64Args base64{};
-  DevBuf<float> d_unpack;        // read-out scratch (cdpr_get_*): robot-major copy of the requested fields, grow-only
   std::string err;
 };
 
@@ -315,9 +316,6 @@ namespace cdpr_host {
 // precision = 64: prior errors kept per cable (the ring of the handle's kernels), and the samples a HOLD record's window holds
 inline int win64(const cdpr_engine* h) { return h->plan.long64 ? kWinLong : kWin; }
 inline int hold_win(const cdpr_engine* h) { return h->plan.hold_long ? kHoldWinLong : kHoldWin; }
-
-// fp32 observable image: (slot, component) of joint field f (0 position, 1 velocity, 2 effort) of cable i
-inline std::pair<int, int> obs_joint_field(int n, int f, uint32_t i) { return {4 + f * joint_groups(n) + (int)(i / 4), (int)(i % 4)}; }
 
 int derivative_weights(uint32_t n, uint32_t degree, double* w);  // cdpr_engine.hip
 
@@ -429,7 +427,6 @@ std::vector<float4> home_state(const cdpr_engine* h, uint32_t rows);
 void copy_pid(const StepArgs& src, StepArgs& dst);
 void copy_pid_alt(const StepArgs& src, PidSet& dst);
 GenCtl general_ctl(const cdpr_engine* h);
-int fetch_slots(cdpr_engine* h, const float4* dsrc, int nslots, std::vector<float4>& host);
 // cdpr_engine_launch.hip
 double sim_time(uint64_t step, double dt);
 LaunchShape launch_shape(const cdpr_engine* h, int k, bool steady = false, const Schedule* sched = nullptr);
@@ -452,11 +449,6 @@ int build_f64(cdpr_engine* h);  // cdpr_create's part of a precision = 64 handle
 size_t state64_rows(const cdpr_engine* h);
 int upload_home64(cdpr_engine* h);
 int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, void* record);  // (its path of the chain; run_steps has latched the commands)
-int fetch_rows64(cdpr_engine* h, const double* rows, uint32_t first_row, uint32_t width, void* host_out, bool as_float);
-int fetch_observables64(cdpr_engine* h, void* position, void* velocity, void* effort, void* pose7, void* twist6, bool as_float);
-int set_platform_state64(cdpr_engine* h, const double* pose7, const double* twist6);
-int fetch_int_row64(cdpr_engine* h, uint32_t row, int32_t* out);
-void decode_image64_to_float(const cdpr_engine* h, const double* image, float* position, float* velocity, float* effort, float* pose7, float* twist6);
 int rollout_enqueue_f64(cdpr_engine* h, int samples, int horizon, const float* d_commands, const float* d_ref, float* d_cost);
 
 // The handle as the kernels that act on chosen robots see it (cdpr_robot_records.hpp), one builder per record layout: the only

@@ -117,78 +117,4 @@ __global__ __launch_bounds__(64) void cdpr_solver_kernel(const SolveArgs a) {
   }
 }
 
-// Observable read-out: slot rows (float4 per robot per slot) -> robot-major float arrays as the C-ABI hands them out
-// ([B][W]), on the device, so the host gets one contiguous copy instead of transposing B x W values in a scalar loop
-// (at 524 288 robots: 50 MB of joint states).  Thread (r, j) picks component comp[j] of slot slot[j] of robot r.
-constexpr uint32_t kUnpackMaxWidth = 24;  // the widest field list of one gather: a joint block (n columns), a pose, a twist
-struct UnpackArgs {
-  const float4* rows;
-  float* out;
-  uint32_t stride, batch, width;
-  uint8_t slot[kUnpackMaxWidth], comp[kUnpackMaxWidth];
-  uint32_t as_int;  // bit j set: the value is converted to int32 (iteration counts, flags) before it is stored
-};
-static_assert(kUnpackMaxWidth >= CDPR_MAX_CABLES, "UnpackArgs: a joint block of CDPR_MAX_CABLES columns must fit the field table");
-static_assert(kUnpackMaxWidth <= 32, "UnpackArgs: as_int has one bit per column");
-
-static __global__ __launch_bounds__(256) void cdpr_unpack_kernel(const UnpackArgs a) {
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-  if (t >= a.batch * a.width) return;
-  const uint32_t r = t / a.width, j = t - r * a.width;
-  const float v = comp4(a.rows[(size_t)a.slot[j] * a.stride + r], a.comp[j]);
-  a.out[t] = ((a.as_int >> j) & 1u) ? __int_as_float((int)v) : v;
-}
-
-// One published step of every robot straight into the caller-visible (pinned, device-mapped) host buffer: five
-// robot-major blocks [position | velocity | effort | pose7 | twist6] gathered from the observable rows by one launch,
-// then a completion word written by the last workgroup after a system-scope fence.  The host spins on that word: no
-// copy engine, no runtime call in the wait (cdpr_get_observables).
-constexpr uint32_t kPublishMaxWidth = 3u * CDPR_MAX_CABLES + 13u;  // three joint blocks of n columns, pose7, twist6
-struct PublishArgs {
-  const float4* rows;
-  float* out;               // host-mapped
-  uint64_t* done;           // host-mapped completion word
-  uint32_t* arrivals;       // device counter, zero between launches
-  uint64_t epoch;
-  uint32_t stride, batch, n, width;  // width = 3 n + 13
-  uint8_t slot[kPublishMaxWidth], comp[kPublishMaxWidth];
-};
-static_assert(sizeof(PublishArgs::slot) == 3u * CDPR_MAX_CABLES + 13u, "PublishArgs: one field per output column at CDPR_MAX_CABLES cables");
-static_assert(CDPR_MAX_CABLES + 1u <= 24u, "pack_flags: the TD flag and one travel-limit bit per cable must stay exact in a float");
-
-static __global__ __launch_bounds__(256) void cdpr_publish_kernel(const PublishArgs a) {
-  // one thread per OUTPUT element, so that a wave writes 256 contiguous bytes (the destination may be host memory behind
-  // PCIe); the output is five robot-major blocks: three joint blocks of n columns, then 7 pose and 6 twist columns
-  const uint32_t o = blockIdx.x * 256u + threadIdx.x;
-  const uint32_t bn = a.batch * a.n, n3 = 3u * a.n;
-  if (o < a.batch * a.width) {
-    uint32_t r, j;
-    if (o < 3u * bn) {
-      const uint32_t f = o / bn, rem = o - f * bn;
-      r = rem / a.n;
-      j = f * a.n + (rem - r * a.n);
-    } else if (o < 3u * bn + 7u * a.batch) {
-      const uint32_t rem = o - 3u * bn;
-      r = rem / 7u;
-      j = n3 + (rem - r * 7u);
-    } else {
-      const uint32_t rem = o - 3u * bn - 7u * a.batch;
-      r = rem / 6u;
-      j = n3 + 7u + (rem - r * 6u);
-    }
-    a.out[o] = comp4(a.rows[(size_t)a.slot[j] * a.stride + r], a.comp[j]);
-  }
-  if (!a.done) return;  // staged read-out: the copy engine and the stream wait finish the job
-  __threadfence_system();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t prev = atomicAdd(a.arrivals, 1u);
-    if (prev == gridDim.x - 1u) {
-      *a.arrivals = 0u;
-      __threadfence_system();
-      __hip_atomic_store(a.done, a.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
-}
-
 }  // namespace cdpr
