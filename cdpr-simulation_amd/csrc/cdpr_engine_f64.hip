@@ -2,6 +2,75 @@
 // launch chain (cdpr_step_kernel_f64.hpp), and the rollout by composition.  Reference paths as in cdpr_engine.hip.
 #include "cdpr_engine_internal.hpp"
 
+namespace cdpr {
+
+// ---- cdpr_rollout_velocity on a precision = 64 handle (round 6), by composition: every (robot, sampled sequence) becomes a column
+// of a scratch state (expand), every step of the horizon is ONE launch of the handle's own step kernel over those columns with the
+// step's commands gathered into a Joy batch (cmd), and a third kernel adds |p(t_k+1) - p_ref|^2 to the trajectory's cost (cost).
+// No rollout kernel of its own: the rollout in double is there for checking the fp32 one, not for throughput.
+struct Roll64Args {
+  const double* src;  // the handle's state rows
+  double* dst;        // the trajectories' state rows
+  uint32_t src_stride, dst_stride, rows, batch, samples;
+  uint32_t zero_from;  // rows >= this are cleared in the copies (a Joy on jointVelocities in Position mode resets the velocity Pid,
+                       // JFC.cpp:113-115); == rows: none
+  // HOLD handles: that Pid has a record of its own per cable (f64_hold_row) - hold_zero_pid = 1 + the Pid whose records are cleared, 0: none
+  uint32_t hold_base, hold_cable_rows, hold_pid_rows, hold_zero_pid;
+  // per-robot handles: the robot's mode / call-count byte decides (a robot that is not in Velocity mode enters it: its - velocity - Pid
+  // is reset, its count 0); every trajectory gets its own byte
+  const uint8_t* meta_src;
+  uint8_t* meta_dst;
+};
+static __global__ __launch_bounds__(256) void cdpr_roll64_expand_kernel(const Roll64Args a) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= a.batch * a.samples) return;
+  const uint32_t b = t / a.samples;
+  bool resets = true;  // (uniform handles: zero_from / hold_zero_pid already say whether the Joy resets the Pid)
+  if (a.meta_src) {
+    const uint32_t m = a.meta_src[b];
+    resets = (m & kMetaModeMask) != kMetaVelocity;
+    a.meta_dst[t] = (uint8_t)(resets ? kMetaVelocity : m);
+  }
+  for (uint32_t r = 0; r < a.rows; ++r) {
+    bool zero = resets && r >= a.zero_from;
+    if (resets && a.hold_zero_pid && r >= a.hold_base) {
+      const uint32_t in_cable = (r - a.hold_base) % a.hold_cable_rows, first = 1u + (a.hold_zero_pid - 1u) * a.hold_pid_rows;
+      zero = zero || (in_cable >= first && in_cable < first + a.hold_pid_rows);
+    }
+    a.dst[(size_t)r * a.dst_stride + t] = zero ? 0.0 : a.src[(size_t)r * a.src_stride + b];
+  }
+}
+struct Roll64CmdArgs {
+  const float* commands;  // float[B][H][S][n]
+  float* out;             // float[B * S][n]: the Joy batch of step k
+  uint32_t batch, samples, horizon, n, k;
+};
+static __global__ __launch_bounds__(256) void cdpr_roll64_cmd_kernel(const Roll64CmdArgs a) {
+  const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+  if (e >= a.batch * a.samples * a.n) return;
+  const uint32_t t = e / a.n, i = e - t * a.n, b = t / a.samples, s = t - b * a.samples;
+  a.out[e] = a.commands[(((size_t)b * a.horizon + a.k) * a.samples + s) * a.n + i];
+}
+struct Roll64CostArgs {
+  const double* state;  // the trajectories' state rows (rows 0..2: position)
+  const float* ref;     // float[B][3]
+  double* acc;          // double[B * S]
+  float* out;           // float[B][S], written with the last step (nullptr before)
+  uint32_t stride, batch, samples;
+};
+static __global__ __launch_bounds__(256) void cdpr_roll64_cost_kernel(const Roll64CostArgs a) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= a.batch * a.samples) return;
+  const uint32_t b = t / a.samples;
+  const double ex = a.state[t] - (double)a.ref[3 * b], ey = a.state[(size_t)a.stride + t] - (double)a.ref[3 * b + 1],
+               ez = a.state[(size_t)2 * a.stride + t] - (double)a.ref[3 * b + 2];
+  const double c = a.acc[t] + fma(ez, ez, fma(ey, ey, ex * ex));
+  a.acc[t] = c;
+  if (a.out) a.out[t] = (float)c;
+}
+
+}  // namespace cdpr
+
 namespace cdpr_host {
 
 // rows of an fp64 handle's state: platform, FK estimate, one Pid's rows per cable - and, hold branch live, both Pids' records
@@ -188,8 +257,7 @@ int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, vo
 
 // Queue one rollout on the handle's stream: trajectories = batch * samples, reference positions and costs in
 // DEVICE buffers.  Nothing is allocated, copied or synchronised here.
-// The rollout of a precision = 64 handle (uniform modes; with the hold branch / cascades / cmd_limit 0 since the end of round 6): see Roll64Args
-// (cdpr_step_kernel_f64.hpp).
+// The rollout of a precision = 64 handle (uniform modes; with the hold branch / cascades / cmd_limit 0 since the end of round 6): see Roll64Args above.
 int rollout_enqueue_f64(cdpr_engine* h, int samples, int horizon, const float* d_commands, const float* d_ref, float* d_cost) {
   const uint32_t n = h->n;
   const uint64_t traj = (uint64_t)h->batch * (uint64_t)samples;

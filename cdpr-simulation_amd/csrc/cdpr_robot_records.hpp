@@ -73,7 +73,7 @@ struct F64Records {
   uint32_t state_rows, obs_rows;
   uint32_t hold;             // HOLD handles: both Pids of every cable live in their own rows behind the state rows (f64_hold_row)
   uint32_t hold_win;         // ... samples such a record's window holds (kHoldWin | kHoldWinLong)
-  uint32_t win;              // prior errors kept per cable (kWin | kWinLong): the integral is row kF64StateCtrl + (win + 1) i + win
+  uint32_t win;              // prior errors kept per cable (kWin | kWinLong): the integral is row f64_integral_row(i, win)
   double home[7];            // cdpr_config_t.home_pose as it is (upload_home64)
 };
 
@@ -102,7 +102,7 @@ CDPR_DEV void pid_reset(const F64Records& v, uint32_t r, int which) {
     for (uint32_t i = 0; i < v.n; ++i)
       for (int row = 0; row < hold_pid_rows((int)v.hold_win); ++row) S[(size_t)(f64_hold_row((int)v.n, (int)i, which, (int)v.hold_win) + row) * v.stride] = 0.0;
   } else {
-    for (uint32_t i = 0; i < v.n; ++i) S[(size_t)(kF64StateCtrl + (v.win + 1u) * i + v.win) * v.stride] = 0.0;
+    for (uint32_t i = 0; i < v.n; ++i) S[(size_t)f64_integral_row((int)i, (int)v.win) * v.stride] = 0.0;
   }
 }
 

@@ -117,7 +117,10 @@ constexpr int kWinLong = 31;  // the ring of a derivative window of 12 .. 32 sam
 // goes on with the FK estimate (7) and the controller rows, the image with the FK residual, its iteration count, the flags, the joint rows
 constexpr int kF64Pose = 0, kF64Twist = 7, kF64StateFk = 13, kF64StateCtrl = 20;
 constexpr int kF64ObsResidual = 13, kF64ObsIterations = 14, kF64ObsFlags = 15, kF64ObsJoint = 16;
-__host__ __device__ constexpr int f64_state_rows(int n, int w = kWin) { return kF64StateCtrl + (w + 1) * n; }
+// ring row k (k = w: the integral) of cable i's single Pid record at a derivative ring of w prior errors; n such records make the state
+__host__ __device__ constexpr int f64_ring_row(int i, int k, int w = kWin) { return kF64StateCtrl + (w + 1) * i + k; }
+__host__ __device__ constexpr int f64_integral_row(int i, int w = kWin) { return f64_ring_row(i, w, w); }
+__host__ __device__ constexpr int f64_state_rows(int n, int w = kWin) { return f64_ring_row(n, 0, w); }
 // HOLD handles keep BOTH Pids of every cable behind those rows: per cable mLastPosition (JFC.h:45), then per Pid (0 position,
 // 1 velocity) one packed word (kHwHead ... kHwWas below) |
 // mIerr | the window's values | the window's stamps (world steps, exact in a double) | mCmd | the biquads' states
@@ -527,6 +530,12 @@ __device__ __forceinline__ double hold_finish64(double* R, size_t st, const Hold
   return was ? out : 0.0;
 }
 
+}  // namespace cdpr
+
+#include "cdpr_step_stages_f64.hpp"  // one definition of each stage of the step for the two kernels below
+
+namespace cdpr {
+
 // RING_LDS: the derivative rings of a lane's cables are loaded once, in one batch, into LDS columns (40 KiB per wave at
 // n = 8) and written back at the end: the FIR then costs no memory round trip per cable and step (small batches: the step
 // is one latency chain).  Otherwise they stay in HBM / L2 (large batches: four waves per CU need the LDS).
@@ -584,19 +593,20 @@ __global__ __launch_bounds__(64) void cdpr_step_kernel_f64(const F64Args a) {
   if (r >= a.batch) return;  // no barrier below: lanes are independent, LDS columns are private
   const size_t st = a.stride;
   double* const S = a.state + r;
-  double p[3] = {S[0 * st], S[1 * st], S[2 * st]};
-  double q4[4] = {S[3 * st], S[4 * st], S[5 * st], S[6 * st]};
-  double v[3] = {S[7 * st], S[8 * st], S[9 * st]}, om[3] = {S[10 * st], S[11 * st], S[12 * st]};
-  double fkp[3] = {S[13 * st], S[14 * st], S[15 * st]};
-  double fkq[4] = {S[16 * st], S[17 * st], S[18 * st], S[19 * st]};
+  double p[3] = {S[(kF64Pose + 0) * st], S[(kF64Pose + 1) * st], S[(kF64Pose + 2) * st]};
+  double q4[4] = {S[(kF64Pose + 3) * st], S[(kF64Pose + 4) * st], S[(kF64Pose + 5) * st], S[(kF64Pose + 6) * st]};
+  double v[3] = {S[(kF64Twist + 0) * st], S[(kF64Twist + 1) * st], S[(kF64Twist + 2) * st]};
+  double om[3] = {S[(kF64Twist + 3) * st], S[(kF64Twist + 4) * st], S[(kF64Twist + 5) * st]};
+  double fkp[3] = {S[(kF64StateFk + 0) * st], S[(kF64StateFk + 1) * st], S[(kF64StateFk + 2) * st]};
+  double fkq[4] = {S[(kF64StateFk + 3) * st], S[(kF64StateFk + 4) * st], S[(kF64StateFk + 5) * st], S[(kF64StateFk + 6) * st]};
   // the integrals and the commands (and, RING_LDS, the derivative rings) in one batch of loads
 #pragma unroll
   for (int i = 0; i < N; ++i) {
-    if (!HOLD) c_ierr[i][lane] = S[(size_t)(20 + (W + 1) * i + W) * st];
+    if (!HOLD) c_ierr[i][lane] = S[(size_t)f64_integral_row(i, W) * st];
     c_des[i][lane] = (double)a.cmd[(size_t)r * N + i];
     if (RING_LDS) {
 #pragma unroll
-      for (int k = 0; k < W; ++k) c_win[RING_LDS ? i : 0][RING_LDS ? k : 0][lane] = S[(size_t)(20 + (W + 1) * i + k) * st];
+      for (int k = 0; k < W; ++k) c_win[RING_LDS ? i : 0][RING_LDS ? k : 0][lane] = S[(size_t)f64_ring_row(i, k, W) * st];
     }
   }
   // uniform handles: mode and call count are launch arguments; PR: this robot's own (per lane)
@@ -634,8 +644,8 @@ __global__ __launch_bounds__(64) void cdpr_step_kernel_f64(const F64Args a) {
         if constexpr (HOLD) hrows = hold_load64<HW>(HR, LP, st);
         double L, j[6];
         ik_row64(c_geom + i * 7, R, p, L, j);
-        const double q = c_geom[i * 7 + 6] - L;
-        const double qd = -fma(j[5], om[2], fma(j[4], om[1], fma(j[3], om[0], fma(j[2], v[2], fma(j[1], v[1], j[0] * v[0])))));
+        double q, qd;
+        joint_coords64(c_geom[i * 7 + 6], L, j, v[0], v[1], v[2], om[0], om[1], om[2], q, qd);
         c_len[i][lane] = L;
         c_q[i][lane] = q;
         c_qd[i][lane] = qd;
@@ -673,7 +683,7 @@ __global__ __launch_bounds__(64) void cdpr_step_kernel_f64(const F64Args a) {
           const double error = desired - (actual_is_vel ? qd : q);
           double acc = wt[W] * error;
 #pragma unroll
-          for (int k = 0; k < W; ++k) acc = fma(wt[k], RING_LDS ? c_win[RING_LDS ? i : 0][RING_LDS ? k : 0][lane] : S[(size_t)(20 + (W + 1) * i + k) * st], acc);
+          for (int k = 0; k < W; ++k) acc = fma(wt[k], RING_LDS ? c_win[RING_LDS ? i : 0][RING_LDS ? k : 0][lane] : S[(size_t)f64_ring_row(i, k, W) * st], acc);
           const double p_term = kp * error;
           const double prev_ierr = c_ierr[i][lane];
           double ie = fma(a.dt, error, prev_ierr);
@@ -697,7 +707,7 @@ __global__ __launch_bounds__(64) void cdpr_step_kernel_f64(const F64Args a) {
           c_ierr[i][lane] = ie;
           force = out;
           if (RING_LDS) c_win[RING_LDS ? i : 0][RING_LDS ? ring_slot : 0][lane] = error;  // (the next steps of this launch read it there)
-          S[(size_t)(20 + (W + 1) * i + ring_slot) * st] = error;  // after the FIR has read the slot's old content; the slot, not the ring at the end
+          S[(size_t)f64_ring_row(i, ring_slot, W) * st] = error;  // after the FIR has read the slot's old content; the slot, not the ring at the end
           if (i == 0) {
             dbg_p = p_term;
             dbg_i = i_raw;
@@ -809,43 +819,29 @@ __global__ __launch_bounds__(64) void cdpr_step_kernel_f64(const F64Args a) {
           td_flag |= (tc != t) ? 1 : 0;
           applied = tc;
         }
-        const double qd = c_qd[i][lane], q = c_q[i][lane];
-        if (a.vel_limit > 0.0)  // Joint::SetForce velocity truncation [EXT]
-          applied = ((qd > a.vel_limit && applied > 0.0) || (qd < -a.vel_limit && applied < 0.0)) ? 0.0 : applied;
-        if (a.effort >= 0.0) applied = fmax(fmin(applied, a.effort), -a.effort);  // Joint::SetForce clamp (cube.sdf:438)
-        if (a.travel_on && (q < a.travel_lo || q > a.travel_hi)) lim |= 1u << i;
-        c_f[i][lane] = applied;
+        c_f[i][lane] = setforce_limits64(applied, c_q[i][lane], c_qd[i][lane], a.vel_limit, a.effort, a.travel_on, a.travel_lo, a.travel_hi, i, lim);
       }
     }
-    if (a.dbg) {  // `pid` topic, cable 0 only (PLG.cpp:223-227; Pid.cpp:139-142,158-168)
-      double* d = a.dbg + (size_t)r * 9;
-      if (HOLD ? dbg_ran : run_pid) {
-        d[0] = dbg_p;
-        d[1] = dbg_i;
-        d[2] = dbg_d;
-        d[3] = HOLD ? dbg_des : c_des[0][lane];
-      }
-      d[4] = c_f[0][lane];
-    }
+    if (a.dbg) write_pid_topic64(a.dbg + (size_t)r * 9, HOLD ? dbg_ran : run_pid, dbg_p, dbg_i, dbg_d, HOLD ? dbg_des : c_des[0][lane], c_f[0][lane]);
     // ---- observables of step t_k (PLG.cpp:236-242, 248-280)
     if ((a.publish_mask >> step) & 1ull) {
       double* const O = a.obs + (size_t)step * a.obs_step_stride + r;
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        O[(size_t)c * st] = p[c];
-        O[(size_t)(7 + c) * st] = v[c];
-        O[(size_t)(10 + c) * st] = om[c];
+        O[(size_t)(kF64Pose + c) * st] = p[c];
+        O[(size_t)(kF64Twist + c) * st] = v[c];
+        O[(size_t)(kF64Twist + 3 + c) * st] = om[c];
       }
 #pragma unroll
-      for (int c = 0; c < 4; ++c) O[(size_t)(3 + c) * st] = q4[c];
-      O[13 * st] = fk_res;
-      O[14 * st] = (double)fk_it;
-      O[15 * st] = (double)((uint32_t)td_flag | (lim << 1));
+      for (int c = 0; c < 4; ++c) O[(size_t)(kF64Pose + 3 + c) * st] = q4[c];
+      O[kF64ObsResidual * st] = fk_res;
+      O[kF64ObsIterations * st] = (double)fk_it;
+      O[kF64ObsFlags * st] = (double)((uint32_t)td_flag | (lim << 1));
 #pragma clang loop unroll_count(kCableUnroll)
       for (int i = 0; i < N; ++i) {
-        O[(size_t)(16 + i) * st] = c_q[i][lane];
-        O[(size_t)(16 + N + i) * st] = c_qd[i][lane];
-        O[(size_t)(16 + 2 * N + i) * st] = c_f[i][lane];
+        O[(size_t)(kF64ObsJoint + i) * st] = c_q[i][lane];
+        O[(size_t)(kF64ObsJoint + N + i) * st] = c_qd[i][lane];
+        O[(size_t)(kF64ObsJoint + 2 * N + i) * st] = c_f[i][lane];
       }
     }
     // ---- world step to t_{k+1}: wrench = -J^T (applied - d qdot) + m g, semi-implicit Euler
@@ -865,10 +861,7 @@ __global__ __launch_bounds__(64) void cdpr_step_kernel_f64(const F64Args a) {
 #pragma unroll
           for (int c = 0; c < 6; ++c) c_js[TSTOP ? i : 0][TSTOP ? c : 0][lane] = j[c];
         }
-        double t = fma(-a.damping, c_qd[i][lane], c_f[i][lane]);
-        if (a.unilateral) t = fmax(t, 0.0);
-#pragma unroll
-        for (int c = 0; c < 6; ++c) w[c] = fma(-j[c], t, w[c]);
+        wrench_add64(j, a.damping, a.unilateral, c_qd[i][lane], c_f[i][lane], w);
       }
       bool lumped_done = false;
       if constexpr (TSTOP) {
@@ -977,7 +970,7 @@ __global__ __launch_bounds__(64) void cdpr_step_kernel_f64(const F64Args a) {
 #pragma unroll
             for (int c = 0; c < 6; ++c) j[c] = c_js[TSTOP ? i : 0][TSTOP ? c : 0][lane];
             const double qi = c_q[i][lane];
-            const double qdn = -fma(j[5], om[2], fma(j[4], om[1], fma(j[3], om[0], fma(j[2], v[2], fma(j[1], v[1], j[0] * v[0])))));
+            const double qdn = joint_velocity64(j, v[0], v[1], v[2], om[0], om[1], om[2]);
             const bool hit = (qi >= a.travel_hi && qdn > 0.0) || (qi <= a.travel_lo && qdn < 0.0);
             // Iw^-1 (rb x u) = R Ib^-1 R^T (rb x u)
             const double sb[3] = {fma(R.r20, j[5], fma(R.r10, j[4], R.r00 * j[3])), fma(R.r21, j[5], fma(R.r11, j[4], R.r01 * j[3])),
@@ -998,37 +991,25 @@ __global__ __launch_bounds__(64) void cdpr_step_kernel_f64(const F64Args a) {
           }
         }
       }
-      p[0] = fma(a.dt, v[0], p[0]);
-      p[1] = fma(a.dt, v[1], p[1]);
-      p[2] = fma(a.dt, v[2], p[2]);
-      const double h = a.half_dt, x = q4[0], y = q4[1], z = q4[2], ww = q4[3];
-      const double nx = fma(h, fma(-om[2], y, fma(om[1], z, ww * om[0])), x);
-      const double ny = fma(h, fma(-om[0], z, fma(om[2], x, ww * om[1])), y);
-      const double nz = fma(h, fma(-om[1], x, fma(om[0], y, ww * om[2])), z);
-      const double nw = fma(-h, fma(om[2], z, fma(om[1], y, om[0] * x)), ww);
-      const double inv = rsqrt64(fma(nw, nw, fma(nz, nz, fma(ny, ny, nx * nx))));
-      q4[0] = nx * inv;
-      q4[1] = ny * inv;
-      q4[2] = nz * inv;
-      q4[3] = nw * inv;
+      pose_integrate64(a.dt, a.half_dt, v[0], v[1], v[2], om[0], om[1], om[2], p, q4);
     }
   }
   // ---- store
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    S[(size_t)c * st] = p[c];
-    S[(size_t)(7 + c) * st] = v[c];
-    S[(size_t)(10 + c) * st] = om[c];
-    S[(size_t)(13 + c) * st] = fkp[c];
+    S[(size_t)(kF64Pose + c) * st] = p[c];
+    S[(size_t)(kF64Twist + c) * st] = v[c];
+    S[(size_t)(kF64Twist + 3 + c) * st] = om[c];
+    S[(size_t)(kF64StateFk + c) * st] = fkp[c];
   }
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    S[(size_t)(3 + c) * st] = q4[c];
-    S[(size_t)(16 + c) * st] = fkq[c];
+    S[(size_t)(kF64Pose + 3 + c) * st] = q4[c];
+    S[(size_t)(kF64StateFk + 3 + c) * st] = fkq[c];
   }
 #pragma clang loop unroll_count(kCableUnroll)
   for (int i = 0; i < N; ++i) {
-    if (!HOLD) S[(size_t)(20 + (W + 1) * i + W) * st] = c_ierr[i][lane];  // (HOLD: the integrals live in the Pids' own rows)
+    if (!HOLD) S[(size_t)f64_integral_row(i, W) * st] = c_ierr[i][lane];  // (HOLD: the integrals live in the Pids' own rows)
   }
   if (PR) a.meta[r] = (uint8_t)((meta & kMetaModeMask) | ((uint32_t)calls << kMetaCallShift));
 }
@@ -1052,7 +1033,7 @@ __global__ __launch_bounds__(128, LEAN ? 2 : 1) void cdpr_split_kernel_f64(const
   __shared__ double c_jt[LEAN ? 1 : N][LEAN ? 1 : 6][64];  // rows at the true pose (controller wave: IK stage -> world step)
   __shared__ double c_je[LEAN ? 1 : N][LEAN ? 1 : 6][64];  // rows at the FK estimate (estimator wave: closing evaluation -> tension distribution)
   __shared__ double x_est[3][64];    // estimator -> controller: residual, iterations, infeasible flag
-  __shared__ double c_park[HOLD ? 13 : 1][64];  // HOLD: the controller wave's platform state between its IK stage and the world step
+  __shared__ double c_park[HOLD ? kF64StateFk : 1][64];  // HOLD: the controller wave's platform state between its IK stage and the world step
 #ifndef CDPR_F64_HOLD_KU
 #define CDPR_F64_HOLD_KU N
 #endif
@@ -1080,10 +1061,10 @@ __global__ __launch_bounds__(128, LEAN ? 2 : 1) void cdpr_split_kernel_f64(const
     // (measured and not kept: s_setprio 3 for this wave in the LEAN build, as cdpr_split_kernel has it: 24.1 against 23.65 us)
     CDPR_F64_STAMP(0);
     CDPR_F64_CLOCK(6);
-    const double p[3] = {S[0 * st], S[1 * st], S[2 * st]};
-    const double q4[4] = {S[3 * st], S[4 * st], S[5 * st], S[6 * st]};
-    double fkp[3] = {S[13 * st], S[14 * st], S[15 * st]};
-    double fkq[4] = {S[16 * st], S[17 * st], S[18 * st], S[19 * st]};
+    const double p[3] = {S[(kF64Pose + 0) * st], S[(kF64Pose + 1) * st], S[(kF64Pose + 2) * st]};
+    const double q4[4] = {S[(kF64Pose + 3) * st], S[(kF64Pose + 4) * st], S[(kF64Pose + 5) * st], S[(kF64Pose + 6) * st]};
+    double fkp[3] = {S[(kF64StateFk + 0) * st], S[(kF64StateFk + 1) * st], S[(kF64StateFk + 2) * st]};
+    double fkq[4] = {S[(kF64StateFk + 3) * st], S[(kF64StateFk + 4) * st], S[(kF64StateFk + 5) * st], S[(kF64StateFk + 6) * st]};
     CDPR_F64_LANDED();
     CDPR_F64_STAMP(1);
     {
@@ -1146,9 +1127,9 @@ __global__ __launch_bounds__(128, LEAN ? 2 : 1) void cdpr_split_kernel_f64(const
     }
     if (live) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) S[(size_t)(13 + c) * st] = fkp[c];
+      for (int c = 0; c < 3; ++c) S[(size_t)(kF64StateFk + c) * st] = fkp[c];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) S[(size_t)(16 + c) * st] = fkq[c];
+      for (int c = 0; c < 4; ++c) S[(size_t)(kF64StateFk + 3 + c) * st] = fkq[c];
     }
     // the tension distribution's matrix and its factor need no forces
     double m[6][6], invd[6];
@@ -1249,10 +1230,15 @@ __global__ __launch_bounds__(128, LEAN ? 2 : 1) void cdpr_split_kernel_f64(const
 #endif
   if (LEAN && CDPR_F64_CTL_SLEEP) __builtin_amdgcn_s_sleep(CDPR_F64_CTL_SLEEP);  // the estimator wave's fourteen rows ahead of this wave's fifty: its chain is the launch's
   CDPR_F64_STAMP(8);
-  double p[3] = {S[0 * st], S[1 * st], S[2 * st]};
-  double q4[4] = {S[3 * st], S[4 * st], S[5 * st], S[6 * st]};
-  double v[3] = {S[7 * st], S[8 * st], S[9 * st]}, om[3] = {S[10 * st], S[11 * st], S[12 * st]};
+  double p[3] = {S[(kF64Pose + 0) * st], S[(kF64Pose + 1) * st], S[(kF64Pose + 2) * st]};
+  double q4[4] = {S[(kF64Pose + 3) * st], S[(kF64Pose + 4) * st], S[(kF64Pose + 5) * st], S[(kF64Pose + 6) * st]};
+  double v[3] = {S[(kF64Twist + 0) * st], S[(kF64Twist + 1) * st], S[(kF64Twist + 2) * st]};
+  double om[3] = {S[(kF64Twist + 3) * st], S[(kF64Twist + 4) * st], S[(kF64Twist + 5) * st]};
   const uint32_t rc = live ? r : a.batch - 1u;
+  // (the ring and integral rows of this wave as the expression f64_ring_row stands for, not as calls of it: with the calls the lean
+  //  build - cdpr_split_kernel_f64<8, LEAN> - comes out 3.6 % shorter, 44 -> 4 spilled SGPRs, and slower: 23.22 - 23.61 us per step at
+  //  65 536 x 8 against 22.63 - 22.81 for this form and 22.70 - 23.04 for the parent, four interleaved repetitions of the three builds,
+  //  profiles/r16_f64_stages_ab.txt)
   if constexpr (HOLD != 0) {
     float joy[N];
 #pragma unroll
@@ -1264,11 +1250,11 @@ __global__ __launch_bounds__(128, LEAN ? 2 : 1) void cdpr_split_kernel_f64(const
   } else {
 #pragma clang loop unroll_count(kU)
     for (int i = 0; i < N; ++i) {
-      c_ierr[i][lane] = S[(size_t)(20 + 11 * i + 10) * st];
+      c_ierr[i][lane] = S[(size_t)(kF64StateCtrl + (kWin + 1) * i + kWin) * st];
       c_des[i][lane] = (double)a.cmd[(size_t)rc * N + i];
       if (!LEAN) {
 #pragma unroll
-        for (int k = 0; k < kWin; ++k) c_win[LEAN ? 0 : i][LEAN ? 0 : k][lane] = S[(size_t)(20 + 11 * i + k) * st];
+        for (int k = 0; k < kWin; ++k) c_win[LEAN ? 0 : i][LEAN ? 0 : k][lane] = S[(size_t)(kF64StateCtrl + (kWin + 1) * i + k) * st];
       }
     }
   }
@@ -1327,12 +1313,12 @@ __global__ __launch_bounds__(128, LEAN ? 2 : 1) void cdpr_split_kernel_f64(const
       if (publish) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          O[(size_t)c * st] = p[c];
-          O[(size_t)(7 + c) * st] = v[c];
-          O[(size_t)(10 + c) * st] = om[c];
+          O[(size_t)(kF64Pose + c) * st] = p[c];
+          O[(size_t)(kF64Twist + c) * st] = v[c];
+          O[(size_t)(kF64Twist + 3 + c) * st] = om[c];
         }
 #pragma unroll
-        for (int c = 0; c < 4; ++c) O[(size_t)(3 + c) * st] = q4[c];
+        for (int c = 0; c < 4; ++c) O[(size_t)(kF64Pose + 3 + c) * st] = q4[c];
       }
       // IK of every cable, straight-line: joint position and velocity into their LDS columns (and out as observables); the platform
       // state then waits in LDS for the world step - its 26 registers are the passes' (two cables at a time: the first pass's rows are
@@ -1344,13 +1330,13 @@ __global__ __launch_bounds__(128, LEAN ? 2 : 1) void cdpr_split_kernel_f64(const
       for (int i = 0; i < N; ++i) {
         double L, j[6];
         ik_row64(c_geom + i * 7, R, p, L, j);
-        const double q = c_geom[i * 7 + 6] - L;
-        const double qd = -fma(j[5], om[2], fma(j[4], om[1], fma(j[3], om[0], fma(j[2], v[2], fma(j[1], v[1], j[0] * v[0])))));
+        double q, qd;
+        joint_coords64(c_geom[i * 7 + 6], L, j, v[0], v[1], v[2], om[0], om[1], om[2], q, qd);
         c_q[i][lane] = q;
         c_qd[i][lane] = qd;
         if (publish) {
-          O[(size_t)(16 + i) * st] = q;
-          O[(size_t)(16 + N + i) * st] = qd;
+          O[(size_t)(kF64ObsJoint + i) * st] = q;
+          O[(size_t)(kF64ObsJoint + N + i) * st] = qd;
         }
         if (!LEAN) {
 #pragma unroll
@@ -1358,9 +1344,9 @@ __global__ __launch_bounds__(128, LEAN ? 2 : 1) void cdpr_split_kernel_f64(const
         }
       }
 #pragma unroll
-      for (int c = 0; c < 3; ++c) c_park[c][lane] = p[c], c_park[7 + c][lane] = v[c], c_park[10 + c][lane] = om[c];
+      for (int c = 0; c < 3; ++c) c_park[kF64Pose + c][lane] = p[c], c_park[kF64Twist + c][lane] = v[c], c_park[kF64Twist + 3 + c][lane] = om[c];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) c_park[3 + c][lane] = q4[c];
+      for (int c = 0; c < 4; ++c) c_park[kF64Pose + 3 + c][lane] = q4[c];
 #pragma clang loop unroll(disable)
       for (int i0 = 0;;) {  // (the next pass's requests at the END of a pass: asked for at its head behind `i0 > 0`, the rows would stay alive across the rare path)
         double qq[Q], qdq[Q];
@@ -1453,19 +1439,19 @@ __global__ __launch_bounds__(128, LEAN ? 2 : 1) void cdpr_split_kernel_f64(const
     if (kRingAhead && run_pid) {
 #pragma unroll
       for (int k = 0; k < kWin; ++k) {
-        rn0[k] = S[(size_t)(20 + 11 * 0 + k) * st];
-        rn1[k] = S[(size_t)(20 + 11 * (N > 1 ? 1 : 0) + k) * st];
+        rn0[k] = S[(size_t)(kF64StateCtrl + (kWin + 1) * 0 + k) * st];
+        rn1[k] = S[(size_t)(kF64StateCtrl + (kWin + 1) * (N > 1 ? 1 : 0) + k) * st];
       }
     }
     if (publish) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        O[(size_t)c * st] = p[c];
-        O[(size_t)(7 + c) * st] = v[c];
-        O[(size_t)(10 + c) * st] = om[c];
+        O[(size_t)(kF64Pose + c) * st] = p[c];
+        O[(size_t)(kF64Twist + c) * st] = v[c];
+        O[(size_t)(kF64Twist + 3 + c) * st] = om[c];
       }
 #pragma unroll
-      for (int c = 0; c < 4; ++c) O[(size_t)(3 + c) * st] = q4[c];
+      for (int c = 0; c < 4; ++c) O[(size_t)(kF64Pose + 3 + c) * st] = q4[c];
     }
 #pragma clang loop unroll_count(kUc)
     for (int i = 0; i < N; ++i) {
@@ -1478,18 +1464,18 @@ __global__ __launch_bounds__(128, LEAN ? 2 : 1) void cdpr_split_kernel_f64(const
         }
         if (i + 2 < N) {
 #pragma unroll
-          for (int k = 0; k < kWin; ++k) rn1[k] = S[(size_t)(20 + 11 * (i + 2) + k) * st];
+          for (int k = 0; k < kWin; ++k) rn1[k] = S[(size_t)(kF64StateCtrl + (kWin + 1) * (i + 2) + k) * st];
         }
       }
       double L, j[6];
       ik_row64(c_geom + i * 7, R, p, L, j);
-      const double q = c_geom[i * 7 + 6] - L;
-      const double qd = -fma(j[5], om[2], fma(j[4], om[1], fma(j[3], om[0], fma(j[2], v[2], fma(j[1], v[1], j[0] * v[0])))));
+      double q, qd;
+      joint_coords64(c_geom[i * 7 + 6], L, j, v[0], v[1], v[2], om[0], om[1], om[2], q, qd);
       c_q[i][lane] = q;
       c_qd[i][lane] = qd;
       if (publish) {
-        O[(size_t)(16 + i) * st] = q;
-        O[(size_t)(16 + N + i) * st] = qd;
+        O[(size_t)(kF64ObsJoint + i) * st] = q;
+        O[(size_t)(kF64ObsJoint + N + i) * st] = qd;
       }
       if (!LEAN) {
 #pragma unroll
@@ -1527,8 +1513,8 @@ __global__ __launch_bounds__(128, LEAN ? 2 : 1) void cdpr_split_kernel_f64(const
         // every cable back at the end of the launch until round 6: 1.4 us of stores behind the critical path at one robot); and the
         // integral from here as well, not from the tail
         if (live) {
-          a.state[(size_t)(20 + 11 * i + ring_slot) * st + r] = error;
-          a.state[(size_t)(20 + 11 * i + 10) * st + r] = ie;
+          a.state[(size_t)(kF64StateCtrl + (kWin + 1) * i + ring_slot) * st + r] = error;
+          a.state[(size_t)(kF64StateCtrl + (kWin + 1) * i + kWin) * st + r] = ie;
         }
         if (i == 0) {
           dbg_p = p_term;
@@ -1570,40 +1556,25 @@ __global__ __launch_bounds__(128, LEAN ? 2 : 1) void cdpr_split_kernel_f64(const
   CDPR_F64_STAMP(11);
   if constexpr (HOLD != 0) {  // (the platform state waited in LDS)
 #pragma unroll
-    for (int c = 0; c < 3; ++c) p[c] = c_park[c][lane], v[c] = c_park[7 + c][lane], om[c] = c_park[10 + c][lane];
+    for (int c = 0; c < 3; ++c) p[c] = c_park[kF64Pose + c][lane], v[c] = c_park[kF64Twist + c][lane], om[c] = c_park[kF64Twist + 3 + c][lane];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) q4[c] = c_park[3 + c][lane];
+    for (int c = 0; c < 4; ++c) q4[c] = c_park[kF64Pose + 3 + c][lane];
   }
   const double fk_res = x_est[0][lane], fk_it = x_est[1][lane];
   const uint32_t td_flag = (uint32_t)x_est[2][lane];
   uint32_t lim = 0u;
 #pragma clang loop unroll_count(kU)
   for (int i = 0; i < N; ++i) {
-    double applied = c_f[i][lane];
-    const double qd = c_qd[i][lane], q = c_q[i][lane];
-    if (a.vel_limit > 0.0)  // Joint::SetForce velocity truncation [EXT]
-      applied = ((qd > a.vel_limit && applied > 0.0) || (qd < -a.vel_limit && applied < 0.0)) ? 0.0 : applied;
-    if (a.effort >= 0.0) applied = fmax(fmin(applied, a.effort), -a.effort);  // Joint::SetForce clamp (cube.sdf:438)
-    if (a.travel_on && (q < a.travel_lo || q > a.travel_hi)) lim |= 1u << i;
-    c_f[i][lane] = applied;
+    c_f[i][lane] = setforce_limits64(c_f[i][lane], c_q[i][lane], c_qd[i][lane], a.vel_limit, a.effort, a.travel_on, a.travel_lo, a.travel_hi, i, lim);
   }
-  if (a.dbg && live) {  // `pid` topic, cable 0 only (PLG.cpp:223-227; Pid.cpp:139-142,158-168)
-    double* d = a.dbg + (size_t)r * 9;
-    if (HOLD ? dbg_ran : run_pid) {
-      d[0] = dbg_p;
-      d[1] = dbg_i;
-      d[2] = dbg_d;
-      d[3] = HOLD ? dbg_des : c_des[0][lane];
-    }
-    d[4] = c_f[0][lane];
-  }
+  if (a.dbg && live) write_pid_topic64(a.dbg + (size_t)r * 9, HOLD ? dbg_ran : run_pid, dbg_p, dbg_i, dbg_d, HOLD ? dbg_des : c_des[0][lane], c_f[0][lane]);
   // ---- observables of step t_k (PLG.cpp:236-242, 248-280)
   if (publish) {  // (the rest of the image left with the IK stage)
-    O[13 * st] = fk_res;
-    O[14 * st] = fk_it;
-    O[15 * st] = (double)(td_flag | (lim << 1));
+    O[kF64ObsResidual * st] = fk_res;
+    O[kF64ObsIterations * st] = fk_it;
+    O[kF64ObsFlags * st] = (double)(td_flag | (lim << 1));
 #pragma clang loop unroll_count(kU)
-    for (int i = 0; i < N; ++i) O[(size_t)(16 + 2 * N + i) * st] = c_f[i][lane];
+    for (int i = 0; i < N; ++i) O[(size_t)(kF64ObsJoint + 2 * N + i) * st] = c_f[i][lane];
   }
   // ---- world step to t_{k+1}: wrench = -J^T (applied - d qdot) + m g, semi-implicit Euler
   {
@@ -1621,10 +1592,7 @@ __global__ __launch_bounds__(128, LEAN ? 2 : 1) void cdpr_split_kernel_f64(const
 #pragma unroll
         for (int c = 0; c < 6; ++c) j[c] = c_jt[LEAN ? 0 : i][LEAN ? 0 : c][lane];
       }
-      double t = fma(-a.damping, c_qd[i][lane], c_f[i][lane]);
-      if (a.unilateral) t = fmax(t, 0.0);
-#pragma unroll
-      for (int c = 0; c < 6; ++c) w[c] = fma(-j[c], t, w[c]);
+      wrench_add64(j, a.damping, a.unilateral, c_qd[i][lane], c_f[i][lane], w);
     }
     v[0] = fma(a.dt * w[0], a.inv_mass, v[0]);
     v[1] = fma(a.dt * w[1], a.inv_mass, v[1]);
@@ -1642,19 +1610,7 @@ __global__ __launch_bounds__(128, LEAN ? 2 : 1) void cdpr_split_kernel_f64(const
     om[0] = fma(a.dt, fma(R.r02, ab[2], fma(R.r01, ab[1], R.r00 * ab[0])), om[0]);
     om[1] = fma(a.dt, fma(R.r12, ab[2], fma(R.r11, ab[1], R.r10 * ab[0])), om[1]);
     om[2] = fma(a.dt, fma(R.r22, ab[2], fma(R.r21, ab[1], R.r20 * ab[0])), om[2]);
-    p[0] = fma(a.dt, v[0], p[0]);
-    p[1] = fma(a.dt, v[1], p[1]);
-    p[2] = fma(a.dt, v[2], p[2]);
-    const double h = a.half_dt, x = q4[0], y = q4[1], z = q4[2], ww = q4[3];
-    const double nx = fma(h, fma(-om[2], y, fma(om[1], z, ww * om[0])), x);
-    const double ny = fma(h, fma(-om[0], z, fma(om[2], x, ww * om[1])), y);
-    const double nz = fma(h, fma(-om[1], x, fma(om[0], y, ww * om[2])), z);
-    const double nw = fma(-h, fma(om[2], z, fma(om[1], y, om[0] * x)), ww);
-    const double inv = rsqrt64(fma(nw, nw, fma(nz, nz, fma(ny, ny, nx * nx))));
-    q4[0] = nx * inv;
-    q4[1] = ny * inv;
-    q4[2] = nz * inv;
-    q4[3] = nw * inv;
+    pose_integrate64(a.dt, a.half_dt, v[0], v[1], v[2], om[0], om[1], om[2], p, q4);
   }
   // ---- store
   CDPR_F64_STAMP(12);
@@ -1662,84 +1618,18 @@ __global__ __launch_bounds__(128, LEAN ? 2 : 1) void cdpr_split_kernel_f64(const
     double* const W = a.state + r;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      W[(size_t)c * st] = p[c];
-      W[(size_t)(7 + c) * st] = v[c];
-      W[(size_t)(10 + c) * st] = om[c];
+      W[(size_t)(kF64Pose + c) * st] = p[c];
+      W[(size_t)(kF64Twist + c) * st] = v[c];
+      W[(size_t)(kF64Twist + 3 + c) * st] = om[c];
     }
 #pragma unroll
-    for (int c = 0; c < 4; ++c) W[(size_t)(3 + c) * st] = q4[c];
+    for (int c = 0; c < 4; ++c) W[(size_t)(kF64Pose + 3 + c) * st] = q4[c];
   }
 #ifdef CDPR_STAMPS
   CDPR_F64_STAMP(13);
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): on gfx9 the stores count too - every store of this wave acknowledged
   CDPR_F64_STAMP(14);
 #endif
-}
-
-// Read-out of double rows into robot-major arrays (double or float), one thread per (robot, column)
-// ---- cdpr_rollout_velocity on a precision = 64 handle (round 6), by composition: every (robot, sampled sequence) becomes a column
-// of a scratch state (expand), every step of the horizon is ONE launch of the handle's own step kernel over those columns with the
-// step's commands gathered into a Joy batch (cmd), and a third kernel adds |p(t_k+1) - p_ref|^2 to the trajectory's cost (cost).
-// No rollout kernel of its own: the rollout in double is there for checking the fp32 one, not for throughput.
-struct Roll64Args {
-  const double* src;  // the handle's state rows
-  double* dst;        // the trajectories' state rows
-  uint32_t src_stride, dst_stride, rows, batch, samples;
-  uint32_t zero_from;  // rows >= this are cleared in the copies (a Joy on jointVelocities in Position mode resets the velocity Pid,
-                       // JFC.cpp:113-115); == rows: none
-  // HOLD handles: that Pid has a record of its own per cable (f64_hold_row) - hold_zero_pid = 1 + the Pid whose records are cleared, 0: none
-  uint32_t hold_base, hold_cable_rows, hold_pid_rows, hold_zero_pid;
-  // per-robot handles: the robot's mode / call-count byte decides (a robot that is not in Velocity mode enters it: its - velocity - Pid
-  // is reset, its count 0); every trajectory gets its own byte
-  const uint8_t* meta_src;
-  uint8_t* meta_dst;
-};
-static __global__ __launch_bounds__(256) void cdpr_roll64_expand_kernel(const Roll64Args a) {
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-  if (t >= a.batch * a.samples) return;
-  const uint32_t b = t / a.samples;
-  bool resets = true;  // (uniform handles: zero_from / hold_zero_pid already say whether the Joy resets the Pid)
-  if (a.meta_src) {
-    const uint32_t m = a.meta_src[b];
-    resets = (m & kMetaModeMask) != kMetaVelocity;
-    a.meta_dst[t] = (uint8_t)(resets ? kMetaVelocity : m);
-  }
-  for (uint32_t r = 0; r < a.rows; ++r) {
-    bool zero = resets && r >= a.zero_from;
-    if (resets && a.hold_zero_pid && r >= a.hold_base) {
-      const uint32_t in_cable = (r - a.hold_base) % a.hold_cable_rows, first = 1u + (a.hold_zero_pid - 1u) * a.hold_pid_rows;
-      zero = zero || (in_cable >= first && in_cable < first + a.hold_pid_rows);
-    }
-    a.dst[(size_t)r * a.dst_stride + t] = zero ? 0.0 : a.src[(size_t)r * a.src_stride + b];
-  }
-}
-struct Roll64CmdArgs {
-  const float* commands;  // float[B][H][S][n]
-  float* out;             // float[B * S][n]: the Joy batch of step k
-  uint32_t batch, samples, horizon, n, k;
-};
-static __global__ __launch_bounds__(256) void cdpr_roll64_cmd_kernel(const Roll64CmdArgs a) {
-  const uint32_t e = blockIdx.x * 256u + threadIdx.x;
-  if (e >= a.batch * a.samples * a.n) return;
-  const uint32_t t = e / a.n, i = e - t * a.n, b = t / a.samples, s = t - b * a.samples;
-  a.out[e] = a.commands[(((size_t)b * a.horizon + a.k) * a.samples + s) * a.n + i];
-}
-struct Roll64CostArgs {
-  const double* state;  // the trajectories' state rows (rows 0..2: position)
-  const float* ref;     // float[B][3]
-  double* acc;          // double[B * S]
-  float* out;           // float[B][S], written with the last step (nullptr before)
-  uint32_t stride, batch, samples;
-};
-static __global__ __launch_bounds__(256) void cdpr_roll64_cost_kernel(const Roll64CostArgs a) {
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-  if (t >= a.batch * a.samples) return;
-  const uint32_t b = t / a.samples;
-  const double ex = a.state[t] - (double)a.ref[3 * b], ey = a.state[(size_t)a.stride + t] - (double)a.ref[3 * b + 1],
-               ez = a.state[(size_t)2 * a.stride + t] - (double)a.ref[3 * b + 2];
-  const double c = a.acc[t] + fma(ez, ez, fma(ey, ey, ex * ex));
-  a.acc[t] = c;
-  if (a.out) a.out[t] = (float)c;
 }
 
 }  // namespace cdpr

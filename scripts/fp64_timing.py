@@ -39,3 +39,22 @@ for B, n, stages in ((1, 8, 3), (4096, 8, 3), (65536, 8, 3)):
             out.append(f"{label}: {np.median(ts):.2f} us/step")
         print(f"hold branch B={B} n={n} stages={stages} fp{prec} ({eng.mapping}): " + ", ".join(out), flush=True)
         eng.close()
+
+# The other families of the one-wave fp64 kernel, by the kernel the handle ran: per-robot modes, derivative windows of 12 .. 32 samples
+# (W = 31), the joint stop with lumped legs (TSTOP), and the long HOLD records (HW = 32).
+from dataclasses import replace
+for B in (1, 65536):
+    model, pose, command, _ = bench.make_workload(pkg, B, 8, 1235, 10)
+    stop = replace(model, passive_damping=0.01, leg_inertia=0.004, travel_lower=-0.004, travel_upper=0.004, travel_stop=2)
+    for label, kw, window in (("per-robot", dict(perRobotCommands=True), None), ("long window", dict(), 16), ("per-robot, long window", dict(perRobotCommands=True), 16),
+                              ("joint stop", dict(model=stop), None), ("hold, long window", dict(velocityEpsilon=0.001), 16)):
+        cfg = pkg.Config(**dict(dict(model=model, batch=B, stages=3, precision=64), **kw))
+        if window:
+            cfg.velocityController.dBufferLength = window
+        eng = pkg.Engine(cfg, 0)
+        eng.set_platform_state(pose7=pose); eng.set_velocity_command(command(0)); eng.update(120); eng.synchronize()
+        ts = []
+        for rnd in range(5):
+            eng.profile_begin(); eng.update(200, 1); ms, nl = eng.profile_end(); ts.append(ms / 200 * 1e3)
+        print(f"{label} B={B} n=8 stages=3 fp64 {eng.kernel_name}: {np.median(ts):.2f} us/step", flush=True)
+        eng.close()

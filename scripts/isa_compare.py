@@ -4,12 +4,16 @@ code or resources?
 
   python scripts/isa_compare.py emit [--jobs 8] CSRC_DIR OUT_DIR [unit ...]   # device-only assembly of every k_*.hip unit
   python scripts/isa_compare.py table OUT_DIR_A OUT_DIR_B                      # the comparison, A -> B
+  python scripts/isa_compare.py rule [--band 1.0] OUT_DIR_A OUT_DIR_B          # the stage-factoring rule on that comparison
 
 `emit` compiles with the unit's flags from csrc/Makefile (FLAGS and the NOVC / NOSLP / k_f64_hold_long additions, read
 from the Makefile of CSRC_DIR).  `table` prints one line per kernel (and per non-inlined device function): "identical"
 where the instruction stream is the same text, else the total and vector instruction counts A -> B; then the resource
 fields of the code object's metadata and the occupancy, and "RESOURCES MOVED" where one of them differs.  A unit whose
-whole text is equal apart from the __hip_cuid_ symbol is reported in one line.  Exit status 1 if any resource moved."""
+whole text is equal apart from the __hip_cuid_ symbol is reported in one line.  Exit status 1 if any resource moved.  `rule` checks, per kernel, what a stage function may not move
+(csrc/cdpr_step_stages_f64.hpp): scratch, spilled VGPRs, LDS and occupancy equal and the vector instruction count not more than
+--band per cent up; it lists the kernels that fail and the ones whose spilled-SGPR, VGPR or AGPR counts moved (allowed, recorded);
+exit status 1 if a kernel fails."""
 import argparse
 import os
 import re
@@ -125,6 +129,39 @@ def table(da, db):
     return 1 if moved else 0
 
 
+HARD_KEYS = [".vgpr_spill_count", ".private_segment_fixed_size", ".group_segment_fixed_size", "occupancy"]
+
+
+def rule(da, db, band):
+    n = ident = failing = 0
+    worst, soft_lines = 0.0, []
+    for f in sorted(os.listdir(da)):
+        if not f.endswith(".s") or not os.path.exists(os.path.join(db, f)):
+            continue
+        ta, tb = open(os.path.join(da, f)).read(), open(os.path.join(db, f)).read()
+        fa, fb, ma, mb = functions(ta), functions(tb), metadata(ta), metadata(tb)
+        names = [k for k in fa if k in fb and k in ma]
+        for k, dn in zip(names, demangle(names)):
+            (ia, oa), (ib, ob) = fa[k], fb[k]
+            n += 1
+            ident += ia == ib
+            va, vb = sum(i.startswith("v_") for i in ia), sum(i.startswith("v_") for i in ib)
+            growth = 100.0 * (vb - va) / va if va else 0.0
+            worst = max(worst, growth)
+            ra, rb = dict(ma[k], occupancy=oa), dict(mb.get(k, {}), occupancy=ob)
+            hard = [f"{x} {ra[x]} -> {rb.get(x)}" for x in HARD_KEYS if ra[x] != rb.get(x)]
+            soft = [f"{x} {ra[x]} -> {rb.get(x)}" for x in ra if x not in HARD_KEYS and ra[x] != rb.get(x)]
+            if hard or growth > band:
+                failing += 1
+                print(f"FAIL {f[:-2]} {dn}: vector {va} -> {vb} ({growth:+.2f} %){'; ' if hard else ''}{', '.join(hard)}")
+            elif soft:
+                soft_lines.append(f"soft {f[:-2]} {dn}: vector {va} -> {vb} ({growth:+.2f} %); {', '.join(soft)}")
+    print("\n".join(soft_lines))
+    print(f"# {n} kernels compared, {ident} identical text, {len(soft_lines)} with only spilled-SGPR / VGPR / AGPR counts moved, "
+          f"worst vector growth {worst:+.2f} %, failing the rule (band {band} %): {failing}")
+    return 1 if failing else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -136,8 +173,12 @@ def main():
     t = sub.add_parser("table")
     t.add_argument("a")
     t.add_argument("b")
+    r = sub.add_parser("rule")
+    r.add_argument("a")
+    r.add_argument("b")
+    r.add_argument("--band", type=float, default=1.0)
     a = ap.parse_args()
-    sys.exit(emit(a.csrc, a.out, a.jobs, a.units) if a.cmd == "emit" else table(a.a, a.b))
+    sys.exit(emit(a.csrc, a.out, a.jobs, a.units) if a.cmd == "emit" else rule(a.a, a.b, a.band) if a.cmd == "rule" else table(a.a, a.b))
 
 
 if __name__ == "__main__":

@@ -85,7 +85,9 @@ def env(**kv):
     return undo
 
 
-def velocity_script(pkg, c, cfg, seed, f64=False, spl=1, rounds=(13, 40, 7, 61, 29, 50), position_at=4, force_at=None, record=False):
+def velocity_script(pkg, c, cfg, seed, f64=False, spl=1, rounds=(13, 40, 7, 61, 29, 50), position_at=4, force_at=None, record=False, names=None, velocity=None, topic=False):
+    """names: a list that collects the kernel of every update; velocity(rng, B, n): the velocity Joys, if not the uniform ones;
+    topic: the `pid` topic's rows join the digest (handles with STAGE_PID_DEBUG)"""
     rng = np.random.default_rng(seed)
     B, n = cfg.batch, cfg.n_cables
     eng = pkg.Engine(cfg, 0)
@@ -97,13 +99,17 @@ def velocity_script(pkg, c, cfg, seed, f64=False, spl=1, rounds=(13, 40, 7, 61, 
         elif force_at is not None and j == force_at:
             eng.set_force_command(rng.uniform(6.0, 12.0, (B, n)).astype(np.float32))
         else:
-            eng.set_velocity_command(rng.uniform(-0.03, 0.03, (B, n)).astype(np.float32))
+            eng.set_velocity_command(velocity(rng, B, n) if velocity else rng.uniform(-0.03, 0.03, (B, n)).astype(np.float32))
         if record:
             r = eng.update_record(k, spl)
             c.add(*[r[key] for key in ("position", "velocity", "effort", "pose", "twist")])
         else:
             eng.update(k, spl)
         c.snap(eng, f64)
+        if topic:
+            c.add(eng.pid_debug())
+        if names is not None:
+            names.append(eng.kernel_name)
     eng.close()
 
 
@@ -224,6 +230,55 @@ def sc_fp64(pkg, c, split, B=130):
         undo()
 
 
+def sc_f64_family(pkg, c, want, cables=8, stages=3, hold=0, lumped=False, **envs):
+    """One family of the fp64 step kernels (`want`: its kernel_name) through velocity, position and force rounds, one-step and fused
+    launches, at B = 130 (two workgroups and a two-lane tail) and at B = 1.  hold: 1 the hold branch, 2 + a cascade, 3 + cmd_limit 0."""
+    eps = 0.001
+    undo = env(**{"CDPR_F64_" + k: v for k, v in envs.pop("f64", {}).items()})
+    try:
+        model = {4: pkg.cube_model, 8: pkg.eight_cable_model, 12: pkg.twelve_cable_model}[cables]() if cables in (4, 8, 12) else None
+        if model is None:
+            full = pkg.eight_cable_model()
+            model = replace(full, frame_anchors=full.frame_anchors[:cables], platform_anchors=full.platform_anchors[:cables])
+        if lumped:
+            model = replace(model, passive_damping=0.01, leg_inertia=0.004, cable_axial_mass=0.001, anchor_point_mass=0.002, anchor_inertia=0.001,
+                            travel_lower=-0.004, travel_upper=0.004, travel_stop=4)
+        window = envs.pop("window", None)
+        for B in (130, 1):
+            cfg = pkg.Config(model=model, batch=B, stages=stages | pkg._abi.STAGE_PID_DEBUG, precision=64, **(dict(envs, velocityEpsilon=eps) if hold else envs))
+            if hold == 2:
+                for f in (cfg.velocityController.pFilter, cfg.velocityController.dFilter):
+                    f.cascade, f.relCutoff, f.quality = 1, 0.05, 0.5
+            if hold == 3:
+                cfg.positionController.cmdLimit = 0.0
+            if window:
+                cfg.velocityController.dBufferLength = window
+            names = []
+            joys = (lambda rng, b, n: hold_commands(rng, b, n, eps)) if hold else None
+            for spl in (1, 4):
+                velocity_script(pkg, c, cfg, 83 + B, f64=True, spl=spl, rounds=(13, 31, 17, 40, 21), position_at=3, force_at=2, names=names, velocity=joys, topic=True)
+            assert want in names, f"meant for {want}, ran {sorted(set(names))}"
+    finally:
+        undo()
+
+
+def sc_fp64_rollout(pkg, c):
+    rng = np.random.default_rng(96)
+    model = pkg.eight_cable_model()
+    B, S, H = 70, 6, 24
+    eng = pkg.Engine(pkg.Config(model=model, batch=B, stages=3, precision=64), 0)
+    eng.set_platform_state(pose7=poses(model, B, rng))
+    eng.update(25)
+    eng.set_velocity_command(rng.uniform(-0.03, 0.03, (B, 8)).astype(np.float32))
+    eng.update(15)
+    cmds = (rng.uniform(-0.03, 0.03, (B, H, 1, 8)) + rng.normal(0.0, 0.01, (B, H, S, 8))).astype(np.float32)
+    ref = eng.raw_state_f64()[0][:, :3].astype(np.float32) + np.float32([0.0, 0.0, 0.005])
+    c.add(eng.rollout_velocity(cmds, ref))
+    assert eng.kernel_name == "cdpr_step_kernel_f64<8>", eng.kernel_name  # (the handle's one-wave kernel, rings in memory)
+    c.snap(eng, True)
+    eng.close()
+
+
 def sc_scheduled(pkg, c, B=4096):
     rng = np.random.default_rng(91)
     for cables, stages in ((4, 0), (8, 3)):
@@ -286,6 +341,31 @@ SCENARIOS = {
     "fp64_one_wave": lambda pkg, c: sc_fp64(pkg, c, 0),
     "fp64_role_split": lambda pkg, c: sc_fp64(pkg, c, 1),
     "fp64_role_split_lean": lambda pkg, c: sc_fp64(pkg, c, 2),
+    # every family the fp64 step stages serve (cdpr_step_stages_f64.hpp), by kernel_name
+    "fp64_one_wave_rings_and_rows_in_lds": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_step_kernel_f64<8, RING_LDS, JCACHE>", f64=dict(SPLIT=0, RING_LDS=1, JCACHE=1)),
+    "fp64_one_wave_rings_in_lds": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_step_kernel_f64<8, RING_LDS>", f64=dict(SPLIT=0, RING_LDS=1, JCACHE=0)),
+    "fp64_one_wave_rings_in_memory": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_step_kernel_f64<8>", f64=dict(SPLIT=0, RING_LDS=0, JCACHE=0)),
+    "fp64_split_6": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_split_kernel_f64<6>", cables=6, f64=dict(SPLIT=1)),
+    "fp64_split_8": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_split_kernel_f64<8>", f64=dict(SPLIT=1)),
+    "fp64_split_lean_6": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_split_kernel_f64<6, LEAN>", cables=6, f64=dict(SPLIT=2)),
+    "fp64_split_lean_8": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_split_kernel_f64<8, LEAN>", f64=dict(SPLIT=2)),
+    "fp64_per_robot_rings_in_lds": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_step_kernel_f64<8, PR, RING_LDS>", perRobotCommands=True, f64=dict(RING_LDS=1)),
+    "fp64_per_robot_rings_in_memory": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_step_kernel_f64<8, PR>", perRobotCommands=True, f64=dict(RING_LDS=0)),
+    "fp64_hold_one_wave": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_step_kernel_f64<8, HOLD = 1>", hold=1, f64=dict(SPLIT=0)),
+    "fp64_hold_split": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_split_kernel_f64<8, HOLD = 1>", hold=1, f64=dict(SPLIT=1)),
+    "fp64_hold_split_lean": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_split_kernel_f64<8, LEAN, HOLD = 1>", hold=1, f64=dict(SPLIT=2)),
+    "fp64_hold_cascade": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_step_kernel_f64<8, HOLD = 2>", hold=2, f64=dict(SPLIT=0)),
+    "fp64_hold_cascade_split": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_split_kernel_f64<8, HOLD = 2>", hold=2, f64=dict(SPLIT=1)),
+    "fp64_hold_no_clamp": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_step_kernel_f64<8, HOLD = 2>", hold=3, f64=dict(SPLIT=0)),
+    "fp64_per_robot_hold": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_step_kernel_f64<8, PR, HOLD = 1>", hold=1, perRobotCommands=True),
+    "fp64_per_robot_hold_cascade": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_step_kernel_f64<8, PR, HOLD = 2>", hold=2, perRobotCommands=True),
+    "fp64_per_robot_hold_no_clamp": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_step_kernel_f64<8, PR, HOLD = 2>", hold=3, perRobotCommands=True),
+    "fp64_joint_stop_lumped_legs": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_step_kernel_f64<8, TSTOP>", lumped=True),
+    "fp64_joint_stop_per_robot": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_step_kernel_f64<8, PR, TSTOP>", lumped=True, perRobotCommands=True),
+    "fp64_long_window": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_step_kernel_f64<8, W = 31>", window=16),
+    "fp64_hold_long_window": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_step_kernel_f64<8, HOLD = 2, HW = 32>", hold=1, window=16),
+    "fp64_twelve_cables": lambda pkg, c: sc_f64_family(pkg, c, "cdpr_step_kernel_f64<12>", cables=12, stages=0),
+    "fp64_rollout": sc_fp64_rollout,
     "scheduled": sc_scheduled,
     "rollout": sc_rollout,
 }
