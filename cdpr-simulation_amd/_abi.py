@@ -146,3 +146,22 @@ class EnvSpec(C.Structure):
             rule = DoneRuleStruct()
             rule.struct_size = C.sizeof(DoneRuleStruct)
         self.done = rule
+
+
+RESAMPLE_STATUS = 5  # cdpr_resample_*_device's d_status: [robots copied, destinations skipped, groups resampled, groups degenerate, bad weights]
+
+
+class ResampleSpec(C.Structure):
+    """cdpr_resample_spec_t: what Engine.resample[_map]_device computes.  group_size: robots per group, consecutive (0 = the whole batch);
+    ess_gate: a group is resampled iff its effective sample size is below ess_gate * group_size (2 = always, 0 = never).  struct_size
+    is filled in."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("group_size", C.c_uint32),
+        ("ess_gate", C.c_float),
+        ("flags", C.c_uint32),
+    ]
+
+    def __init__(self, group_size=0, ess_gate=2.0, flags=0):
+        super().__init__(C.sizeof(ResampleSpec), int(group_size), float(ess_gate), int(flags))

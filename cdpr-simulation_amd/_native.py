@@ -18,7 +18,7 @@ EXPORTS = [
     "cdpr_create", "cdpr_destroy", "cdpr_reset", "cdpr_last_error", "cdpr_set_platform_state", "cdpr_reset_robots", "cdpr_reset_robots_device",
     "cdpr_done_rule_size", "cdpr_evaluate_done_device", "cdpr_evaluate_done", "cdpr_reset_done_device", "cdpr_get_episode_start",
     "cdpr_env_spec_size", "cdpr_observation_width", "cdpr_observe_device", "cdpr_env_evaluate_device",
-    "cdpr_copy_robots", "cdpr_copy_robots_device",
+    "cdpr_copy_robots", "cdpr_copy_robots_device", "cdpr_resample_spec_size", "cdpr_resample_map_device", "cdpr_resample_device",
     "cdpr_set_velocity_command", "cdpr_set_position_command", "cdpr_set_velocity_command_device",
     "cdpr_set_position_command_device", "cdpr_bind_velocity_command_device", "cdpr_bind_position_command_device",
     "cdpr_set_velocity_command_masked", "cdpr_set_position_command_masked", "cdpr_set_force_command", "cdpr_set_force_command_device",
@@ -83,6 +83,11 @@ def lib():
     if hasattr(L, "cdpr_copy_robots"):
         L.cdpr_copy_robots.argtypes = [H, ip]
         L.cdpr_copy_robots_device.argtypes = [H, C.c_void_p, C.c_void_p]
+    # ... and the resampler that computes the fork's map on the device
+    if hasattr(L, "cdpr_resample_spec_size"):
+        L.cdpr_resample_spec_size.restype = C.c_size_t
+        for name in ("cdpr_resample_map_device", "cdpr_resample_device"):
+            getattr(L, name).argtypes = [H, C.POINTER(_abi.ResampleSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in ("cdpr_set_velocity_command", "cdpr_set_position_command", "cdpr_set_force_command"):
         getattr(L, name).argtypes = [H, fp, C.c_size_t]
     for name in ("cdpr_set_velocity_command_device", "cdpr_set_position_command_device", "cdpr_bind_velocity_command_device",
@@ -137,5 +142,7 @@ def lib():
         raise ImportError("cdpr_done_rule_t layout mismatch between include/cdpr.h and _abi.py")
     if hasattr(L, "cdpr_env_spec_size") and L.cdpr_env_spec_size() != C.sizeof(_abi.EnvSpec):
         raise ImportError("cdpr_env_spec_t layout mismatch between include/cdpr.h and _abi.py")
+    if hasattr(L, "cdpr_resample_spec_size") and L.cdpr_resample_spec_size() != C.sizeof(_abi.ResampleSpec):
+        raise ImportError("cdpr_resample_spec_t layout mismatch between include/cdpr.h and _abi.py")
     _lib = L
     return L

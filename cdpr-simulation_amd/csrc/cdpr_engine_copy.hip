@@ -21,10 +21,12 @@ static __global__ __launch_bounds__(256) void cdpr_copy_f64_kernel(const CopyWho
 
 namespace cdpr_host {
 
-// Queue the copy behind every update queued so far.  d_source int32[B], d_status uint32[2] or null (zeroed on the stream first):
-// device buffers.  The world step, the publish clock, the status word and every pending command stay as they are.
-static int launch_copy(cdpr_engine* h, const int32_t* d_source, uint32_t* d_status) {
-  if (int rc = zero_counts(h, d_status, 2)) return rc;
+// Queue the copy behind every update queued so far.  d_source int32[B], d_status uint32[2] or null (zeroed on the stream first, unless
+// the caller has done that: `zeroed`): device buffers.  The world step, the publish clock, the status word and every pending command
+// stay as they are.  (Also the second launch of cdpr_resample_device, cdpr_engine_resample.hip.)
+int launch_copy(cdpr_engine* h, const int32_t* d_source, uint32_t* d_status, bool zeroed) {
+  if (!zeroed)
+    if (int rc = zero_counts(h, d_status, 2)) return rc;
   return launch_per_robot(h, CopyWho{d_source, d_status}, cdpr_copy_fast_kernel, cdpr_copy_gen_kernel, cdpr_copy_f64_kernel, true);
 }
 

@@ -7,7 +7,7 @@
 // cdpr_engine_launch.hip (what turns "advance n world steps" into launches: the latch, the chain and its clock, the fp32 and
 // general paths, schedules), cdpr_engine_f64.hip (precision = 64: set-up, its path of the chain), cdpr_engine_rollout.hip (cdpr_rollout_velocity*), cdpr_engine_solvers.hip (cdpr_solve_ik / fk / td), cdpr_engine_reset.hip
 // (cdpr_reset_robots*), cdpr_engine_copy.hip (cdpr_copy_robots*), cdpr_engine_done.hip (cdpr_evaluate_done*, cdpr_reset_done_device, cdpr_get_episode_start), cdpr_engine_env.hip (cdpr_observe_device,
-// cdpr_env_evaluate_device, cdpr_observation_width).  Not installed, not part of the C-ABI (include/cdpr.h is).
+// cdpr_env_evaluate_device, cdpr_observation_width), cdpr_engine_resample.hip (cdpr_resample_map_device, cdpr_resample_device).  Not installed, not part of the C-ABI (include/cdpr.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -294,7 +294,8 @@ struct cdpr_engine {
   // scratch on the handle's stream ([uint8 mask[B], padded to 16 B | float pose[B][7] | float twist[B][6]], sized once: B is fixed)
   DevBuf<char> d_reset_args;
   StagePair reset_stage;
-  // cdpr_copy_robots (host form): the caller's source map, staged the same way (int32[B], sized once)
+  // cdpr_copy_robots (host form): the caller's source map, staged the same way (int32[B], sized once); also the map of
+  // cdpr_resample_device where the caller gives none
   DevBuf<int32_t> d_copy_map;
   StagePair copy_stage;
   // episode clock: uint32[stride], the world step (low word) of every robot's last model reset; zero after create / cdpr_reset and
@@ -441,6 +442,8 @@ int scheduled_update(cdpr_engine* h, uint32_t kind, int nsteps, int refresh_step
                      void* d_record, size_t record_bytes);
 // cdpr_engine_reset.hip
 int launch_reset(cdpr_engine* h, const uint8_t* d_mask, const float* d_pose, const float* d_twist);
+// cdpr_engine_copy.hip
+int launch_copy(cdpr_engine* h, const int32_t* d_source, uint32_t* d_status, bool zeroed = false);
 // cdpr_engine_done.hip
 int done_checks(cdpr_engine* h, const cdpr_done_rule_t* rule, const char* what);  // what every call refuses of a done rule
 int ensure_done_scratch(cdpr_engine* h);                                          // h->d_done: [mask | reason | counts]

@@ -131,6 +131,46 @@ class Engine:
         [robots copied, destinations skipped]."""
         self._check(lib().cdpr_copy_robots_device(self._h, C.c_void_p(d_source) if d_source else None, C.c_void_p(d_status) if d_status else None))
 
+    # -- resampling: weights to the fork's map, on the device
+    def resample_map_device(self, spec: _abi.ResampleSpec, d_weights: int, d_source: int, d_words: int = 0, d_ess: int = 0, d_status: int = 0) -> None:
+        """Systematic resampling per group of spec.group_size consecutive robots (cdpr_resample_map_device): device float[B] weights to the
+        device int32[B] map copy_robots_device takes; nothing is copied or synchronised.  d_words: device uint32[G], one random word per
+        group (0 = 2^31 for every group); d_ess: device float[G], the groups' effective sample sizes; d_status: device
+        uint32[_abi.RESAMPLE_STATUS]; 0 = not wanted.  Any handle: no robot state is read."""
+        vp = lambda x: C.c_void_p(x) if x else None  # noqa: E731
+        self._check(lib().cdpr_resample_map_device(self._h, C.byref(spec), vp(d_weights), vp(d_words), vp(d_source), vp(d_ess), vp(d_status)))
+
+    def resample_device(self, spec: _abi.ResampleSpec, d_weights: int, d_source: int = 0, d_words: int = 0, d_ess: int = 0, d_status: int = 0) -> None:
+        """The map and the copy on it, back to back on the engine's stream (cdpr_resample_device).  d_source 0: a buffer of the engine's
+        own.  Needs Config.perRobotCommands."""
+        vp = lambda x: C.c_void_p(x) if x else None  # noqa: E731
+        self._check(lib().cdpr_resample_device(self._h, C.byref(spec), vp(d_weights), vp(d_words), vp(d_source), vp(d_ess), vp(d_status)))
+
+    def resample(self, weights, words=None, group_size: int = 0, ess_gate: float = 2.0, copy: bool = True):
+        """(source int32[B], ess float32[G], status uint32[_abi.RESAMPLE_STATUS]) on the host: the weights (and words, uint32[G], or None)
+        go up, resample_device (copy=True) or resample_map_device (copy=False) runs into scratch buffers, the results come down."""
+        P = int(group_size) or self.B
+        if P < 1 or self.B % P:
+            raise ValueError("resample: the batch is not a whole number of groups")
+        G = self.B // P
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(self.B)
+        u = None if words is None else np.ascontiguousarray(words, dtype=np.uint32).reshape(G)
+        spec = _abi.ResampleSpec(group_size, ess_gate)
+
+        def body(ptrs):
+            d_w, d_u, d_source, d_ess, d_status = ptrs
+            self.device_upload_into(d_w, w)
+            if u is not None:
+                self.device_upload_into(d_u, u)
+            if copy:
+                self.resample_device(spec, d_w, d_source, d_u, d_ess, d_status)
+            else:
+                self.resample_map_device(spec, d_w, d_source, d_u, d_ess, d_status)
+            return (self.device_download(d_source, self.B, np.int32), self.device_download(d_ess, G, np.float32),
+                    self.device_download(d_status, _abi.RESAMPLE_STATUS, np.uint32))
+
+        return self._with_scratch([4 * self.B, None if u is None else 4 * G, 4 * self.B, 4 * G, 4 * _abi.RESAMPLE_STATUS], body)
+
     # -- done rules: who should be put back, decided on the device
     @staticmethod
     def _rule(rule):

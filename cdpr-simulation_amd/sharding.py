@@ -95,6 +95,24 @@ class ShardedEngine:
         for e, part in zip(self.engines, parts):
             e.copy_robots(part)
 
+    def resample(self, weights, words=None, group_size=0, ess_gate=2.0, copy=True):
+        """Engine.resample over the shards: weights split by shard_range, words by the groups of each shard; the map comes back re-based
+        to batch indices, ess concatenated in shard order, status summed.  There is no cross-GPU data path: a group that straddles two
+        shards raises ValueError before any shard is touched."""
+        import numpy as np
+
+        P = int(group_size) or self.B
+        if P < 1 or self.B % P:
+            raise ValueError("resample: the batch is not a whole number of groups")
+        for lo, hi in self.spans:
+            if lo % P or hi % P:
+                raise ValueError(f"resample: a group of {P} robots straddles the shard [{lo}, {hi}); there is no cross-GPU copy")
+        w = np.asarray(weights, dtype=np.float32).reshape(self.B)
+        u = None if words is None else np.asarray(words, dtype=np.uint32).reshape(self.B // P)
+        parts = [e.resample(w[lo:hi], None if u is None else u[lo // P:hi // P], P, ess_gate, copy) for e, (lo, hi) in zip(self.engines, self.spans)]
+        source = np.concatenate([np.where(p[0] >= 0, p[0] + lo, -1).astype(np.int32) for p, (lo, _) in zip(parts, self.spans)])
+        return source, np.concatenate([p[1] for p in parts]), np.sum([p[2] for p in parts], axis=0, dtype=np.uint32)
+
     def evaluate_done(self, rule):
         """Engine.evaluate_done over the shards: masks and reasons concatenated in shard_range order, counts summed."""
         import numpy as np

@@ -38,7 +38,8 @@ extern "C" {
 
 /* The environment view (cdpr_env_spec_t, cdpr_env_spec_size, cdpr_observation_width, cdpr_observe_device, cdpr_env_evaluate_device) came
  * after 8 as new exports only: no struct or call that existed changed, so the number stays 8.  A caller discovers the feature by those
- * symbols and checks its cdpr_env_spec_t against cdpr_env_spec_size(). */
+ * symbols and checks its cdpr_env_spec_t against cdpr_env_spec_size().  So did the fork (cdpr_copy_robots*) and the resampler
+ * (cdpr_resample_spec_t, cdpr_resample_spec_size, cdpr_resample_map_device, cdpr_resample_device). */
 #define CDPR_ABI_VERSION 8u   /* 8 = 7 + cdpr_done_rule_t, cdpr_evaluate_done, cdpr_evaluate_done_device, cdpr_reset_done_device, cdpr_get_episode_start, cdpr_done_rule_size; 7 = 6 + cdpr_reset_robots, cdpr_reset_robots_device; 6 = 5 + cdpr_plan_kernel, cdpr_kernel_name, CDPR_MAX_CABLES 8 -> 12 (cdpr_config_t's anchor arrays grow); 5 = 4 + cdpr_update_scheduled_kind, cdpr_device_pci_bus_id, cdpr_decode_observables_f64 */
 #define CDPR_MAX_CABLES 12u         /* PLG.h:20 fixes 4 (kCableCount); cube.yaml:21-29 is a free-length `points` list: the engine takes 1..12
                                       (9..12: uniform-mode fp32 handles on the lane-per-robot kernels, FK and TD included; see cdpr_create) */
@@ -257,6 +258,55 @@ int cdpr_reset_robots_device(cdpr_handle_t h, const uint8_t *d_robot_mask, const
  *   then copied before the call returns and queued; the stream is not waited for. */
 int cdpr_copy_robots_device(cdpr_handle_t h, const int32_t *d_source, uint32_t *d_status);
 int cdpr_copy_robots(cdpr_handle_t h, const int32_t *source);
+
+/* Resampling on the device: weights to the map of the fork, no host wait.  Systematic (low-variance) resampling per group of P
+ * consecutive robots (G = B / P groups; a particle filter per robot team, MPPI / CEM populations, restart-from-the-best): float
+ * weights that live on the GPU - a reward buffer, a policy's output - become the int32 source map cdpr_copy_robots_device takes, and
+ * the fused form queues the copy right behind.  New exports after ABI 8, no struct changes.
+ *
+ * The definition is in integers, so that the result does not depend on the order a parallel scan adds in and a sequential restatement
+ * (tests/resample_oracle.py) reproduces map, ess and counts to the bit.  Group g has the weights w[gP .. gP + P) and one random word
+ * u_g (uint32):
+ *   usable   a weight that is finite and > 0; every other weight counts as 0, and NaN, +-inf and negative ones are counted as BAD.
+ *            m = the largest usable weight.  None: the group is DEGENERATE - map entries -1, ess 0, counted.
+ *   q_i      (uint64) floor((double)w_i / (double)m * 2^30) for a usable weight, else 0: one IEEE double division, then the power of
+ *            two.  The maximum becomes exactly 2^30.  Q = sum q_i, C_i its inclusive prefix sum, C_{-1} = 0 (P <= 65 536: Q <= 2^46,
+ *            P * C_i <= 2^62).
+ *   ess      q_i^2 = hi_i * 2^30 + lo_i, Shi = sum hi_i, Slo = sum lo_i (exact in uint64 and as doubles);
+ *            ess = ((double)Q * (double)Q) / ((double)Shi * 2^30 + (double)Slo), exactly those four double operations, never
+ *            contracted.  d_ess[g] = (float)ess.  The group is RESAMPLED iff ess < (double)ess_gate * (double)P; ess <= P, so a gate
+ *            of 2 means "always" and 0 "never".  A group that is not resampled has map entries -1.
+ *   counts   o = (Q * u_g) >> 32 (the full 96-bit product), positions j * Q + o for j = 0 .. P - 1 against the bounds P * C_i:
+ *            c_i = #{ j : P * C_{i-1} <= j * Q + o < P * C_i } = N(P * C_i) - N(P * C_{i-1}), N(x) = 0 for x <= o, else
+ *            min(P, (x - o + Q - 1) / Q).  sum c_i = P and |c_i - P * q_i / Q| < 1.
+ *   the map  survivors (c_i > 0) keep their index, as the copy's rule demands.  extras_i = max(c_i - 1, 0), dead_i = (c_i == 0),
+ *            sum extras = sum dead.  The k-th dead robot in index order takes the k-th extra slot in index order: its source is the
+ *            smallest i whose inclusive scan of extras exceeds k, its entry gP + i.  Every other entry is -1: all of d_source[0, B) is
+ *            written, the buffer needs no clearing.  Every source is a survivor, so the copy skips nothing.
+ * spec: struct_size = sizeof(cdpr_resample_spec_t) (cdpr_resample_spec_size()), group_size P (0: the whole batch), ess_gate, flags 0.
+ * d_weights float[B]; d_words uint32[G] or NULL (u_g = 2^31 for every group); d_source int32[B]; d_ess float[G] or NULL; d_status
+ * uint32[5] or NULL, zeroed on the stream in front of the kernels: [0] robots copied (the map call: its own count of destinations, the
+ * same number), [1] destinations the copy skipped (the map call: 0; the fused call: 0 by construction), [2] groups resampled, [3] groups
+ * degenerate, [4] bad weights.  All device buffers; they must stay valid until the stream has passed the call.
+ * cdpr_resample_map_device: the map alone.  Any handle - uniform or per-robot, every kernel family, both precisions: it reads no robot
+ *   state, the handle supplies B and the stream.  Stream-ordered behind everything queued; copies nothing, waits for nothing.
+ * cdpr_resample_device: the map, then cdpr_copy_robots_device on it, back to back.  d_source NULL: a buffer of the handle's own.
+ *   Per-robot handles only (per_robot_commands = 1), else CDPR_ERR_UNSUPPORTED.
+ * Refusals (a refused call queues nothing): CDPR_ERR_INVALID for a NULL handle, spec or weights, a NULL map (the map call),
+ * struct_size != sizeof(cdpr_resample_spec_t), flags != 0, B not a multiple of P, an ess_gate that is NaN or negative;
+ * CDPR_ERR_UNSUPPORTED for P > 65 536.  No step launch: cdpr_kernel_name and cdpr_plan_kernel do not see it. */
+typedef struct cdpr_resample_spec {
+  uint32_t struct_size;  /* sizeof(cdpr_resample_spec_t)                                  */
+  uint32_t group_size;   /* P: robots per group, consecutive; 0 = the whole batch         */
+  float ess_gate;        /* resample a group iff ess < ess_gate * P                       */
+  uint32_t flags;        /* 0                                                             */
+} cdpr_resample_spec_t;
+
+size_t cdpr_resample_spec_size(void);                /* sizeof(cdpr_resample_spec_t) as compiled */
+int cdpr_resample_map_device(cdpr_handle_t h, const cdpr_resample_spec_t *spec, const float *d_weights, const uint32_t *d_words,
+                             int32_t *d_source, float *d_ess, uint32_t *d_status);
+int cdpr_resample_device(cdpr_handle_t h, const cdpr_resample_spec_t *spec, const float *d_weights, const uint32_t *d_words,
+                         int32_t *d_source, float *d_ess, uint32_t *d_status);
 
 /* Done rules: which robots a loop should put back, decided on the device.  cdpr_reset_robots_device takes a "done" mask that lives
  * on the GPU; these calls compute it there, from the state the handle already holds, so that a Monte-Carlo sweep, an RL-style
