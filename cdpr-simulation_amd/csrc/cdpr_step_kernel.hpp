@@ -996,6 +996,9 @@ __global__ __launch_bounds__(64, LOWREG ? 2 : CDPR_LPR_WAVES) void cdpr_step_ker
         calls = 0;
       }
       actual_is_vel = true;
+      // ... and one in Force mode: the Joy takes it into Velocity mode, the trajectory's commands are velocity targets (the
+      // lane's copy of the mode says so; the handle's meta byte stays)
+      meta = (meta & ~kMetaModeMask) | kMetaVelocity;
     } else if (a.flags & kFlagRolloutResetPid) {
 #pragma unroll
       for (int k = 0; k < NP; ++k) {

@@ -1,0 +1,149 @@
+"""What tests/test_launch_form_inputs.py (CPU) and tests/test_gpu_launch_forms_after_robot_ops.py (GPU) share: the launch forms a
+per-robot handle can be stepped in, the script that puts a reset or a copy between segments stepped in ONE form, the rollout inputs,
+and the "half recipe" - a reset that forgets the controller - which the CPU module uses to show that the script can tell.
+
+A Player is one simulator (an Engine, or an OracleSim as form "oracle") that runs every segment of k world steps in its form:
+
+  one      update(1) x k, the observables read after every step
+  fused10  update(k, 10)
+  fused3   update(k, 3)             (30 steps: ten launches of three, the captured graph of the register-resident kinds)
+  rec      update_record(k, 10)     (every step's image kept)
+  long     update(k, min(k, 64))    (one launch per segment)
+  sched    as long; a Joy segment goes in as a one-batch schedule update_scheduled(k, k, rows, kind, masks), the engine's own
+           set_*_command is not called for it
+  oracle   update(1) x k, platform_state + joint_states kept after every step
+
+B = 130: two full wavefronts and a ragged one, stride 192.
+"""
+import numpy as np
+
+import test_reset_robots_inputs as ri
+from per_robot_kinds import ALL
+
+B = ri.B
+KINDS = ALL + ["general_one_wave"]
+GENERAL = ["general_n8", "general_lean_hot", "general_long", "general_one_wave"]  # per-wave tier decisions: exact only lane for lane
+FORMS = ("one", "fused10", "fused3", "rec", "long", "sched")
+NAMES = ("pose", "twist", "q", "qd", "eff")
+SAMPLES = 3  # trajectories per robot in a rollout: a wave mixes those of reset and of untouched robots
+SETTER = {"velocity": "set_velocity_command", "position": "set_position_command", "force": "set_force_command"}
+# the after-script: (checkpoint, the masked Joy in front of the segment or None, its key in after_inputs, steps)
+SEGMENTS = (
+    ("13 steps after the op", None, None, 13),
+    ("30 steps after the masked velocity Joy", "velocity", "v", 30),
+    ("25 steps after the masked position Joy", "position", "p", 25),
+    ("12 steps after the masked force Joy", "force", "f", 12),
+)
+
+
+def readout(sim, cfg):
+    """pose, twist, q, qd, effort of the last published step (an oracle: platform_state + joint_states)"""
+    if cfg.precision == 64 and hasattr(sim, "observables_f64"):
+        q, qd, e, p, t = sim.observables_f64()
+        return p, t, q, qd, e
+    return tuple(sim.platform_state()) + tuple(sim.joint_states())
+
+
+def steps_of_the_last_launch(form, k):
+    """world steps of the last launch of a segment of k steps (what kernel_name then speaks of)"""
+    spl = {"one": 1, "fused10": 10, "fused3": 3, "rec": 10}.get(form, min(k, 64))
+    return k % spl or spl
+
+
+class Player:
+    def __init__(self, sim, form, cfg):
+        assert form in FORMS + ("oracle",)
+        self.sim, self.form, self.cfg = sim, form, cfg
+        self.steps = []     # forms one, rec, oracle: readout after every world step
+        self.record = None  # form rec: what the last update_record returned
+        self.launches = []  # engines: (form's steps in the last launch of the segment, kernel_name after it)
+
+    def run(self, k):
+        s, form = self.sim, self.form
+        if form in ("one", "oracle"):
+            for _ in range(k):
+                s.update(1)
+                self.steps.append(readout(s, self.cfg))
+        elif form == "rec":
+            self.record = r = s.update_record(k, 10)
+            self.steps += [(r["pose"][j], r["twist"][j], r["position"][j], r["velocity"][j], r["effort"][j]) for j in range(k)]
+        else:
+            s.update(k, {"fused10": 10, "fused3": 3}.get(form, min(k, 64)))
+        self._log(k)
+
+    def joy(self, kind, rows, mask, k):
+        """the masked Joy `kind`, then k steps"""
+        if self.form != "sched":
+            assert getattr(self.sim, SETTER[kind])(rows, mask=mask) == 0
+            return self.run(k)
+        s = self.sim
+        d_rows = s.device_upload(np.ascontiguousarray(rows, dtype=np.float32).reshape(1, B, -1))
+        d_mask = s.device_upload(np.ascontiguousarray(mask, dtype=np.uint8).reshape(1, B))
+        s.update_scheduled(k, k, d_rows, kind=kind, d_robot_masks=d_mask)
+        s.synchronize()
+        s.device_free(d_rows), s.device_free(d_mask)
+        self._log(k)
+
+    def _log(self, k):
+        if self.form != "oracle":
+            self.launches.append((steps_of_the_last_launch(self.form, k), self.sim.kernel_name))
+
+    def close(self):
+        self.sim.close()
+
+
+def after_inputs(model, seed, batch=B):
+    """ri.after_inputs and the force Joy of the last segment: around what holds the platform, for every fifth robot"""
+    a = ri.after_inputs(model, seed, batch)
+    a["f"] = ri.forces(model.n_cables, np.random.default_rng(9), batch)
+    a["f_mask"] = (np.arange(batch) % 5 == 0).astype(np.uint8)
+    return a
+
+
+def play_history(players, h, steps=ri.HISTORY):
+    """ri.play_history, every player in its own form"""
+    for p in players:
+        assert p.sim.set_position_command(h["p"], mask=(h["group"] == 0).astype(np.uint8)) == 0
+        assert p.sim.set_velocity_command(h["v"], mask=(h["group"] == 1).astype(np.uint8)) == 0
+        assert p.sim.set_force_command(h["f"], mask=(h["group"] == 2).astype(np.uint8)) == 0
+        p.run(steps)
+
+
+def play_after(players, a, check):
+    """The script behind the op; check(label, steps of the segment) after each segment."""
+    for label, kind, key, k in SEGMENTS:
+        for p in players:
+            p.run(k) if kind is None else p.joy(kind, a[key], a[key + "_mask"], k)
+        check(label, k)
+
+
+def half_reset(ora, mask, pose7):
+    """The half recipe: pose and twist rows of the mask through set_platform_state only; the Pids keep their past (mode, target,
+    integral, derivative window, call count).  What a launch form that ignored the reset's call count would resemble."""
+    m = np.asarray(mask).astype(bool)
+    p, t = ora.raw_state()
+    p[m] = np.asarray(pose7, dtype=np.float32).astype(np.float64)[m]
+    t[m] = 0.0
+    ora.set_platform_state(pose7=p, twist6=t)
+
+
+def window_of(cfg):
+    return max(cfg.velocityController.dBufferLength, cfg.positionController.dBufferLength)
+
+
+def rollout_inputs(cfg, pose, seed):
+    """cmds [B, H, SAMPLES, n] with H = nbuf + 3 (the window of a robot whose Pid starts at the rollout's first Joy fills inside the
+    rollout), ref [B, 3] = `pose` plus (0, 0, 0.01)"""
+    rng = np.random.default_rng(seed)
+    H, n = window_of(cfg) + 3, cfg.n_cables
+    cmds = (rng.uniform(-0.03, 0.03, (B, H, 1, n)) + rng.normal(0.0, 0.01, (B, H, SAMPLES, n))).astype(np.float32)
+    return dict(cmds=cmds, ref=(pose[:, :3].astype(np.float32) + np.float32([0.0, 0.0, 0.01])).astype(np.float32))
+
+
+def rollout_tolerance(cfg, general, oc):
+    """the suite's own: test_gpu_fp64.test_fp64_rollout_on_per_robot_handles, test_gpu_general_matrix,
+    test_gpu_parity.test_per_robot_rollout_record_and_fused_updates_against_the_oracle"""
+    scale = float(np.abs(oc).max())
+    if cfg.precision == 64:
+        return 3e-7 * scale
+    return (1e-9 if general else 1e-6) + 2e-4 * scale

@@ -1,6 +1,7 @@
 """The nine kinds of per-robot handle the tests of the calls over chosen robots run on (reset_robots, copy_robots, the done rules, the
 environment view): three per record layout - register-resident per-robot records, the general path's record buffer, the
 precision = 64 rows - with the Config that makes each, the environment switches it needs and what kernel_name must then hold.
+ALL names those nine; HANDLES holds one more, general_one_wave, for the launch-form tests (tests/launch_forms.py).
 
 B = 130: two full wavefronts and a ragged one, stride 192.
 """
@@ -22,8 +23,11 @@ HANDLES = {
     "fp64_n8": (8, dict(stages=3, precision=64), {}, ("cdpr_step_kernel_f64<8, PR",)),
     "fp64_hold_n8": (8, dict(stages=3, precision=64, velocityEpsilon=EPS), {}, ("cdpr_step_kernel_f64<8, PR, HOLD = 1",)),
     "fp64_hold_long": (8, dict(stages=3, precision=64, velocityEpsilon=EPS), {}, ("cdpr_step_kernel_f64<8, PR, HOLD = 2, HW = 32",)),
+    # the one-wave general kernel on 11-sample windows: the only such handle whose fused launches are several steps per launch
+    # (tests/launch_forms.py; not one of ALL)
+    "general_one_wave": (8, dict(stages=3, velocityEpsilon=EPS), {"CDPR_GEN_SPLIT": "0", "CDPR_GEN_LEAN": "0"}, ("cdpr_gen_step_kernel<8,",)),
 }
-ALL = list(HANDLES)
+ALL = ["fast_n8", "fast_n4", "fast_n7", "general_n8", "general_lean_hot", "general_long", "fp64_n8", "fp64_hold_n8", "fp64_hold_long"]
 LAYOUTS = ["fast_n8", "general_lean_hot", "fp64_hold_n8"]  # one handle per record layout
 
 
