@@ -3,7 +3,7 @@ pure-Python statement of what a valid map is, and the "twin from birth" inputs -
 of its source, so that an oracle started on them holds, at every step, what a copied engine must hold after the copy."""
 import numpy as np
 
-import test_reset_robots_inputs as ri
+import robot_histories as ri
 
 B = ri.B
 

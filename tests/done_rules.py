@@ -10,8 +10,8 @@ kernels' in the last bits, so every scenario keeps those metrics away from their
 import numpy as np
 from scipy.spatial.transform import Rotation
 
-import test_reset_robots_inputs as ri
-from test_gpu_parity import perturbed_poses
+import robot_histories as ri
+from parity import perturbed_poses
 
 B = ri.B
 NONFINITE, WORKSPACE, TILT, SPEED, RATE, FK_RESIDUAL, INFEASIBLE, TRAVEL, TIMEOUT = (1 << k for k in range(9))
@@ -170,7 +170,7 @@ def loop_inputs(model):
 
 def loop_margins(rule, pose, twist, tol):
     """The distance of every oracle robot's metric from its threshold in units of the parity tolerance of that quantity (`tol`: TOL
-    of tests/test_gpu_parity.py or TOL64 of tests/test_gpu_fp64.py): position components against the faces of the box at tol["pose"];
+    or TOL64 of tests/parity.py): position components against the faces of the box at tol["pose"];
     R33 at 4 tol["pose"] (|dR33/dq| <= 4 |q| on quaternions of length ~1, and the quaternion is compared at the pose tolerance); |v|
     against max_speed at sqrt(3) tol["twist"].  An engine within tolerance of the oracle takes the oracle's decisions where every
     entry is above 1; the tests ask for 100."""

@@ -17,14 +17,14 @@ B = 130: two full wavefronts and a ragged one, stride 192.
 """
 import numpy as np
 
-import test_reset_robots_inputs as ri
+import robot_histories as ri
+from parity import observed, rollout_cost_tol
 from per_robot_kinds import ALL
 
 B = ri.B
 KINDS = ALL + ["general_one_wave"]
 GENERAL = ["general_n8", "general_lean_hot", "general_long", "general_one_wave"]  # per-wave tier decisions: exact only lane for lane
 FORMS = ("one", "fused10", "fused3", "rec", "long", "sched")
-NAMES = ("pose", "twist", "q", "qd", "eff")
 SAMPLES = 3  # trajectories per robot in a rollout: a wave mixes those of reset and of untouched robots
 SETTER = {"velocity": "set_velocity_command", "position": "set_position_command", "force": "set_force_command"}
 # the after-script: (checkpoint, the masked Joy in front of the segment or None, its key in after_inputs, steps)
@@ -34,14 +34,6 @@ SEGMENTS = (
     ("25 steps after the masked position Joy", "position", "p", 25),
     ("12 steps after the masked force Joy", "force", "f", 12),
 )
-
-
-def readout(sim, cfg):
-    """pose, twist, q, qd, effort of the last published step (an oracle: platform_state + joint_states)"""
-    if cfg.precision == 64 and hasattr(sim, "observables_f64"):
-        q, qd, e, p, t = sim.observables_f64()
-        return p, t, q, qd, e
-    return tuple(sim.platform_state()) + tuple(sim.joint_states())
 
 
 def steps_of_the_last_launch(form, k):
@@ -63,7 +55,7 @@ class Player:
         if form in ("one", "oracle"):
             for _ in range(k):
                 s.update(1)
-                self.steps.append(readout(s, self.cfg))
+                self.steps.append(observed(s, self.cfg.precision == 64))
         elif form == "rec":
             self.record = r = s.update_record(k, 10)
             self.steps += [(r["pose"][j], r["twist"][j], r["position"][j], r["velocity"][j], r["effort"][j]) for j in range(k)]
@@ -143,7 +135,6 @@ def rollout_inputs(cfg, pose, seed):
 def rollout_tolerance(cfg, general, oc):
     """the suite's own: test_gpu_fp64.test_fp64_rollout_on_per_robot_handles, test_gpu_general_matrix,
     test_gpu_parity.test_per_robot_rollout_record_and_fused_updates_against_the_oracle"""
-    scale = float(np.abs(oc).max())
     if cfg.precision == 64:
-        return 3e-7 * scale
-    return (1e-9 if general else 1e-6) + 2e-4 * scale
+        return 3e-7 * float(np.abs(oc).max())
+    return rollout_cost_tol(oc, 1e-9 if general else 1e-6)

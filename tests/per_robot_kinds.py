@@ -5,9 +5,8 @@ ALL names those nine; HANDLES holds one more, general_one_wave, for the launch-f
 
 B = 130: two full wavefronts and a ragged one, stride 192.
 """
-import pytest
-
-import test_reset_robots_inputs as ri
+import parity
+import robot_histories as ri
 
 B = ri.B
 EPS = ri.EPS
@@ -31,15 +30,12 @@ ALL = ["fast_n8", "fast_n4", "fast_n7", "general_n8", "general_lean_hot", "gener
 LAYOUTS = ["fast_n8", "general_lean_hot", "fp64_hold_n8"]  # one handle per record layout
 
 
-@pytest.fixture(autouse=True)
-def clean_env(monkeypatch):
-    """(autouse in every module that imports it)"""
-    for k in ("CDPR_GEN_SPLIT", "CDPR_GEN_LEAN", "CDPR_GEN_HOT", "CDPR_MAPPING", "CDPR_NO_GRAPH"):
-        monkeypatch.delenv(k, raising=False)
+clean_env = parity.clean_env_fixture("CDPR_NO_GRAPH")  # (autouse in every module that imports it)
 
 
 def config_of(pkg, kind, monkeypatch, per_robot=True, more_stages=0):
     n, kw, env, _ = HANDLES[kind]
+    parity.clear_overrides(monkeypatch, ("CDPR_NO_GRAPH",))
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     kw = dict(kw, stages=kw["stages"] | more_stages)
@@ -47,7 +43,7 @@ def config_of(pkg, kind, monkeypatch, per_robot=True, more_stages=0):
     if kind.endswith("_long"):  # 32-sample derivative windows ...
         for p in (cfg.velocityController, cfg.positionController):
             p.dBufferLength, p.dDegree = 32, 2
-    if kind == "general_long":  # ... and a gentle loop through a biquad on the P and the D input of the velocity Pid (test_gpu_general_matrix.cascade_config)
+    if kind == "general_long":  # ... and a gentle loop through a biquad on the P and the D input of the velocity Pid (cascade_config of tests/test_gpu_general_matrix.py)
         for f in (cfg.velocityController.pFilter, cfg.velocityController.dFilter):
             f.cascade, f.relCutoff, f.quality = 1, 0.05, 0.5
         cfg.velocityController.pGain, cfg.velocityController.iGain, cfg.velocityController.dGain = 4.0, 40.0, 0.01
@@ -61,6 +57,4 @@ def named(eng, kind):
 
 def state_of(eng, cfg):
     """raw_state, joint_states and observables (the doubles of a precision = 64 handle)"""
-    if cfg.precision == 64:
-        return eng.raw_state_f64() + eng.observables_f64()
-    return eng.raw_state() + eng.joint_states() + eng.observables()
+    return parity.state_of(eng, cfg.precision == 64, joint_states=True)

@@ -14,7 +14,7 @@ which therefore ends up beyond the clamp); SetForce then clamps at the joint's e
   integral            iGain 400 / 1400, iLimit 0.5 / 1.0, cmdLimit and effort limit at the shipped 100 (tension bounds as shipped)
 
 The scripts (SCRIPTS) alternate runs and Joys; every command array is float32 and goes to every simulator unchanged.  Start poses:
-test_gpu_parity.perturbed_poses(model, 130, rng, 0.02, 0.05) rounded to float32.
+parity.perturbed_poses(model, 130, rng, 0.02, 0.05) rounded to float32.
 
 The hold ladder: JFC.cpp:72 runs the velocity Pid where abs(mVelocityTarget) > mVelocityEpsilon, in double, on a Joy axis that
 is a float32.  The ladder puts targets on, one float32 below and one float32 above float32(eps), and at eps = 0 on +-0, the
@@ -26,7 +26,7 @@ from dataclasses import replace
 import numpy as np
 
 import workspace_poses as wp
-from test_gpu_parity import perturbed_poses
+from parity import perturbed_poses
 
 B = 130
 SEED_OFFSET = 4000  # added to the cell's own seed (workspace_poses.CELLS)
@@ -186,10 +186,6 @@ def velocity_branch_float32(t, eps):
 # ---- the rollout case ----------------------------------------------------------------------------------------------------------
 ROLLOUT = dict(B=12, S=16, H=24, n=8, seed=9500, eps=0.004, warm=30)
 ROLLOUT_HANDLES = {"fast": dict(), "general": dict(velocityEpsilon=ROLLOUT["eps"]), "f64": dict(precision=64)}
-
-
-def rollout_cost_tolerance(cost):
-    return 1e-6 + 2e-4 * float(np.abs(cost).max())
 
 
 def rollout_ref(ora):

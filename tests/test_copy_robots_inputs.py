@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import copy_robots as cr
-import test_reset_robots_inputs as ri
+import robot_histories as ri
 
 B = ri.B
 

@@ -18,9 +18,8 @@ import numpy as np
 import pytest
 
 import done_rules as dr
-import test_reset_robots_inputs as ri
-from test_gpu_fp64 import TOL64
-from test_gpu_parity import TOL
+import robot_histories as ri
+from parity import TOL, TOL64
 
 B = dr.B
 

@@ -19,7 +19,7 @@ from scipy.spatial.transform import Rotation
 
 import done_rules as dr
 import env_view as ev
-import test_reset_robots_inputs as ri
+import robot_histories as ri
 
 B = dr.B
 

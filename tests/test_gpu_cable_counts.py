@@ -2,8 +2,8 @@
 
 Models are subsets of twelve_cable_model (as test_gpu_more_cables.py).  Robots with one to three cables are under-constrained and
 swing (twist up to 0.7 at n = 1); the oracle stays bounded over the 110-step script below, and a 3e-8 m perturbation of the spawn
-pose stays below 1e-7 in every observable there, so the fp32 tolerances of test_gpu_parity.py (TOL) and the fp64 ones of
-test_gpu_fp64.py (TOL64) hold unchanged at every count.  Measured on MI355X over this module (test_zz_report_measured_agreement
+pose stays below 1e-7 in every observable there, so the fp32 tolerances (TOL) and the fp64 ones (TOL64) of tests/parity.py
+hold unchanged at every count.  Measured on MI355X over this module (test_zz_report_measured_agreement
 prints them with -s), worst over n = 1 .. 12: fp32 pose 4.3e-7, twist 2.0e-5, q 4.8e-7, qd 2.3e-5, effort 3.9e-3, pid topic 4.1e-4,
 rollout cost 6.6e-5 relative; fp64 pose 1.0e-15, twist 5.3e-14, q 1.0e-15, qd 4.8e-14, effort 9.4e-12, rollout cost 5.3e-8 relative.
 
@@ -23,19 +23,14 @@ from dataclasses import replace
 import numpy as np
 import pytest
 
-from test_gpu_parity import TOL, perturbed_poses
+import parity
+from parity import TOL, perturbed_poses, state_of
+from parity import sliced_twelve as model_of
 
 pytestmark = pytest.mark.gpu
 
-TOL64 = {"pose": 1e-13, "twist": 5e-12, "q": 1e-13, "qd": 5e-12, "eff": 1e-9}  # = test_gpu_fp64.py
 FIRST, SCHEDULED, ROLLOUT, NOT_STEADY = 1, 2, 4, 8  # CDPR_PLAN_* (include/cdpr.h)
 WORST = {}
-NAMES = ("pose", "twist", "q", "qd", "eff")
-
-
-def model_of(pkg, n):
-    m = pkg.twelve_cable_model()
-    return m if n == 12 else replace(m, frame_anchors=m.frame_anchors[:n], platform_anchors=m.platform_anchors[:n])
 
 
 def note(n, name, err):
@@ -43,24 +38,9 @@ def note(n, name, err):
 
 
 def against_oracle(eng, ora, n, f64, where):
-    """The last published step of `eng` against the oracle: observables_f64 at TOL64, else the float getters at TOL."""
-    if f64:
-        gq, gqd, ge, gp, gt = eng.observables_f64()
-    else:
-        gq, gqd, ge = eng.joint_states()
-        gp, gt = eng.platform_state()
-    op, ot = ora.platform_state()
-    oq, oqd, oe = ora.joint_states()
-    tol = TOL64 if f64 else TOL
-    for name, g, o in zip(NAMES, (gp, gt, gq, gqd, ge), (op, ot, oq, oqd, oe)):
-        assert np.isfinite(g).all(), where
-        err = float(np.abs(g - o).max())
+    """parity.against_the_oracle, the worst errors noted under the cable count"""
+    for name, (err, _, _) in parity.against_the_oracle(eng, ora, f64, where).items():
         note(n, name + ("64" if f64 else ""), err)
-        assert err <= tol[name], f"{where}: {name} differs from the oracle by {err:.3e} (tolerance {tol[name]:.1e})"
-
-
-def state_of(eng, f64):
-    return (eng.raw_state_f64() + eng.observables_f64()) if f64 else (eng.raw_state() + eng.observables())
 
 
 # ---- a. the cable-count matrix ----------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """The engine's host-side command state, one channel per kind (velocity, position, force): what a single update does with the
 commands that are pending when it starts, whatever route they came by.  Against the fp64 oracle at the tolerances of
-tests/test_gpu_parity.py.
+tests/parity.py.
 
   1  all three kinds (and every pair) pending before one update, in every arrival order: the latch order is fixed - velocity,
      position, force (PLG.cpp:206-219 plus the [NEW] force ordering) - so Force mode wins, and on the way the Pid of every mode
@@ -22,8 +22,7 @@ import itertools
 import numpy as np
 import pytest
 
-from test_gpu_force_mode import static_forces
-from test_gpu_parity import TOL, compare, pair, perturbed_poses
+from parity import compare, pair, perturbed_poses, static_forces
 
 pytestmark = pytest.mark.gpu
 

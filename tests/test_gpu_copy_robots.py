@@ -1,6 +1,6 @@
 """cdpr_copy_robots / cdpr_copy_robots_device: robots of a per-robot handle continue from where other robots of the handle are now - on
 every record layout (register-resident per-robot records, the general path's record buffer with its hot rows, the precision = 64 rows),
-against the fp64 oracle at the tolerances of tests/test_gpu_parity.py (TOL) and tests/test_gpu_fp64.py (TOL64).  On the oracle a copy is
+against the fp64 oracle at the tolerances of tests/parity.py (TOL, TOL64).  On the oracle a copy is
 the "twin from birth" of tests/test_copy_robots_inputs.py: an oracle whose destination rows were those of the sources from the start.
 
   1  right after the copy, every kind: every getter returns for a destination its source's row to the bit; a twin engine that ran the
@@ -17,66 +17,19 @@ import numpy as np
 import pytest
 
 import copy_robots as cr
-import test_reset_robots_inputs as ri
+import parity
+import robot_histories as ri
+from parity import NAMES, TOL, TOL64, engines, equal_rows, every_getter, observed, oracle_at
 from per_robot_kinds import ALL, LAYOUTS, clean_env, config_of, named, state_of  # noqa: F401  (clean_env: autouse here too)
-from test_gpu_fp64 import TOL64
-from test_gpu_parity import TOL
 
 pytestmark = pytest.mark.gpu
 
 B = ri.B
-NAMES = ("pose", "twist", "q", "qd", "eff")
 GENERAL = ["general_n8", "general_lean_hot", "general_long"]  # per-wave tier decisions (gen_controller): exact only lane for lane
 
 
-def engines(pkg, cfg, pose, count):
-    out = [pkg.Engine(cfg, 0) for _ in range(count)]
-    for e in out:
-        e.set_platform_state_f64(pose7=pose.astype(np.float64)) if cfg.precision == 64 else e.set_platform_state(pose7=pose)
-    return out
-
-
-def oracle_at(oracle, cfg, pose):
-    ora = oracle.OracleSim(cfg.to_struct(), oracle.DERIV_EXACT)
-    ora.set_platform_state(pose7=pose.astype(np.float32).astype(np.float64))
-    return ora
-
-
-def readout(sim, cfg):
-    """pose, twist, q, qd, effort as compare / compare64 take them from an engine (an oracle: platform_state + joint_states)"""
-    if cfg.precision == 64 and hasattr(sim, "observables_f64"):
-        q, qd, e, p, t = sim.observables_f64()
-        return p, t, q, qd, e
-    return sim.platform_state() + sim.joint_states()
-
-
 def against_the_oracle(eng, ora, cfg, where):
-    tol = TOL64 if cfg.precision == 64 else TOL
-    worst = {}
-    for name, g, o in zip(NAMES, readout(eng, cfg), readout(ora, cfg)):
-        assert np.isfinite(g).all(), f"{where}: {name} is not finite"
-        worst[name] = float(np.abs(g - o).max())
-    print(f"copy_robots, {where}: " + "  ".join(f"{k} {v:.2e}" for k, v in worst.items()))
-    for name in NAMES:
-        assert worst[name] <= tol[name], f"{where}: {name} differs from the oracle by {worst[name]:.3e} (tolerance {tol[name]:.1e})"
-
-
-def every_getter(eng, cfg, pkg):
-    """state_of, the episode clock and the FK, TD, limit and pid-debug read-outs the handle's stages have"""
-    out = list(state_of(eng, cfg)) + [eng.episode_start(), eng.limit_state()]
-    if cfg.precision == 64:
-        out += list(eng.raw_state()) + list(eng.joint_states())  # (the float getters of the double rows)
-    if cfg.stages & pkg._abi.STAGE_FK:
-        out += list(eng.fk_state())
-    if cfg.stages & pkg._abi.STAGE_TD:
-        out += list(eng.td_state())
-    if cfg.stages & pkg._abi.STAGE_PID_DEBUG:
-        out.append(eng.pid_debug())
-    return out
-
-
-def equal_rows(xs, ys, rows_x, rows_y):
-    return all(np.array_equal(x[rows_x], y[rows_y]) for x, y in zip(xs, ys))
+    parity.against_the_oracle(eng, ora, cfg.precision == 64, where, printed="copy_robots")
 
 
 # ---- 1, 2, 3, 4 ----------------------------------------------------------------------------------------------------------------
@@ -128,7 +81,7 @@ def run_scenario(pkg, oracle, monkeypatch, kind, source, seed, exact, kicked=Non
         bits.append(equal_rows(got, got, dest, src))
         if exact:
             assert bits[-1], f"{kind}, {label}: destination and source have parted"
-        for name, x in zip(NAMES, readout(eng, cfg)):
+        for name, x in zip(NAMES, observed(eng, cfg.precision == 64)):
             err = float(np.abs(x[dest] - x[src]).max())
             assert err <= tol[name], f"{kind}, {label}: {name} of destination and source differ by {err:.3e}"
 
@@ -325,7 +278,7 @@ def test_a_pending_command_stays_with_its_index(pkg, oracle, monkeypatch, kind):
     against_the_oracle(eng, born, cfg, f"{kind}, pending velocity Joy, 1 step")
     eng.update(20), born.update(20)
     against_the_oracle(eng, born, cfg, f"{kind}, pending velocity Joy, 21 steps")
-    q = readout(eng, cfg)[2]
+    q = observed(eng, cfg.precision == 64)[2]
     assert not np.array_equal(q[0], q[2]) and not np.array_equal(q[0], q[4])
     eng.close(), born.close()
 

@@ -1,10 +1,10 @@
 """cdpr_evaluate_done / cdpr_evaluate_done_device / cdpr_reset_done_device / cdpr_get_episode_start: the verdict of a done rule computed
 on the device, and the per-robot episode clock.  The verdict is specified as a pure function of what the getters return, so every
 verdict here is compared - equal, not close - with tests/done_rules.py's done_reference on the engine's own getters; the closed loop
-is compared with the fp64 oracle at the tolerances of tests/test_gpu_parity.py (TOL) and tests/test_gpu_fp64.py (TOL64) under the
+is compared with the fp64 oracle at the tolerances of tests/parity.py (TOL, TOL64) under the
 oracle-side condition tests/test_done_rule_inputs.py establishes.
 
-Handle kinds: one per record layout of tests/test_gpu_reset_robots.py (fast_n8, general_lean_hot, fp64_hold_n8: per-robot commands), a
+Handle kinds (tests/done_handles.py): one per record layout of tests/per_robot_kinds.py (fast_n8, general_lean_hot, fp64_hold_n8: per-robot commands), a
 uniform n = 8 handle with FK + TD, a uniform n = 4 lane-pair handle, a uniform n = 12 handle.
 
   1  static verdicts   2  after real steps (FK residual, infeasible flag, travel bits; publish decimation)   3  forms and outputs
@@ -14,81 +14,19 @@ uniform n = 8 handle with FK + TD, a uniform n = 4 lane-pair handle, a uniform n
 B = 130: two full wavefronts and a ragged one, stride 192.
 """
 import ctypes as C
-from dataclasses import replace
 
 import numpy as np
 import pytest
 
 import done_rules as dr
+import parity
 import per_robot_kinds as prk
-import test_gpu_reset_robots as rr
-import test_reset_robots_inputs as ri
+import robot_histories as ri
+from done_handles import B, KINDS, LAYOUTS, STRIDE, UNIFORM, assert_verdict, config_of, drive, expect, getters, limited, put
 
 pytestmark = pytest.mark.gpu
 
-B = dr.B
-STRIDE = 192
-LAYOUTS = prk.LAYOUTS  # fast_n8, general_lean_hot, fp64_hold_n8
-UNIFORM = {  # kind: (cables, Config arguments)
-    "uniform_n8": (8, dict(stages=3)),
-    "uniform_n4_pair": (4, dict(stages=0, mapping=2)),  # _abi.MAP_LANE_PAIR
-    "uniform_n12": (12, dict(stages=3)),
-}
-KINDS = LAYOUTS + list(UNIFORM)
-
-
 clean_env = prk.clean_env  # (autouse here too)
-
-
-def config_of(pkg, kind, monkeypatch, model_edit=None, **extra):
-    """The Config of a handle kind; model_edit(model) -> model and extra Config arguments for the cases that need limits."""
-    if kind in UNIFORM:
-        n, kw = UNIFORM[kind]
-        per_robot = False
-    else:
-        n, kw, env, _ = prk.HANDLES[kind]
-        per_robot = True
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-    model = ri.model_of(pkg, n)
-    if model_edit is not None:
-        model = model_edit(model)
-    return pkg.Config(model=model, batch=B, perRobotCommands=per_robot, **{**kw, **extra})
-
-
-def put(eng, cfg, pose, twist=None):
-    if cfg.precision == 64:
-        eng.set_platform_state_f64(pose7=None if pose is None else np.asarray(pose, dtype=np.float64), twist6=None if twist is None else np.asarray(twist, dtype=np.float64))
-    else:
-        eng.set_platform_state(pose7=pose, twist6=twist)
-
-
-def getters(eng, cfg):
-    """what the verdict is a function of, as the getters hand it out"""
-    f64 = cfg.precision == 64
-    pose, twist = eng.raw_state_f64() if f64 else eng.raw_state()
-    fk, td = bool(cfg.stages & 1), bool(cfg.stages & 2)
-    return dict(pose=pose, twist=twist, fk_residual=eng.fk_state()[1] if fk else None, infeasible=eng.td_state()[1] if td else None,
-                limit_mask=eng.limit_state(), start=eng.episode_start(), step_count=eng.step_count, f64=f64)
-
-
-def expect(eng, cfg, rule):
-    return dr.done_reference(rule, **getters(eng, cfg))
-
-
-def assert_verdict(got, want, where):
-    for name, g, w in zip(("mask", "reason", "counts"), got, want):
-        assert g.dtype == w.dtype and np.array_equal(g, w), f"{where}: {name} differs from the reference at {np.nonzero(np.asarray(g) != np.asarray(w))[0][:8]}"
-
-
-def drive(engs, cfg, h, steps):
-    """the history of the reset tests on a per-robot handle (modes by index mod 3); one velocity Joy on a uniform handle"""
-    if cfg.perRobotCommands:
-        ri.play_history(engs, h, steps)
-    else:
-        for e in engs:
-            assert e.set_velocity_command(h["v"]) == 0
-            e.update(steps)
 
 
 # ---- 1 -------------------------------------------------------------------------------------------------------------------------
@@ -130,10 +68,6 @@ def test_static_verdicts(pkg, monkeypatch, kind):
 
 
 # ---- 2 -------------------------------------------------------------------------------------------------------------------------
-def limited(model):
-    return replace(model, travel_lower=-0.015, travel_upper=0.015)
-
-
 @pytest.mark.parametrize("period", [0.0, 0.0025], ids=["every_step", "decimated"])
 @pytest.mark.parametrize("kind", KINDS)
 def test_after_real_steps(pkg, monkeypatch, kind, period):
@@ -366,12 +300,12 @@ def test_the_closed_loop_against_the_oracle(pkg, oracle, monkeypatch, kind):
     cfg = config_of(pkg, kind, monkeypatch)
     rule = dr.loop_rule(pkg, cfg.model)
     h, respawn = dr.loop_inputs(cfg.model)
-    (eng,), ora = rr.start(pkg, oracle, cfg, h["pose"])
+    (eng,), ora = parity.sims_at(pkg, oracle, cfg, h["pose"])
     points = dr.LOOP_STEPS // dr.LOOP_EVERY
     d_pose, d_counts = eng.device_alloc(B * 7 * 4), eng.device_alloc(points * dr.COUNTS * 4)
 
     def check(j, mask, reason, counts, p, t):
-        rr.against_the_oracle(eng, ora, cfg, f"done rules, {kind}, evaluation point {j}")
+        parity.against_the_oracle(eng, ora, cfg.precision == 64, printed="reset_robots", where=f"done rules, {kind}, evaluation point {j}")
 
     def reset_engine(j, poses):
         eng.device_upload_into(d_pose, poses)  # fresh poses from a device buffer (on the engine's stream, behind the reset that read it last)
@@ -389,7 +323,7 @@ def test_the_closed_loop_against_the_oracle(pkg, oracle, monkeypatch, kind):
         start[mask.astype(bool)] = (j + 1) * dr.LOOP_EVERY
     assert np.array_equal(eng.episode_start(), start)
     eng.update(1), ora.update(1)
-    rr.against_the_oracle(eng, ora, cfg, f"done rules, {kind}, one step after the last reset")
+    parity.against_the_oracle(eng, ora, cfg.precision == 64, printed="reset_robots", where=f"done rules, {kind}, one step after the last reset")
     eng.device_free(d_pose), eng.device_free(d_counts)
     eng.close(), ora.close()
 

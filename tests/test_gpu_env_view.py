@@ -4,7 +4,7 @@ compared - equal, not close, NaN and Inf included - with the getter it names (te
 with Engine.evaluate_done on the same state, the reward with reward_reference at the bound tests/test_env_view_inputs.py establishes
 (64 * 2^-24 * M on fp32 handles, 2^-24 |r| + 64 * 2^-53 * M on precision = 64 handles).
 
-Handle kinds and batch are those of tests/test_gpu_done.py: fast_n8, general_lean_hot, fp64_hold_n8 (per-robot commands), uniform_n8,
+Handle kinds and batch are those of tests/done_handles.py: fast_n8, general_lean_hot, fp64_hold_n8 (per-robot commands), uniform_n8,
 uniform_n4_pair, uniform_n12; B = 130 (two full wavefronts and a ragged one - one 128-robot workgroup and two robots of a second);
 on fast_n8 also B = 1 and B = 321.
 
@@ -18,11 +18,11 @@ from dataclasses import replace
 import numpy as np
 import pytest
 
+import done_handles as gd
 import done_rules as dr
 import env_view as ev
 import per_robot_kinds as prk
-import test_gpu_done as gd
-import test_reset_robots_inputs as ri
+import robot_histories as ri
 
 pytestmark = pytest.mark.gpu
 

@@ -1,21 +1,15 @@
 """UpdateMode::Force through the boundary (JointForceCalculator::setForce, JFC.h:42,92-95; JFC.cpp:67-70): the HIP engine
 against the fp64 oracle.  Force mode is the mode a JointForceCalculator is constructed in; `force = mForce`, no Pid runs,
 setForce resets nothing, leaving Force through a Joy resets the Pid of the mode entered (JFC.cpp:99-119).
-Tolerances: tests/test_gpu_parity.py."""
+Tolerances: tests/parity.py."""
 from dataclasses import replace
 
 import numpy as np
 import pytest
 
-from test_gpu_parity import TOL, compare, pair, perturbed_poses
+from parity import compare, pair, perturbed_poses, static_forces
 
 pytestmark = pytest.mark.gpu
-
-
-def static_forces(cfg, B, rng, spread=0.5):
-    """Forces around what holds the platform: 3.9657 N per cable on the shipped cube, mid tension on 8 cables."""
-    base = 3.965671444 if cfg.n_cables == 4 else 7.0
-    return (base + rng.uniform(-spread, spread, (B, cfg.n_cables))).astype(np.float32)
 
 
 @pytest.mark.parametrize("mapping_env", ["1", "2", "3"])

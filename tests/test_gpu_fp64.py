@@ -1,38 +1,12 @@
 """cdpr_config_t.precision = 64: the step in the reference's own precision (cdpr_step_kernel_f64.hpp), through the C-ABI,
-against the fp64 oracle.  Both sides compute in double; they differ in the order of the sums and in the derivative's
-formulation (closed-form end-point weights here, a least-squares fit in centred time there), so the agreement is that of
-two double implementations.  Measured on MI355X over this module: pose 8.3e-16, twist 5.1e-14, joint position 6.7e-16,
-joint velocity 3.9e-14, effort 1.2e-11 N (the position Pid's D gain times 1/dt = 8e4 N s/m amplifies the last bits of the
-1 ms window); config 1 over 3 000 steps: pose 1.7e-16, effort 7.3e-14.  Tolerances: two orders above that."""
+against the fp64 oracle at TOL64 (tests/parity.py, with the reasons for the numbers; compare64 and pair64 are that module's)."""
 import numpy as np
 import pytest
 
-from test_gpu_parity import perturbed_poses
+from parity import WORST64 as WORST
+from parity import TOL64, compare64, hold_commands, pair64, perturbed_poses
 
 pytestmark = pytest.mark.gpu
-
-TOL64 = {"pose": 1e-13, "twist": 5e-12, "q": 1e-13, "qd": 5e-12, "eff": 1e-9}
-WORST = {}
-
-
-def compare64(eng, ora, where, tol=TOL64):
-    gq, gqd, ge, gp, gt = eng.observables_f64()
-    op, ot = ora.platform_state()
-    oq, oqd, oe = ora.joint_states()
-    worst = {}
-    for name, g, o in (("pose", gp, op), ("twist", gt, ot), ("q", gq, oq), ("qd", gqd, oqd), ("eff", ge, oe)):
-        assert g.dtype == np.float64 and np.isfinite(g).all(), where
-        worst[name] = float(np.abs(g - o).max())
-        assert worst[name] <= tol[name], f"{where}: {name} differs from the oracle by {worst[name]:.3e} (tolerance {tol[name]:.1e})"
-        WORST[name] = max(WORST.get(name, 0.0), worst[name])
-    return worst
-
-
-def pair64(pkg, oracle, cfg, pose=None):
-    eng, ora = pkg.Engine(cfg, 0), oracle.OracleSim(cfg.to_struct(), oracle.DERIV_EXACT)
-    if pose is not None:
-        eng.set_platform_state_f64(pose7=pose), ora.set_platform_state(pose7=pose)
-    return eng, ora
 
 
 def test_config1_in_the_reference_precision(pkg, oracle):
@@ -199,8 +173,6 @@ def test_fp64_per_robot_modes_with_the_hold_branch(pkg, oracle, cables, stages, 
     per lane; the latch clears the rows of the Pid a robot's mode change enters): velocity Joys with cables at or below epsilon,
     position and setForce commands reaching subsets, a group going Velocity -> Position -> Velocity (both resets) while the
     others keep their Pids, fused launches and a trajectory record, a world reset - against the fp64 oracle."""
-    from test_gpu_general_matrix import hold_commands
-
     eps = 0.004
     rng = np.random.default_rng(184 + cables)
     model = pkg.eight_cable_model() if cables == 8 else pkg.cube_model()
@@ -329,8 +301,6 @@ def test_fp64_hold_branch(pkg, oracle, monkeypatch, cables, stages, B, split):
     beyond; CDPR_F64_SPLIT forces one or, "0", the one-wave kernel); the others the one-wave kernel's.  Round 6: the role-split
     kernels step the cables in passes (4 in the LDS build, 2 in the lean one; steady cables through the straight-line path, every
     other call through the per-cable code): 6 and 7 cables end on a short pass that repeats its last cable."""
-    from test_gpu_general_matrix import hold_commands
-
     if split is not None:
         monkeypatch.setenv("CDPR_F64_SPLIT", split)
 
@@ -413,8 +383,6 @@ def test_fp64_rest_of_pid_update(pkg, oracle, variant):
     (Pid.cpp:27-44; different depths on the two Pids), cmdLimit = 0 (Pid.cpp:175-184: without the clamp the Pid returns its stale
     mCmd member plus the anti-windup increment and restores the integral - the oracle follows the reference there), with and
     without the hold branch, and all of it together on a per-robot handle whose two Pids also fit different windows."""
-    from test_gpu_general_matrix import hold_commands
-
     B, n = 150, 8
     rng = np.random.default_rng(300 + len(variant))
     model = pkg.eight_cable_model()
@@ -489,7 +457,6 @@ def test_fp64_hold_branch_with_long_windows(pkg, oracle, variant):
     windows, cables crossing epsilon in both directions, mode changes (masked, on the per-robot variant, whose two Pids fit windows of
     24 and 11 samples), fused launches and the record - against the fp64 oracle."""
     from dataclasses import replace
-    from test_gpu_general_matrix import hold_commands
 
     B, cables = 110, 8
     pr = variant.startswith("per_robot")
@@ -544,7 +511,6 @@ def test_fp64_optional_physics_with_per_robot_modes_and_the_hold_branch(pkg, ora
     below epsilon, position and setForce commands on subsets (per-robot variants), joints running into their stops, one-step and
     fused launches, the trajectory record - against the fp64 oracle."""
     from dataclasses import replace
-    from test_gpu_general_matrix import hold_commands
 
     B, cables = 140, 8
     pr = variant.startswith("per_robot")
@@ -647,7 +613,6 @@ def test_role_split_fp64_hold_controller_against_the_one_wave_kernel(pkg, monkey
     window fills, held cables, cables crossing epsilon in both directions (windows with a gap: the fit), Position and Force mode,
     saturating commands (the clamp and its back-calculation), a ragged last block."""
     from dataclasses import replace
-    from test_gpu_general_matrix import hold_commands
 
     B, eps = 64 * 2 + 9, 0.004
     rng = np.random.default_rng(700 + cables)
@@ -741,8 +706,6 @@ def test_fp64_rollout_on_per_robot_handles(pkg, oracle, variant):
     with Pids reset at different times - a robot that is not in Velocity mode enters it with the rollout's first Joy (its Pid reset,
     its call count 0), the others carry their windows on; every trajectory has its own mode / call-count byte.  Against the oracle
     (B independent JointForceCalculator sets); the handle's own state and modes are left alone."""
-    from test_gpu_general_matrix import hold_commands
-
     B, n, S, H = 90, 8, 5, 14
     hold = variant.endswith("hold_branch")
     eps = 0.004 if hold else -0.001

@@ -11,7 +11,7 @@ import sys
 import numpy as np
 import pytest
 
-from test_gpu_parity import perturbed_poses
+from parity import perturbed_poses
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts"))
 from variant_digest import Collector  # noqa: E402  (what the bit-level digests snapshot of a handle)

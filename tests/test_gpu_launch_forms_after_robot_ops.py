@@ -3,7 +3,7 @@ robots (model_reset, take_over: csrc/cdpr_robot_records.hpp) against every step 
 one-step launches the modules of those calls use, but several steps per launch (update(k, spl), update_record, the per-robot schedule
 chain), the captured graph of ten fused launches and the MPC rollout.  Forms, script and rollout inputs: tests/launch_forms.py; the
 oracle-side conditions (history independence of the recipe, the script's sensitivity to a reset that forgets the controller):
-tests/test_launch_form_inputs.py.  Tolerances: test_gpu_parity.TOL, test_gpu_fp64.TOL64, the suite's rollout tolerances.
+tests/test_launch_form_inputs.py.  Tolerances: TOL and TOL64 of tests/parity.py, the suite's rollout tolerances.
 
 Kinds: per_robot_kinds.ALL and general_one_wave (the one-wave general kernel on 11-sample windows, whose fused launches really are
 several steps per launch).  Ops: reset_robots(reset_mask, fresh poses), copy_robots(copy_map), on the general kinds copy_robots(aligned_map)
@@ -55,17 +55,16 @@ import pytest
 
 import copy_robots as cr
 import launch_forms as lf
+import parity
 import resample_oracle as ro
-import test_reset_robots_inputs as ri
+import robot_histories as ri
+from parity import NAMES, TOL, TOL64, engines, equal_rows, every_getter, observed, oracle_at
 from per_robot_kinds import LAYOUTS, clean_env, config_of  # noqa: F401  (clean_env: autouse here too)
-from test_gpu_copy_robots import against_the_oracle, engines, equal_rows, every_getter, oracle_at
-from test_gpu_fp64 import TOL64
-from test_gpu_parity import TOL
 
 pytestmark = pytest.mark.gpu
 
 B = ri.B
-KINDS, GENERAL, FORMS, NAMES = lf.KINDS, lf.GENERAL, lf.FORMS, lf.NAMES
+KINDS, GENERAL, FORMS = lf.KINDS, lf.GENERAL, lf.FORMS
 FAST = ["fast_n8", "fast_n4", "fast_n7"]
 CASES = [(kind, op) for kind in KINDS for op in ["reset", "copy"] + (["copy_aligned"] if kind in GENERAL else [])]
 EVERY = slice(None)
@@ -73,6 +72,10 @@ EVERY = slice(None)
 NOT_BIT_EQUAL = set()
 MINIMUM = [(kind, form) for kind in ("fast_n8", "fast_n4", "fast_n7", "fp64_n8", "fp64_hold_n8", "fp64_hold_long") for form in ("fused10", "rec", "long")]
 assert not NOT_BIT_EQUAL & set(MINIMUM)
+
+
+def against_the_oracle(eng, ora, cfg, where):
+    parity.against_the_oracle(eng, ora, cfg.precision == 64, where, printed="copy_robots")  # (as tests/test_gpu_copy_robots.py)
 
 
 def tol_of(cfg):
@@ -132,16 +135,16 @@ class Scenario:
 def test_forms_against_the_oracle(pkg, oracle, monkeypatch, kind, op):
     sc = Scenario(pkg, oracle, monkeypatch, kind, op, FORMS, 301)
     cfg, tol = sc.cfg, tol_of(sc.cfg)
-    want = lf.readout(sc.ora.sim, cfg)
+    want = observed(sc.ora.sim, cfg.precision == 64)
     for p in sc.players:  # (the twin from birth holds the plain history on every robot that is no destination)
-        within(errors(lf.readout(p.sim, cfg), want, EVERY if op == "reset" else ~sc.touched), tol, f"{kind}, {op}, {p.form}, the end of the history")
+        within(errors(observed(p.sim, cfg.precision == 64), want, EVERY if op == "reset" else ~sc.touched), tol, f"{kind}, {op}, {p.form}, the end of the history")
     sc.apply()
     worst = {p.form: dict.fromkeys(NAMES, 0.0) for p in sc.players}
 
     def check(label, k):
-        want = lf.readout(sc.ora.sim, cfg)
+        want = observed(sc.ora.sim, cfg.precision == 64)
         for p in sc.players:
-            got = lf.readout(p.sim, cfg)
+            got = observed(p.sim, cfg.precision == 64)
             for name, v in errors(got, want).items():
                 worst[p.form][name] = max(worst[p.form][name], v)
             against_the_oracle(p.sim, sc.ora.sim, cfg, f"{kind}, {op}, {p.form}, {label}")
@@ -251,7 +254,7 @@ def test_a_reset_robot_forgets(pkg, monkeypatch, kind, form):
         exact.append(equal_rows(gx, gy, m, m))
         if kind not in GENERAL:
             assert exact[-1], f"{kind}, {form}, {label}: a reset robot remembers its history"
-        within(errors(lf.readout(x.sim, cfg), lf.readout(y.sim, cfg), m), tol, f"{kind}, {form}, {label}, the reset robots of two histories")
+        within(errors(observed(x.sim, cfg.precision == 64), observed(y.sim, cfg.precision == 64), m), tol, f"{kind}, {form}, {label}, the reset robots of two histories")
         apart.append(float(np.abs(gx[0][~m] - gy[0][~m]).max()))
 
     check("right after the reset")

@@ -19,7 +19,7 @@ step apart costs at most half the effort tolerance.
      steps after each of two Joys.  A branch taken differently from the oracle moves efforts by tens of newtons.
   d. the MPC rollout under `command` on a fast, a general and an fp64 handle: costs against oracle.rollout_velocity at
      1e-6 + 2e-4 max |cost|, the engine's state bit-identical before and after.
-  e. coverage (every family of test_gpu_workspace.FAMILIES ran) and the report of the worst errors (-s).
+  e. coverage (every family of workspace_poses.FAMILIES ran) and the report of the worst errors (-s).
 
 Measured on MI355X (this module's run inside the whole GPU suite; test_zz_report_measured_agreement prints every row with -s):
   a. worst over the fp32 cells, one-step and fused launches (pose, twist, q, qd, effort):
@@ -42,62 +42,34 @@ at 0.01 and 0, and on both fp64 controls at every epsilon; general_ctl now passe
 import numpy as np
 import pytest
 
+import parity
 import pid_limits as pl
 import workspace_poses as wp
-from test_gpu_cable_counts import TOL64
-from test_gpu_parity import TOL
-from test_gpu_workspace import FAMILIES
+from parity import TOL, TOL64, observed, state_of
 
 pytestmark = pytest.mark.gpu
 
-NAMES = ("pose", "twist", "q", "qd", "eff")
 WORST = {}
 RAN = {}  # cell -> kernel names its launches ran on
+clean_env = parity.clean_env_fixture()
 
 
 def note(where, name, err):
     WORST[(where, name)] = max(WORST.get((where, name), 0.0), float(err))
 
 
-@pytest.fixture(autouse=True)
-def clean_env(monkeypatch):
-    for k in wp.OVERRIDES:
-        monkeypatch.delenv(k, raising=False)
-
-
-def observed(eng, f64):
-    """(pose, twist, q, qd, effort) of the last published step."""
-    if f64:
-        q, qd, e, p, t = eng.observables_f64()
-    else:
-        q, qd, e = eng.joint_states()
-        p, t = eng.platform_state()
-    return p, t, q, qd, e
-
-
-def state_of(eng, f64):
-    return (eng.raw_state_f64() + eng.observables_f64()) if f64 else (eng.raw_state() + eng.observables())
-
-
 def start(pkg, oracle, cfg, pose, engines=1):
-    f64 = cfg.precision == 64
-    engs = [pkg.Engine(cfg, 0) for _ in range(engines)]
-    ora = oracle.OracleSim(cfg.to_struct(), oracle.DERIV_EXACT)
-    for e in engs:
-        e.set_platform_state_f64(pose7=pose.astype(np.float64)) if f64 else e.set_platform_state(pose7=pose)
-    ora.set_platform_state(pose7=pose.astype(np.float64))
-    return engs, ora
+    return parity.sims_at(pkg, oracle, cfg, pose, engines, through_f32=False)  # (the oracle starts at the doubles)
 
 
 def against_the_oracle(eng, ora, f64, where, report, failures):
+    """every quantity outside its tolerance is a line of `failures`, with the robot and the column"""
     tol = TOL64 if f64 else TOL
-    want = ora.platform_state() + ora.joint_states()
-    for name, g, o in zip(NAMES, observed(eng, f64), want):
-        assert np.isfinite(g).all(), f"{where}: {name}"
-        err = float(np.abs(g - o).max())
+    got, want = observed(eng, f64), observed(ora)
+    for name, (err, r, i) in parity.worst_errors(got, want, where, f64=f64).items():
         note(report, name, err)
         if err > tol[name]:
-            r, i = np.unravel_index(np.abs(g - o).argmax(), g.shape)
+            g, o = got[parity.NAMES.index(name)], want[parity.NAMES.index(name)]
             failures.append(f"{where}: {name} differs from the oracle by {err:.3e} (tolerance {tol[name]:.1e}; robot {r}, column {i}: {g[r, i]!r} against {o[r, i]!r})")
 
 
@@ -207,7 +179,7 @@ def test_rollout_under_the_command_clamp(pkg, oracle, handle):
     before = state_of(eng, f64)
     gc = eng.rollout_velocity(cmds, ref)
     oc = ora.rollout_velocity(cmds, ref.astype(np.float64))
-    err, tol = float(np.abs(gc - oc).max()), pl.rollout_cost_tolerance(oc)
+    err, tol = float(np.abs(gc - oc).max()), parity.rollout_cost_tol(oc, 1e-6)
     note(f"rollout, {handle}", "cost / tolerance", err / tol)
     print(f"rollout under the command clamp, {handle} handle: costs differ by {err:.3e} (tolerance {tol:.3e})")
     assert gc.shape == (pl.ROLLOUT["B"], pl.ROLLOUT["S"]) and np.isfinite(gc).all()
@@ -224,9 +196,9 @@ def test_rollout_under_the_command_clamp(pkg, oracle, handle):
 
 # ---- e. coverage and report ----------------------------------------------------------------------------------------------------
 def test_zy_every_family_ran(pkg):
-    """The launches of the matrix ran on every family of test_gpu_workspace.FAMILIES (a routing change, or a limit that re-routes
+    """The launches of the matrix ran on every family of workspace_poses.FAMILIES (a routing change, or a limit that re-routes
     a handle, cannot hollow the module out)."""
-    missing = [fam for fam, (cell, pred) in FAMILIES.items() if not any(pred(k) for k in RAN.get(cell, ()))]
+    missing = [fam for fam, (cell, pred) in wp.FAMILIES.items() if not any(pred(k) for k in RAN.get(cell, ()))]
     assert not missing, (f"families that did not run IN THIS PROCESS: {missing}.  This test reads what test_clamps_against_the_oracle recorded: run "
                          f"the whole module in one process (no -k, no single node id, no distributing plugin); only then does a missing family "
                          f"mean a routing change.  Ran: { {c: sorted(v) for c, v in RAN.items()} }")

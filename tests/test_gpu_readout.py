@@ -29,8 +29,8 @@ import pytest
 
 import per_robot_kinds as prk
 import readout_layout as rl
-import test_reset_robots_inputs as ri
-from test_gpu_parity import perturbed_poses
+import robot_histories as ri
+from parity import perturbed_poses
 
 pytestmark = pytest.mark.gpu
 

@@ -24,9 +24,9 @@ import numpy as np
 import pytest
 
 import resample_oracle as ro
-import test_reset_robots_inputs as ri
+import robot_histories as ri
+from parity import engines, equal_rows, every_getter
 from per_robot_kinds import LAYOUTS, clean_env, config_of  # noqa: F401  (clean_env: autouse here too)
-from test_gpu_copy_robots import engines, equal_rows, every_getter
 
 pytestmark = pytest.mark.gpu
 

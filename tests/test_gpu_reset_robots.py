@@ -1,8 +1,8 @@
 """cdpr_reset_robots / cdpr_reset_robots_device: chosen robots of a per-robot handle go back to the state Load leaves, at a pose of the
 caller's, while the others run on - on every record layout (register-resident per-robot records, the general path's record buffer
-with its hot rows, the precision = 64 rows), against the fp64 oracle at the tolerances of tests/test_gpu_parity.py (TOL) and
-tests/test_gpu_fp64.py (TOL64).  On the oracle a reset is the recipe of tests/test_reset_robots_inputs.py (oracle_reset), whose
-history independence that module establishes on the oracle alone.
+with its hot rows, the precision = 64 rows), against the fp64 oracle at the tolerances of tests/parity.py (TOL, TOL64).  On the oracle
+a reset is the recipe of tests/robot_histories.py (oracle_reset), whose history independence tests/test_reset_robots_inputs.py
+establishes on the oracle alone.
 
   1  against the oracle on every handle kind: robots in Position / Velocity / Force mode by index mod 3, 37 steps, every fourth robot
      plus 0, 63, 64, 129 reset to fresh poses; compared 1 and 7 steps later, 30 steps after a masked velocity Joy whose even cables
@@ -21,35 +21,19 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import test_reset_robots_inputs as ri
+import parity
+import robot_histories as ri
+from parity import TOL, TOL64, perturbed_poses, sims_at
 from per_robot_kinds import ALL, LAYOUTS, clean_env, config_of, named, state_of  # noqa: F401  (clean_env: autouse here too)
-from test_gpu_fp64 import TOL64, compare64, pair64
-from test_gpu_parity import TOL, compare, pair, perturbed_poses
 
 pytestmark = pytest.mark.gpu
 
 B = ri.B
-NAMES = ("pose", "twist", "q", "qd", "eff")
 BIT_EQUAL = ("fast_n8", "fast_n4", "fast_n7", "fp64_n8")   # one Pid record per robot: the recipe and the call zero it the same way
 
 
-def start(pkg, oracle, cfg, pose, engines=1):
-    """One engine with its oracle (pair / pair64) and engines - 1 more engines at the same start poses."""
-    f64 = cfg.precision == 64
-    eng, ora = pair64(pkg, oracle, cfg, pose.astype(np.float64)) if f64 else pair(pkg, oracle, cfg, pose)
-    more = [pkg.Engine(cfg, 0) for _ in range(engines - 1)]
-    for e in more:
-        e.set_platform_state_f64(pose7=pose.astype(np.float64)) if f64 else e.set_platform_state(pose7=pose)
-    return [eng] + more, ora
-
-
 def against_the_oracle(eng, ora, cfg, where):
-    if cfg.precision == 64:
-        worst = compare64(eng, ora, where)
-    else:
-        compare(eng, ora, where=where)
-        worst = {k: float(np.abs(g - o).max()) for k, g, o in zip(NAMES, eng.platform_state() + eng.joint_states(), ora.platform_state() + ora.joint_states())}
-    print(f"reset_robots, {where}: " + "  ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+    parity.against_the_oracle(eng, ora, cfg.precision == 64, where, printed="reset_robots")
 
 
 # ---- 1, 2 ----------------------------------------------------------------------------------------------------------------------
@@ -58,7 +42,7 @@ def run_scenario(pkg, oracle, monkeypatch, kind, twin):
     model = cfg.model
     h, a = ri.history_inputs(model, 31), ri.after_inputs(model, 32)
     mask = ri.reset_mask()
-    engs, ora = start(pkg, oracle, cfg, h["pose"], 2 if twin else 1)
+    engs, ora = sims_at(pkg, oracle, cfg, h["pose"], 2 if twin else 1)
     eng = engs[0]
     ri.play_history(engs + [ora], h)
     named(eng, kind)
@@ -99,7 +83,7 @@ def test_read_out_before_any_update(pkg, oracle, monkeypatch, kind):
     h, a = ri.history_inputs(cfg.model, 41), ri.after_inputs(cfg.model, 42)
     mask = ri.reset_mask()
     m = mask.astype(bool)
-    (eng,), ora = start(pkg, oracle, cfg, h["pose"])
+    (eng,), ora = sims_at(pkg, oracle, cfg, h["pose"])
     ri.play_history([eng], h)
     before = state_of(eng, cfg) + eng.fk_state() + (eng.limit_state(),) + eng.td_state()
     steps = eng.step_count
@@ -128,7 +112,7 @@ def test_read_out_of_the_pid_topic(pkg, oracle, monkeypatch):
     for precision in (32, 64):
         cfg = pkg.Config(model=ri.model_of(pkg, 8), batch=B, stages=3 | pkg._abi.STAGE_PID_DEBUG, perRobotCommands=True, precision=precision)
         h = ri.history_inputs(cfg.model, 44)
-        (eng,), ora = start(pkg, oracle, cfg, h["pose"])
+        (eng,), ora = sims_at(pkg, oracle, cfg, h["pose"])
         ri.play_history([eng], h, 15)
         m = ri.reset_mask().astype(bool)
         before = eng.pid_debug()
@@ -147,7 +131,7 @@ def test_forms_and_defaults(pkg, oracle, monkeypatch, kind):
     rng = np.random.default_rng(53)
     mask = ri.reset_mask()
     twist = rng.uniform(-0.01, 0.01, (B, 6)).astype(np.float32)
-    (host, dev, twin, every), ora = start(pkg, oracle, cfg, h["pose"], 4)
+    (host, dev, twin, every), ora = sims_at(pkg, oracle, cfg, h["pose"], 4)
     ri.play_history([host, dev, twin, every, ora], h)
     # host form = device form, with a twist
     host.reset_robots(mask, a["pose"], twist)
@@ -195,7 +179,7 @@ def test_a_pending_command_survives_the_reset(pkg, oracle, monkeypatch, kind):
     cfg = config_of(pkg, kind, monkeypatch)
     h, a = ri.history_inputs(cfg.model, 61), ri.after_inputs(cfg.model, 62)
     mask = ri.reset_mask()
-    (eng,), ora = start(pkg, oracle, cfg, h["pose"])
+    (eng,), ora = sims_at(pkg, oracle, cfg, h["pose"])
     ri.play_history([eng, ora], h)
     f = ri.forces(cfg.n_cables, np.random.default_rng(63))
     f_mask = (np.arange(B) % 8 < 3).astype(np.uint8)  # robots 0, 8, 16 ... are reset AND addressed; 1, 2, 9 ... only addressed
@@ -221,7 +205,7 @@ def test_a_reset_in_front_of_every_step(pkg, oracle, monkeypatch, kind):
     cfg = config_of(pkg, kind, monkeypatch)
     h = ri.history_inputs(cfg.model, 71)
     rng = np.random.default_rng(72)
-    (eng,), ora = start(pkg, oracle, cfg, h["pose"])
+    (eng,), ora = sims_at(pkg, oracle, cfg, h["pose"])
     ri.play_history([eng, ora], h)
     d_mask, d_pose = eng.device_alloc(B), eng.device_alloc(B * 7 * 4)
     for step in range(40):
@@ -249,7 +233,7 @@ def test_refusals_leave_the_handle_as_it_was(pkg, oracle, monkeypatch):
     # a uniform handle: one mode and one Pid call count for the whole batch
     cfg = config_of(pkg, "fast_n8", monkeypatch, per_robot=False)
     h = ri.history_inputs(cfg.model, 81)
-    (eng,), ora = start(pkg, oracle, cfg, h["pose"])
+    (eng,), ora = sims_at(pkg, oracle, cfg, h["pose"])
     for s in (eng, ora):
         s.set_velocity_command(h["v"])
         s.update(20)
@@ -264,7 +248,7 @@ def test_refusals_leave_the_handle_as_it_was(pkg, oracle, monkeypatch):
     eng.close(), ora.close()
     # a null mask, a null handle
     cfg = config_of(pkg, "fast_n8", monkeypatch)
-    (eng,), ora = start(pkg, oracle, cfg, h["pose"])
+    (eng,), ora = sims_at(pkg, oracle, cfg, h["pose"])
     ri.play_history([eng, ora], h, 20)
     assert lib().cdpr_reset_robots(eng._h, None, None, None) == pkg._abi.ERR_INVALID
     assert lib().cdpr_reset_robots_device(eng._h, None, None, None) == pkg._abi.ERR_INVALID
@@ -292,7 +276,7 @@ def test_the_engine_against_itself(pkg, oracle, monkeypatch, kind):
     h, a = ri.history_inputs(cfg.model, 91), ri.after_inputs(cfg.model, 92)
     mask = ri.reset_mask()
     m = mask.astype(bool)
-    (eng, rec), ora = start(pkg, oracle, cfg, h["pose"], 2)
+    (eng, rec), ora = sims_at(pkg, oracle, cfg, h["pose"], 2)
     ri.play_history([eng, rec], h)
     eng.reset_robots(mask, a["pose"])
     if f64:

@@ -2,38 +2,28 @@
 sequence it replaces (`for j: <callback of the kind>(batch j [, mask j]); refresh x update()`) bit for bit, and against the
 fp64 oracle.  The reference's own publishers give the schedules: squarepositiontest (squarepositiontest.cpp:21-35),
 squarevelocitytest with velocityEpsilon > 0 (squarevelocitytest.cpp:20-34 + the hold branch JFC.cpp:78-82), a setForce
-schedule (JFC.h:92-95) with the tension distribution on.  Tolerances: tests/test_gpu_parity.py."""
+schedule (JFC.h:92-95) with the tension distribution on.  Tolerances: tests/parity.py."""
 import itertools
 
 import numpy as np
 import pytest
 
-from test_gpu_parity import TOL, compare, perturbed_poses
+from parity import TOL, compare, perturbed_poses, sims_at, state_of
 
 pytestmark = pytest.mark.gpu
 
 SETTER = {"velocity": "set_velocity_command", "position": "set_position_command", "force": "set_force_command"}
 
 
-def state_of(e, f64=False):
-    if f64:
-        return e.observables_f64() + e.raw_state_f64()
-    return e.platform_state() + e.joint_states() + e.raw_state()
-
-
 def assert_same(a, b, what, f64=False):
-    for x, y in zip(state_of(a, f64), state_of(b, f64)):
+    for x, y in zip(state_of(a, f64, joint_states=True), state_of(b, f64, joint_states=True)):
         assert np.array_equal(x, y), what
 
 
 def run_both(pkg, oracle, cfg, pose, kind, sched, refresh, T, masks=None, record=True, f64=False, before=None, tol=TOL):
     """Engine `a` takes the schedule in one call, `b` the call sequence, the oracle runs beside them.  Returns (a, b, ora)."""
     B, n = cfg.batch, cfg.n_cables
-    a, b = pkg.Engine(cfg, 0), pkg.Engine(cfg, 0)
-    ora = oracle.OracleSim(cfg.to_struct(), oracle.DERIV_EXACT)
-    for e in (a, b):
-        e.set_platform_state_f64(pose7=pose) if f64 else e.set_platform_state(pose7=pose.astype(np.float32))
-    ora.set_platform_state(pose7=pose.astype(np.float64) if f64 else pose.astype(np.float32).astype(np.float64))
+    (a, b), ora = sims_at(pkg, oracle, cfg, pose, 2, through_f32=not f64, f64=f64)
     if before:
         for e in (a, b, ora):
             before(e)

@@ -166,9 +166,9 @@ def test_the_steady_variant_is_taken_and_left(pkg, monkeypatch):
 
 def test_steady_path_against_the_oracle_on_the_benchmark_workload(pkg, oracle, monkeypatch):
     """128 robots x 8 cables, 200 steps of bench.make_workload (seed 1235, a new command every 10 steps); tolerances of
-    tests/test_gpu_parity.py (TOL: its 200-step runs use them unchanged)."""
+    tests/parity.py (TOL: the 200-step runs of tests/test_gpu_parity.py use them unchanged)."""
     import bench
-    from test_gpu_parity import TOL, compare
+    from parity import TOL, compare
 
     monkeypatch.delenv("CDPR_SPLIT_STEADY", raising=False)
     batch, steps = 128, 200

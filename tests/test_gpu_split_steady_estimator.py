@@ -25,6 +25,7 @@ import numpy as np
 import pytest
 
 import workspace_poses as wp
+from parity import ROUTING_OVERRIDES
 
 pytestmark = pytest.mark.gpu
 
@@ -36,7 +37,7 @@ FK_VARIANTS = {"tolerance 1e-6 x 4": dict(fkTolerance=1e-6, fkMaxIterations=4), 
 STEADY = [(f"{mode} n{n} b{b}", n, b, mode) for n in (6, 7, 8) for mode in ("velocity", "position") for b in (65, 1)]
 GENERIC = [(f"generic handle: {name}", 8, 65, name) for name in FK_VARIANTS]
 SCENARIOS = STEADY + GENERIC + [("mode switch n8 b65", 8, 65, "switch")]
-OVERRIDES = tuple(wp.OVERRIDES) + ("CDPR_SPLIT_STEADY", "CDPR_NO_GRAPH", "CDPR_LIB")
+OVERRIDES = ROUTING_OVERRIDES + ("CDPR_SPLIT_STEADY", "CDPR_NO_GRAPH", "CDPR_LIB")
 
 
 def poses(pkg, model, batch, seed):

@@ -12,9 +12,9 @@ import numpy as np
 import pytest
 
 import copy_robots as cr
-import test_reset_robots_inputs as ri
+import robot_histories as ri
+from parity import perturbed_poses
 from per_robot_kinds import LAYOUTS, clean_env, config_of, state_of  # noqa: F401  (clean_env: autouse here too)
-from test_gpu_parity import perturbed_poses
 
 pytestmark = pytest.mark.gpu
 

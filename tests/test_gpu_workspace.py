@@ -47,14 +47,12 @@ import numpy as np
 import pytest
 
 import workspace_poses as wp
-from test_gpu_cable_counts import TOL64
-from test_gpu_parity import FULL_SIZE_SLICES, TOL, check_slice
+from parity import FULL_SIZE_SLICES, TOL, TOL64, check_slice, clean_env_fixture, observed, state_of, worst_errors
 
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 FIRST, NOT_STEADY = 1, 8  # CDPR_PLAN_* (include/cdpr.h)
-NAMES = ("pose", "twist", "q", "qd", "eff")
 WORST = {}
 RAN = {}  # cell -> kernel names its launches ran on
 
@@ -63,10 +61,7 @@ def note(where, name, err):
     WORST[(where, name)] = max(WORST.get((where, name), 0.0), float(err))
 
 
-@pytest.fixture(autouse=True)
-def clean_env(monkeypatch):
-    for k in wp.OVERRIDES:
-        monkeypatch.delenv(k, raising=False)
+clean_env = clean_env_fixture()
 
 
 def quat_diff(g, o):
@@ -182,20 +177,6 @@ def test_solve_td_over_the_edge_box(pkg, oracle, n):
 
 
 # ---- c. the closed-loop matrix over W ------------------------------------------------------------------------------------------
-def observed(eng, f64):
-    """(pose, twist, q, qd, effort) of the last published step."""
-    if f64:
-        q, qd, e, p, t = eng.observables_f64()
-    else:
-        q, qd, e = eng.joint_states()
-        p, t = eng.platform_state()
-    return p, t, q, qd, e
-
-
-def state_of(eng, f64):
-    return (eng.raw_state_f64() + eng.observables_f64()) if f64 else (eng.raw_state() + eng.observables())
-
-
 def oracle_jacobians(oracle, s, poses):
     return np.array([oracle.ik(s, p)[3] for p in poses])
 
@@ -243,13 +224,11 @@ def test_closed_loop_cell_over_the_wide_box(pkg, oracle, monkeypatch, cell):
         assert b.kernel_name == planned == c.kernel_name, where
         ran.update((a.kernel_name, b.kernel_name))
         # the oracle
-        got, want = observed(a, f64), ora.platform_state() + ora.joint_states()
-        for name, g, o in zip(NAMES, got, want):
-            assert np.isfinite(g).all(), f"{where}: {name}"
-            err = float(np.abs(g - o).max())
+        got = observed(a, f64)
+        for name, (err, robot, _) in worst_errors(got, observed(ora), where, f64=f64).items():
             note(cell, name, err)
             if err > tol[name]:
-                failures.append(f"{where}: {name} differs from the oracle by {err:.3e} (tolerance {tol[name]:.1e}, robot {int(np.abs(g - o).max(axis=1).argmax())})")
+                failures.append(f"{where}: {name} differs from the oracle by {err:.3e} (tolerance {tol[name]:.1e}, robot {robot})")
         # launch forms
         sa = state_of(a, f64)
         for e, form in ((b, "fused"), (c, "recorded")):
@@ -348,40 +327,10 @@ def test_full_size_launch_over_the_wide_box(pkg, oracle):
 
 
 # ---- e. coverage and report ----------------------------------------------------------------------------------------------------
-# kernel family or handle kind -> (cell, predicate on a kernel name).  The lumped legs and the joint stop are two options of ONE
-# kernel (the PHYS instantiations): their cells differ in the configuration, which test_zy_every_family_ran checks, not in the name.
-# The joint-stop cell runs the stop's sweeps every step with limits no joint reaches (test_workspace_inputs asserts it): a stop is a
-# threshold float32 and float64 may cross a step apart, so contact stays with test_travel_stop_against_the_oracle.
-FAMILIES = {
-    "cdpr_step_kernel (plain)": ("step", lambda k: k == "cdpr_step_kernel<8, true, true, SINGLE>"),
-    "cdpr_step_kernel (several steps)": ("step", lambda k: k == "cdpr_step_kernel<8, true, true>"),
-    "cdpr_step_kernel (low-register)": ("lowreg", lambda k: k.startswith("cdpr_step_kernel<8,") and "LOWREG" in k),
-    "cdpr_onestep_kernel": ("onestep", lambda k: k.startswith("cdpr_onestep_kernel<8,")),
-    "cdpr_split_kernel": ("split", lambda k: k == "cdpr_split_kernel<8, false>"),
-    "cdpr_step_kernel_pair": ("pair", lambda k: k.startswith("cdpr_step_kernel_pair<8, true, true")),
-    "cdpr_pair_stream_kernel": ("pair_stream", lambda k: k.startswith("cdpr_pair_stream_kernel<")),
-    "lane-per-cable": ("cable", lambda k: k.startswith("cdpr_step_kernel_cable<8,")),
-    "cdpr_gen_step_kernel": ("gen_step", lambda k: k.startswith("cdpr_gen_step_kernel<8,")),
-    "cdpr_gen_split_kernel": ("gen_split", lambda k: k.startswith("cdpr_gen_split_kernel<8>")),
-    "cdpr_gen_lean_kernel": ("gen_lean", lambda k: k.startswith("cdpr_gen_lean_kernel<8>")),
-    "cdpr_step_kernel_f64": ("f64_step", lambda k: k.startswith("cdpr_step_kernel_f64<8")),
-    "cdpr_split_kernel_f64": ("f64_split", lambda k: k.startswith("cdpr_split_kernel_f64<8")),
-    "per-robot handle (role-split)": ("per_robot", lambda k: k == "cdpr_split_kernel<8, true>"),
-    "per-robot handle (several steps)": ("per_robot", lambda k: k.startswith("cdpr_step_kernel<8,") and k.endswith(", PR>")),
-    "lumped-leg physics": ("lumped", lambda k: k.startswith("cdpr_step_kernel<8,") and "PHYS" in k),
-    "joint stop (the same PHYS kernel, travel_stop sweeps on)": ("joint_stop", lambda k: k.startswith("cdpr_step_kernel<8,") and "PHYS" in k),
-    "nine cables": ("n9", lambda k: k.startswith("cdpr_step_kernel<9,")),
-    "ten cables": ("n10", lambda k: k.startswith("cdpr_step_kernel<10,")),
-    "eleven cables": ("n11", lambda k: k.startswith("cdpr_step_kernel<11,")),
-    "twelve cables": ("n12", lambda k: k.startswith("cdpr_step_kernel<12,")),
-    "twelve cables, precision = 64": ("n12_f64", lambda k: k.startswith("cdpr_step_kernel_f64<12")),
-}
-
-
 def test_zy_every_family_ran(pkg):
     """The launches of the closed-loop matrix ran on every family of the list (a routing change cannot hollow the module out), and
     the optional-physics cells carry the options they are named for."""
-    missing = [fam for fam, (cell, pred) in FAMILIES.items() if not any(pred(k) for k in RAN.get(cell, ()))]
+    missing = [fam for fam, (cell, pred) in wp.FAMILIES.items() if not any(pred(k) for k in RAN.get(cell, ()))]
     assert not missing, (f"families that did not run IN THIS PROCESS: {missing}.  This test reads what test_closed_loop_cell_over_the_wide_box "
                          f"recorded: run the whole module in one process (no -k, no single node id, no distributing plugin); only then "
                          f"does a missing family mean a routing change.  Ran: { {c: sorted(v) for c, v in RAN.items()} }")

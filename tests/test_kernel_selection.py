@@ -12,12 +12,10 @@ import os
 import sys
 from dataclasses import replace
 
-import pytest
+from parity import ROUTING_OVERRIDES, clean_env_fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "kernel_selection.json")
-OVERRIDES = ("CDPR_MAPPING", "CDPR_LOWREG", "CDPR_CHUNK", "CDPR_PERSIST", "CDPR_ONESTEP", "CDPR_SPLIT", "CDPR_PAIR_STREAM", "CDPR_GEN_SPLIT", "CDPR_GEN_LEAN",
-             "CDPR_GEN_HOT")
 CABLES, BATCHES = tuple(range(1, 13)), (1, 4096, 32768, 65536, 131072, 524288)
 STAGES = {"none": 0, "fk": 1, "td": 2, "fk+td": 3}
 HANDLES = ("uniform", "per_robot", "general", "fp64")
@@ -61,10 +59,7 @@ def table(pkg):
     return out
 
 
-@pytest.fixture
-def clean_env(monkeypatch):
-    for k in OVERRIDES:
-        monkeypatch.delenv(k, raising=False)
+clean_env = clean_env_fixture()
 
 
 def test_auto_routing_table_is_pinned(pkg, clean_env):
@@ -167,7 +162,7 @@ if __name__ == "__main__":
     sys.path.insert(0, ROOT)
     import cdpr_simulation_amd as pkg_
 
-    for k_ in OVERRIDES:
+    for k_ in ROUTING_OVERRIDES:
         os.environ.pop(k_, None)
     if "--write" in sys.argv:
         json.dump(table(pkg_), open(GOLDEN, "w"), indent=0, sort_keys=True)

@@ -18,9 +18,9 @@ import numpy as np
 import pytest
 
 import launch_forms as lf
-import test_reset_robots_inputs as ri
+import robot_histories as ri
+from parity import NAMES, TOL
 from per_robot_kinds import ALL, clean_env, config_of  # noqa: F401  (clean_env: autouse here too)
-from test_gpu_parity import TOL
 
 B = ri.B
 
@@ -51,7 +51,7 @@ def test_the_after_script_is_benign_and_the_reset_robots_forget(pkg, oracle, mon
     assert len(labels) == 4 and len(players[0].steps) == len(players[1].steps) == 80
     apart, peak = [], 0.0
     for step, (xs, ys) in enumerate(zip(players[0].steps, players[1].steps)):
-        for quantity, x, y in zip(lf.NAMES, xs, ys):
+        for quantity, x, y in zip(NAMES, xs, ys):
             assert np.isfinite(x).all() and np.isfinite(y).all(), (kind, step, quantity)
             assert np.array_equal(x[m], y[m]), f"{kind}, step {step + 1}: {quantity} of the reset robots depends on their history (max difference {np.abs(x[m] - y[m]).max():.3e})"
         apart.append(float(np.abs(xs[0][~m] - ys[0][~m]).max()))

@@ -27,16 +27,10 @@ import pytest
 
 import pid_limits as pl
 import workspace_poses as wp
-from test_gpu_parity import TOL
+from parity import NAMES, TOL, clean_env_fixture, rollout_cost_tol
 
-NAMES = ("pose", "twist", "q", "qd", "eff")
 _BASE = {}
-
-
-@pytest.fixture
-def clean_env(monkeypatch):
-    for k in wp.OVERRIDES:
-        monkeypatch.delenv(k, raising=False)
+clean_env = clean_env_fixture()
 
 
 def run(oracle, cfg, variant, pose, cmds, stepwise=False):
@@ -258,7 +252,7 @@ def test_rollout_case_meets_the_command_clamp_and_is_benign(pkg, oracle, handle)
     cfg, pose, cmds = pl.rollout_inputs(pkg, handle)
     assert cmds.shape == (pl.ROLLOUT["B"], pl.ROLLOUT["H"], pl.ROLLOUT["S"], pl.ROLLOUT["n"]) and cmds.dtype == np.float32
     cost, ref = rollout_costs(oracle, cfg, pose, cmds)
-    tol = pl.rollout_cost_tolerance(cost)
+    tol = rollout_cost_tol(cost, 1e-6)
     free, _ = rollout_costs(oracle, pl.without(cfg, "cmd_limit"), pose, cmds, ref)
     share = float((np.abs(cost - free) > 10.0 * tol).mean())
     twin = np.nextafter(pose, np.where(np.random.default_rng(pl.ROLLOUT["seed"] + 2).random(pose.shape) < 0.5, -np.inf, np.inf).astype(np.float32))

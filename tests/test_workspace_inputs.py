@@ -14,12 +14,9 @@ import numpy as np
 import pytest
 
 import workspace_poses as wp
+from parity import clean_env_fixture
 
-
-@pytest.fixture
-def clean_env(monkeypatch):
-    for k in wp.OVERRIDES:
-        monkeypatch.delenv(k, raising=False)
+clean_env = clean_env_fixture()
 
 
 def run_script(oracle, cfg, pose, cmds, targets=None):

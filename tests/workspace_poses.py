@@ -19,7 +19,7 @@ BOXES = {
 
 def box_poses(model, B, rng, box):
     """B poses (x y z, quaternion x y z w; float64) drawn from box "W" or "E".  `model` is taken for symmetry with
-    special_poses and test_gpu_parity.perturbed_poses: the boxes are stated in frame coordinates."""
+    special_poses and parity.perturbed_poses: the boxes are stated in frame coordinates."""
     b = BOXES[box]
     pose = np.empty((B, 7))
     pose[:, :2] = rng.uniform(-b["dxy"], b["dxy"], (B, 2))
@@ -165,8 +165,36 @@ CELLS = {
     "n12":         (12, dict(stages=3), {}, 130, 9120),
     "n12_f64":     (12, dict(stages=3, precision=64), {}, 130, 9121),
 }
-OVERRIDES = ("CDPR_MAPPING", "CDPR_LOWREG", "CDPR_CHUNK", "CDPR_PERSIST", "CDPR_ONESTEP", "CDPR_SPLIT", "CDPR_PAIR_STREAM", "CDPR_GEN_SPLIT",
-             "CDPR_GEN_LEAN", "CDPR_GEN_HOT")
+
+
+# kernel family or handle kind -> (cell, predicate on a kernel name).  The lumped legs and the joint stop are two options of ONE
+# kernel (the PHYS instantiations): their cells differ in the configuration, which the test_zy_every_family_ran of tests/test_gpu_workspace.py and tests/test_gpu_pid_limits.py check, not in the name.
+# The joint-stop cell runs the stop's sweeps every step with limits no joint reaches (test_workspace_inputs asserts it): a stop is a
+# threshold float32 and float64 may cross a step apart, so contact stays with test_travel_stop_against_the_oracle.
+FAMILIES = {
+    "cdpr_step_kernel (plain)": ("step", lambda k: k == "cdpr_step_kernel<8, true, true, SINGLE>"),
+    "cdpr_step_kernel (several steps)": ("step", lambda k: k == "cdpr_step_kernel<8, true, true>"),
+    "cdpr_step_kernel (low-register)": ("lowreg", lambda k: k.startswith("cdpr_step_kernel<8,") and "LOWREG" in k),
+    "cdpr_onestep_kernel": ("onestep", lambda k: k.startswith("cdpr_onestep_kernel<8,")),
+    "cdpr_split_kernel": ("split", lambda k: k == "cdpr_split_kernel<8, false>"),
+    "cdpr_step_kernel_pair": ("pair", lambda k: k.startswith("cdpr_step_kernel_pair<8, true, true")),
+    "cdpr_pair_stream_kernel": ("pair_stream", lambda k: k.startswith("cdpr_pair_stream_kernel<")),
+    "lane-per-cable": ("cable", lambda k: k.startswith("cdpr_step_kernel_cable<8,")),
+    "cdpr_gen_step_kernel": ("gen_step", lambda k: k.startswith("cdpr_gen_step_kernel<8,")),
+    "cdpr_gen_split_kernel": ("gen_split", lambda k: k.startswith("cdpr_gen_split_kernel<8>")),
+    "cdpr_gen_lean_kernel": ("gen_lean", lambda k: k.startswith("cdpr_gen_lean_kernel<8>")),
+    "cdpr_step_kernel_f64": ("f64_step", lambda k: k.startswith("cdpr_step_kernel_f64<8")),
+    "cdpr_split_kernel_f64": ("f64_split", lambda k: k.startswith("cdpr_split_kernel_f64<8")),
+    "per-robot handle (role-split)": ("per_robot", lambda k: k == "cdpr_split_kernel<8, true>"),
+    "per-robot handle (several steps)": ("per_robot", lambda k: k.startswith("cdpr_step_kernel<8,") and k.endswith(", PR>")),
+    "lumped-leg physics": ("lumped", lambda k: k.startswith("cdpr_step_kernel<8,") and "PHYS" in k),
+    "joint stop (the same PHYS kernel, travel_stop sweeps on)": ("joint_stop", lambda k: k.startswith("cdpr_step_kernel<8,") and "PHYS" in k),
+    "nine cables": ("n9", lambda k: k.startswith("cdpr_step_kernel<9,")),
+    "ten cables": ("n10", lambda k: k.startswith("cdpr_step_kernel<10,")),
+    "eleven cables": ("n11", lambda k: k.startswith("cdpr_step_kernel<11,")),
+    "twelve cables": ("n12", lambda k: k.startswith("cdpr_step_kernel<12,")),
+    "twelve cables, precision = 64": ("n12_f64", lambda k: k.startswith("cdpr_step_kernel_f64<12")),
+}
 
 
 def cell_model(pkg, n, **model_kw):
