@@ -1,5 +1,6 @@
 """The environment view (cdpr_observe_device, cdpr_env_evaluate_device): the observation tensor and the reward in numpy, and the
-scenario shared by tests/test_env_view_inputs.py (CPU) and tests/test_gpu_env_view.py (GPU).  A plain module: no fixtures, no hooks.
+scenario shared by tests/test_env_view_inputs.py (CPU) and tests/test_gpu_env_view.py (GPU), and the comparisons of an engine with them
+that tests/test_gpu_env_view.py and tests/test_gpu_padded_stride.py make.  A plain module: no fixtures, no hooks.
 
 Both references take only what the engine's getters return (include/cdpr.h specifies the view as a function of them):
 `observation_reference` concatenates getter outputs, so the comparison with the device tensor is bit for bit; `reward_reference` is
@@ -16,6 +17,7 @@ precision = 64 handle computes in double and rounds once at the store: 2^-24 |r|
 import numpy as np
 from scipy.spatial.transform import Rotation
 
+import done_handles as gd
 import done_rules as dr
 
 FIELD_NAMES = ("pose", "twist", "joint_position", "joint_velocity", "effort", "fk_pose", "fk_residual", "age")
@@ -156,6 +158,80 @@ def spec_of(pkg, cfg, rule, weights, fields=0, ld=0, **over):
     if not cfg.stages & 1:
         kw["w_fk_residual"] = 0.0
     return pkg.EnvSpec(done=rule, fields=fields, ld=ld, **kw)
+
+
+# ---- the comparisons on an engine (tests/test_gpu_env_view.py, tests/test_gpu_padded_stride.py) -----------------------------------
+SENTINEL = np.float32(-77.25)
+
+
+class Buffers:
+    """device buffers of a test, freed together"""
+
+    def __init__(self, eng):
+        self.eng, self.ptrs = eng, []
+
+    def upload(self, array):
+        self.ptrs.append(self.eng.device_upload(array))
+        return self.ptrs[-1]
+
+    def free(self):
+        self.eng.synchronize()
+        for p in self.ptrs:
+            self.eng.device_free(p)
+        self.ptrs = []
+
+
+def observe_padded(eng, bufs, fields, ld, batch, d_row_mask=0, rows=None):
+    """observe_device into a sentinel-filled float[rows][ld] (rows > B): the whole buffer back"""
+    rows = rows or batch + 7
+    d = bufs.upload(np.full((rows, ld), SENTINEL, np.float32))
+    eng.observe_device(fields, d, ld, d_row_mask)
+    return eng.device_download(d, (rows, ld), np.float32)
+
+
+def check_observation(eng, cfg, bufs, where, batch=dr.B):
+    """case 1 at the engine's present state: every single field and all fields, ld = width and width + 3"""
+    g = view_getters(eng, cfg)
+    every = fields_of(cfg)
+    for fields in [1 << k for k in range(8) if (every >> k) & 1] + [every]:
+        want = observation_reference(fields, **g)
+        width = want.shape[1]
+        assert eng.observation_width(fields) == width == observation_reference(fields, **g).shape[1], f"{where}, fields {fields:#x}: the width"
+        for ld in (width, width + 3):
+            got = observe_padded(eng, bufs, fields, ld, batch)
+            assert np.array_equal(got[:batch, :width], want, equal_nan=True), f"{where}, fields {fields:#x}, ld {ld}: columns differ from the getters at {np.argwhere(~((got[:batch, :width] == want) | (np.isnan(want) & np.isnan(got[:batch, :width]))))[:6].tolist()}"
+            assert (got[batch:] == SENTINEL).all() and (got[:, width:] == SENTINEL).all(), f"{where}, fields {fields:#x}, ld {ld}: written past row B or past the width"
+    assert np.array_equal(eng.observe(every), observation_reference(every, **g), equal_nan=True), f"{where}: Engine.observe"
+    return g
+
+
+def check_reward_and_verdict(pkg, eng, cfg, rule, weights, target, where, nan_robots=(), batch=dr.B):
+    """cases 3 and 4 at the engine's present state; returns (spec, reward, reason)"""
+    f64 = cfg.precision == 64
+    every = fields_of(cfg)
+    spec = spec_of(pkg, cfg, rule, weights, fields=every)
+    want_verdict = eng.evaluate_done(rule)
+    obs, reward, mask, reason, counts = eng.env_evaluate(spec, target)
+    gd.assert_verdict((mask, reason, counts), want_verdict, f"{where}, verdict")
+    assert np.array_equal(obs, eng.observe(every), equal_nan=True), f"{where}: the observation of env_evaluate"
+    rg = reward_getters(eng, cfg)
+    home = cfg.model.home_pose()
+    r, M = reward_reference(spec, reason=reason, target7=target, home=home, **rg)
+    finite = np.isfinite(r)
+    with np.errstate(all="ignore"):
+        worst = float((np.abs(reward.astype(np.float64) - r)[finite] / reward_bound(r, M, f64)[finite]).max())
+    print(f"env view, {where}: reward within {worst:.3f} of the bound, {int((reason != 0).sum())} robots done")
+    assert reward.dtype == np.float32 and inside(reward, r, M, f64)[finite].all(), f"{where}: the reward leaves the bound ({worst:.2f} x) for robots {np.nonzero(finite & ~inside(reward, r, M, f64))[0][:8]}"
+    assert np.array_equal(np.nonzero(~finite)[0], np.sort(np.asarray(nan_robots, dtype=np.int64))), f"{where}: the reference is not finite for robots {np.nonzero(~finite)[0]}"
+    assert np.array_equal(reward[~finite].astype(np.float64), r[~finite], equal_nan=True), f"{where}: NaN / Inf rewards differ from the reference's"
+    # the bound separates this formula from a wrong one on these very inputs (both weights are live here)
+    swapped = spec_of(pkg, cfg, rule, dict(weights, w_position=weights["w_orientation"], w_orientation=weights["w_position"]))
+    assert (~inside(reward, *reward_reference(swapped, reason=reason, target7=target, home=home, **rg), f64)[finite]).sum() >= batch // 2, f"{where}: swapped weights stay inside the bound"
+    # the penalty is visible on exactly the done robots
+    free = eng.env_evaluate(spec_of(pkg, cfg, rule, weights, done_penalty=0.0), target)[1]
+    with np.errstate(all="ignore"):
+        assert np.array_equal((free != reward)[finite], (reason != 0)[finite]) and np.allclose((free - reward)[finite & (reason != 0)], weights["done_penalty"], rtol=0, atol=1e-3), f"{where}: the done penalty"
+    return spec, reward, reason
 
 
 def stand_in_efforts(n, f64):

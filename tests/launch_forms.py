@@ -13,13 +13,17 @@ A Player is one simulator (an Engine, or an OracleSim as form "oracle") that run
            set_*_command is not called for it
   oracle   update(1) x k, platform_state + joint_states kept after every step
 
+A Scenario is the engines (one Player per form), the oracle Player, the op and the after-script of one case; its `make` lets
+tests/test_gpu_padded_stride.py put the same case on handles with a padded row stride.
+
 B = 130: two full wavefronts and a ragged one, stride 192.
 """
 import numpy as np
 
+import copy_robots as cr
 import robot_histories as ri
-from parity import observed, rollout_cost_tol
-from per_robot_kinds import ALL
+from parity import engines, observed, oracle_at, rollout_cost_tol
+from per_robot_kinds import ALL, config_of
 
 B = ri.B
 KINDS = ALL + ["general_one_wave"]
@@ -69,8 +73,9 @@ class Player:
             assert getattr(self.sim, SETTER[kind])(rows, mask=mask) == 0
             return self.run(k)
         s = self.sim
-        d_rows = s.device_upload(np.ascontiguousarray(rows, dtype=np.float32).reshape(1, B, -1))
-        d_mask = s.device_upload(np.ascontiguousarray(mask, dtype=np.uint8).reshape(1, B))
+        batch = self.cfg.batch
+        d_rows = s.device_upload(np.ascontiguousarray(rows, dtype=np.float32).reshape(1, batch, -1))
+        d_mask = s.device_upload(np.ascontiguousarray(mask, dtype=np.uint8).reshape(1, batch))
         s.update_scheduled(k, k, d_rows, kind=kind, d_robot_masks=d_mask)
         s.synchronize()
         s.device_free(d_rows), s.device_free(d_mask)
@@ -82,6 +87,46 @@ class Player:
 
     def close(self):
         self.sim.close()
+
+
+class Scenario:
+    """Engines (one per form) and, with an oracle, its Player at the end of the history; the op; the after-script.  On a copy the oracle
+    is the twin from birth and the after-script's input rows of every destination are those of its source.  make(cfg, pose, forms):
+    the engines at `pose`, one per form (default: parity.engines; tests/padded_stride.py passes handles on a padded row stride)."""
+
+    def __init__(self, pkg, oracle, monkeypatch, kind, op, forms, seed, shift=0, make=None):
+        self.pkg, self.kind, self.op = pkg, kind, op
+        self.cfg = cfg = config_of(pkg, kind, monkeypatch)
+        self.source = None if op == "reset" else cr.copy_map() if op == "copy" else cr.aligned_map()
+        self.mask = ri.reset_mask()
+        self.touched = self.mask.astype(bool) if op == "reset" else cr.destinations_of(self.source)
+        self.h, self.a = ri.history_inputs(cfg.model, seed, shift), after_inputs(cfg.model, 77)
+        twinned = (lambda x: x) if op == "reset" else (lambda x: cr.twin_rows(x, self.source))
+        self.ht, self.at = twinned(self.h), twinned(self.a)
+        made = engines(pkg, cfg, self.h["pose"], len(forms)) if make is None else make(cfg, self.h["pose"], forms)
+        self.players = [Player(e, form, cfg) for e, form in zip(made, forms)]
+        self.ora = Player(oracle_at(oracle, cfg, self.ht["pose"]), "oracle", cfg) if oracle is not None else None
+        play_history(self.players, self.h)
+        if self.ora:
+            play_history([self.ora], self.ht)
+
+    def everyone(self):
+        return self.players + ([self.ora] if self.ora else [])
+
+    def apply(self):
+        for p in self.players:
+            p.sim.reset_robots(self.mask, self.a["pose"]) if self.op == "reset" else p.sim.copy_robots(self.source)
+        if self.ora and self.op == "reset":
+            ri.oracle_reset(self.ora.sim, self.mask, self.a["pose"])
+        for p in self.everyone():
+            p.steps.clear()
+
+    def play_after(self, check):
+        play_after(self.everyone(), self.at, check)
+
+    def close(self):
+        for p in self.everyone():
+            p.close()
 
 
 def after_inputs(model, seed, batch=B):

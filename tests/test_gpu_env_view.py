@@ -23,84 +23,14 @@ import done_rules as dr
 import env_view as ev
 import per_robot_kinds as prk
 import robot_histories as ri
+from env_view import SENTINEL, Buffers, check_observation, check_reward_and_verdict, observe_padded
 
 pytestmark = pytest.mark.gpu
 
 B, STRIDE, KINDS, LAYOUTS = gd.B, gd.STRIDE, gd.KINDS, gd.LAYOUTS
-SENTINEL = np.float32(-77.25)
 
 
 clean_env = prk.clean_env  # (autouse here too)
-
-
-class Buffers:
-    """device buffers of a test, freed together"""
-
-    def __init__(self, eng):
-        self.eng, self.ptrs = eng, []
-
-    def upload(self, array):
-        self.ptrs.append(self.eng.device_upload(array))
-        return self.ptrs[-1]
-
-    def free(self):
-        self.eng.synchronize()
-        for p in self.ptrs:
-            self.eng.device_free(p)
-        self.ptrs = []
-
-
-def observe_padded(eng, bufs, fields, ld, batch, d_row_mask=0, rows=None):
-    """observe_device into a sentinel-filled float[rows][ld] (rows > B): the whole buffer back"""
-    rows = rows or batch + 7
-    d = bufs.upload(np.full((rows, ld), SENTINEL, np.float32))
-    eng.observe_device(fields, d, ld, d_row_mask)
-    return eng.device_download(d, (rows, ld), np.float32)
-
-
-def check_observation(eng, cfg, bufs, where, batch=B):
-    """case 1 at the engine's present state: every single field and all fields, ld = width and width + 3"""
-    g = ev.view_getters(eng, cfg)
-    every = ev.fields_of(cfg)
-    for fields in [1 << k for k in range(8) if (every >> k) & 1] + [every]:
-        want = ev.observation_reference(fields, **g)
-        width = want.shape[1]
-        assert eng.observation_width(fields) == width == ev.observation_reference(fields, **g).shape[1]
-        for ld in (width, width + 3):
-            got = observe_padded(eng, bufs, fields, ld, batch)
-            assert np.array_equal(got[:batch, :width], want, equal_nan=True), f"{where}, fields {fields:#x}, ld {ld}: columns differ from the getters at {np.argwhere(~((got[:batch, :width] == want) | (np.isnan(want) & np.isnan(got[:batch, :width]))))[:6].tolist()}"
-            assert (got[batch:] == SENTINEL).all() and (got[:, width:] == SENTINEL).all(), f"{where}, fields {fields:#x}, ld {ld}: written past row B or past the width"
-    assert np.array_equal(eng.observe(every), ev.observation_reference(every, **g), equal_nan=True), f"{where}: Engine.observe"
-    return g
-
-
-def check_reward_and_verdict(pkg, eng, cfg, rule, weights, target, where, nan_robots=(), batch=B):
-    """cases 3 and 4 at the engine's present state; returns the reward"""
-    f64 = cfg.precision == 64
-    every = ev.fields_of(cfg)
-    spec = ev.spec_of(pkg, cfg, rule, weights, fields=every)
-    want_verdict = eng.evaluate_done(rule)
-    obs, reward, mask, reason, counts = eng.env_evaluate(spec, target)
-    gd.assert_verdict((mask, reason, counts), want_verdict, f"{where}, verdict")
-    assert np.array_equal(obs, eng.observe(every), equal_nan=True), f"{where}: the observation of env_evaluate"
-    rg = ev.reward_getters(eng, cfg)
-    home = cfg.model.home_pose()
-    r, M = ev.reward_reference(spec, reason=reason, target7=target, home=home, **rg)
-    finite = np.isfinite(r)
-    with np.errstate(all="ignore"):
-        worst = float((np.abs(reward.astype(np.float64) - r)[finite] / ev.reward_bound(r, M, f64)[finite]).max())
-    print(f"env view, {where}: reward within {worst:.3f} of the bound, {int((reason != 0).sum())} robots done")
-    assert reward.dtype == np.float32 and ev.inside(reward, r, M, f64)[finite].all(), f"{where}: the reward leaves the bound ({worst:.2f} x) for robots {np.nonzero(finite & ~ev.inside(reward, r, M, f64))[0][:8]}"
-    assert np.array_equal(np.nonzero(~finite)[0], np.sort(np.asarray(nan_robots, dtype=np.int64))), f"{where}: the reference is not finite for robots {np.nonzero(~finite)[0]}"
-    assert np.array_equal(reward[~finite].astype(np.float64), r[~finite], equal_nan=True), f"{where}: NaN / Inf rewards differ from the reference's"
-    # the bound separates this formula from a wrong one on these very inputs (both weights are live here)
-    swapped = ev.spec_of(pkg, cfg, rule, dict(weights, w_position=weights["w_orientation"], w_orientation=weights["w_position"]))
-    assert (~ev.inside(reward, *ev.reward_reference(swapped, reason=reason, target7=target, home=home, **rg), f64)[finite]).sum() >= batch // 2, where
-    # the penalty is visible on exactly the done robots
-    free = eng.env_evaluate(ev.spec_of(pkg, cfg, rule, weights, done_penalty=0.0), target)[1]
-    with np.errstate(all="ignore"):
-        assert np.array_equal((free != reward)[finite], (reason != 0)[finite]) and np.allclose((free - reward)[finite & (reason != 0)], weights["done_penalty"], rtol=0, atol=1e-3), where
-    return spec, reward, reason
 
 
 # ---- 1, 3, 4 -------------------------------------------------------------------------------------------------------------------

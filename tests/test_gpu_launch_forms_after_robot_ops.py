@@ -58,8 +58,9 @@ import launch_forms as lf
 import parity
 import resample_oracle as ro
 import robot_histories as ri
-from parity import NAMES, TOL, TOL64, engines, equal_rows, every_getter, observed, oracle_at
-from per_robot_kinds import LAYOUTS, clean_env, config_of  # noqa: F401  (clean_env: autouse here too)
+from parity import NAMES, TOL, TOL64, equal_rows, every_getter, observed
+from launch_forms import Scenario
+from per_robot_kinds import LAYOUTS, clean_env  # noqa: F401  (clean_env: autouse here too)
 
 pytestmark = pytest.mark.gpu
 
@@ -90,44 +91,6 @@ def within(worst, tol, where):
     print(f"launch forms, {where}: " + "  ".join(f"{k} {v:.2e}" for k, v in worst.items()))
     for name in NAMES:
         assert np.isfinite(worst[name]) and worst[name] <= tol[name], f"{where}: {name} differs from the oracle by {worst[name]:.3e} (tolerance {tol[name]:.1e})"
-
-
-class Scenario:
-    """Engines (one per form) and, with an oracle, its Player at the end of the history; the op; the after-script.  On a copy the oracle
-    is the twin from birth and the after-script's input rows of every destination are those of its source."""
-
-    def __init__(self, pkg, oracle, monkeypatch, kind, op, forms, seed, shift=0):
-        self.pkg, self.kind, self.op = pkg, kind, op
-        self.cfg = cfg = config_of(pkg, kind, monkeypatch)
-        self.source = None if op == "reset" else cr.copy_map() if op == "copy" else cr.aligned_map()
-        self.mask = ri.reset_mask()
-        self.touched = self.mask.astype(bool) if op == "reset" else cr.destinations_of(self.source)
-        self.h, self.a = ri.history_inputs(cfg.model, seed, shift), lf.after_inputs(cfg.model, 77)
-        twinned = (lambda x: x) if op == "reset" else (lambda x: cr.twin_rows(x, self.source))
-        self.ht, self.at = twinned(self.h), twinned(self.a)
-        self.players = [lf.Player(e, form, cfg) for e, form in zip(engines(pkg, cfg, self.h["pose"], len(forms)), forms)]
-        self.ora = lf.Player(oracle_at(oracle, cfg, self.ht["pose"]), "oracle", cfg) if oracle is not None else None
-        lf.play_history(self.players, self.h)
-        if self.ora:
-            lf.play_history([self.ora], self.ht)
-
-    def everyone(self):
-        return self.players + ([self.ora] if self.ora else [])
-
-    def apply(self):
-        for p in self.players:
-            p.sim.reset_robots(self.mask, self.a["pose"]) if self.op == "reset" else p.sim.copy_robots(self.source)
-        if self.ora and self.op == "reset":
-            ri.oracle_reset(self.ora.sim, self.mask, self.a["pose"])
-        for p in self.everyone():
-            p.steps.clear()
-
-    def play_after(self, check):
-        lf.play_after(self.everyone(), self.at, check)
-
-    def close(self):
-        for p in self.everyone():
-            p.close()
 
 
 # ---- 1 -------------------------------------------------------------------------------------------------------------------------
