@@ -172,7 +172,7 @@ std::vector<float4> home_state(const cdpr_engine* h, uint32_t rows) {
 }
 
 int upload_home(cdpr_engine* h) {
-  HIP_TRY(h, hipMemsetAsync(h->d_episode, 0, (size_t)h->stride * sizeof(uint32_t), h->stream));  // every episode starts at world step 0
+  HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)h->d_episode.p, (int)(uint32_t)h->origin, h->stride, h->stream));  // every episode starts at the origin (low word): age 0
   if (h->plan.fp64) return upload_home64(h);
   std::vector<float4> s = home_state(h, h->stride);
   HIP_TRY(h, hipMemcpyAsync(h->d_state, s.data(), s.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream));
@@ -220,9 +220,9 @@ void engine_reset_host(cdpr_engine* h) {
   }
   if (h->h_fault) *h->h_fault = 0u;
   h->mode = kModePosition;  // PLG.cpp:153-157: Position mode, target 0 after operator= -> reset()
-  h->step = 0;
+  h->step = h->origin;
   h->pid_calls = 0;
-  h->prev_publish = 0.0;  // PLG.cpp:59
+  h->prev_publish = sim_time(h->origin, h->cfg.dt);  // PLG.cpp:59 (0 at origin 0)
 }
 
 // Everything the copy stream still has in flight lands before the compute stream (or the host) touches a pending buffer
@@ -392,6 +392,8 @@ static int build_handle(cdpr_engine* h) {
   // profiles/r04_stride_padding.txt: this was most of "the 131 072 anomaly").  Any pad of 64 .. 1 088 columns cures it
   // alike; smaller batches are not padded (16 384: a pad costs 3-4 %).  CDPR_STRIDE_PAD=<columns> forces a pad (A/B).
   if (h->stride % 131072u == 0u) h->stride += 128u;
+  // CDPR_STEP_ORIGIN=<world step>: the handle's clock starts there, and returns there on cdpr_reset (tests: the late clock in seconds).
+  if (const char* so = std::getenv("CDPR_STEP_ORIGIN")) h->origin = (uint64_t)strtoull(so, nullptr, 10);
   if (const char* sp = std::getenv("CDPR_STRIDE_PAD")) h->stride = ((h->batch + 63u) & ~63u) + ((uint32_t)(std::max(0L, std::atol(sp)) + 63L) & ~63u);
   h->dbg = (cfg.stages & CDPR_STAGE_PID_DEBUG) != 0;
   if (h->plan.persist) {

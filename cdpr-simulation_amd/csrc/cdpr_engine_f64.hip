@@ -308,7 +308,7 @@ int rollout_enqueue_f64(cdpr_engine* h, int samples, int horizon, const float* d
     Roll64CmdArgs c{};
     c.commands = d_commands, c.out = h->d_roll64_cmd, c.batch = h->batch, c.samples = (uint32_t)samples, c.horizon = (uint32_t)horizon, c.n = n, c.k = (uint32_t)k;
     hipLaunchKernelGGL(cdpr_roll64_cmd_kernel, dim3((uint32_t)((traj * n + 255u) / 256u)), dim3(256), 0, h->stream, c);
-    const bool first_world = (h->step + (uint64_t)k) == 0;
+    const bool first_world = (steps_since_load(h) + (uint64_t)k) == 0;
     a.flags = (pr ? 0u : kFlagActualIsVelocity) | (first_world ? kFlagFirstWorldStep : 0u);
     a.pid_calls = sat_pid_calls(calls);
     a.ring_slot = ring_slot_of(h->step + (uint64_t)k, win64(h));

@@ -272,6 +272,7 @@ struct cdpr_engine {
   hipStream_t copy_stream = nullptr;  // host-side Joy batches travel on their own stream (CmdChannel::stage)
   int mode = kModePosition;
   uint64_t step = 0;
+  uint64_t origin = 0;           // the world step a fresh or reset handle stands at (CDPR_STEP_ORIGIN, read once by cdpr_create; default 0)
   double prev_publish = 0.0;
   StepArgs base{};               // world/body/FK/TD constants, pointers; Pid fields filled per launch
   StepArgs pid_vel{}, pid_pos{};  // only the Pid fields of these are used
@@ -394,6 +395,18 @@ inline int cmd_kind_of_mode(int mode) { return mode == kModeVelocity ? (int)CDPR
 
 constexpr int kCallSat = 64;  // Pid call counts saturate here on the host (the kernels ask "0?", ">= nbuf?")
 inline int sat_pid_calls(int calls) { return calls < kCallSat ? calls : kCallSat; }
+// World steps since Load (cdpr_create, cdpr_reset): the clock starts at h->origin, so "the first update has not run yet" is
+// steps_since_load(h) == 0 - the only spelling of that test on the host.
+inline uint64_t steps_since_load(const cdpr_engine* h) { return h->step - h->origin; }
+// The general controller path keeps world-step stamps as int32 (controller records, hot rows; GenCtl::now_step): a call that would take
+// the counter to 2^31 is refused - before a command is latched or a launch queued, so the handle is as it was.
+inline int general_clock_check(cdpr_engine* h, uint64_t nsteps) {
+  if (h->plan.general && h->step + nsteps >= (1ull << 31)) {
+    h->err = "general controller path: world-step counter would pass 2^31";
+    return CDPR_ERR_UNSUPPORTED;
+  }
+  return CDPR_OK;
+}
 // ring slot the error of world step `step` is written to (fp32 kernels: a ring of kWin; fp64: of w = win64)
 inline int ring_slot_of(uint64_t step) { return (int)((step + 8u) % (uint64_t)kWin); }
 inline int ring_slot_of(uint64_t step, int w) { return (int)((step + (uint64_t)(w - 2)) % (uint64_t)w); }
@@ -407,7 +420,7 @@ struct Schedule { int refresh; const uint32_t* ready; uint32_t* fault; };
 struct ChainStep {
   int k;                  // world steps of this launch: min(per_launch, left)
   int left;               // steps of the call not yet queued, this launch's included
-  uint32_t first_flag;    // kFlagFirstWorldStep at world step 0, else 0
+  uint32_t first_flag;    // kFlagFirstWorldStep at the first world step since Load, else 0
   uint64_t publish_mask;  // which of the k steps publish (bit j: world step h->step + j)
   void* record;           // where this launch's first observable image goes, null without a record
   int used, launches;     // out: world steps consumed, launches queued (k and 1 unless the path says otherwise)
@@ -544,7 +557,7 @@ int run_chain(cdpr_engine* h, int nsteps, int per_launch, void* record, void* ow
     s.k = s.used = std::min(per_launch, nsteps - done);
     s.left = nsteps - done;
     s.launches = 1;
-    s.first_flag = (h->step == 0) ? kFlagFirstWorldStep : 0u;
+    s.first_flag = (steps_since_load(h) == 0) ? kFlagFirstWorldStep : 0u;
     s.record = record ? static_cast<char*>(record) + (size_t)done * image : nullptr;
     double last;
     s.publish_mask = publish_mask(h, s.k, last);
@@ -552,7 +565,7 @@ int run_chain(cdpr_engine* h, int nsteps, int per_launch, void* record, void* ow
     advance_clock(h, s.used, s.launches);
     done += s.used;
   }
-  if (record && h->cfg.publish_period == 0.0 && h->step > 1)  // keep cdpr_get_* consistent: latest image into the engine's own
+  if (record && h->cfg.publish_period == 0.0 && steps_since_load(h) > 1)  // keep cdpr_get_* consistent: latest image into the engine's own
     HIP_TRY(h, hipMemcpyAsync(own_obs, static_cast<char*>(record) + (size_t)(nsteps - 1) * image, image, hipMemcpyDeviceToDevice, h->stream));
   return CDPR_OK;
 }

@@ -44,9 +44,9 @@ uint64_t publish_mask(const cdpr_engine* h, int k, double& last) {
   uint64_t mask = 0;
   last = h->prev_publish;
   if (h->cfg.publish_period == 0.0) {
-    if (k > 0 && h->step + (uint64_t)k > 1) last = sim_time(h->step + (uint64_t)k - 1, h->cfg.dt);
+    if (k > 0 && steps_since_load(h) + (uint64_t)k > 1) last = sim_time(h->step + (uint64_t)k - 1, h->cfg.dt);
     mask = (k >= 64) ? ~0ull : ((1ull << k) - 1ull);
-    return h->step == 0 ? (mask & ~1ull) : mask;
+    return steps_since_load(h) == 0 ? (mask & ~1ull) : mask;
   }
   for (int j = 0; j < k; ++j) {
     const double now = sim_time(h->step + (uint64_t)j, h->cfg.dt);
@@ -64,7 +64,7 @@ uint64_t publish_mask(const cdpr_engine* h, int k, double& last) {
 // general path keeps its counts on the device, in the controller records.
 void advance_clock(cdpr_engine* h, int k, int launches) {
   (void)publish_mask(h, k, h->prev_publish);
-  if (!h->plan.general && h->mode != kModeForce) h->pid_calls = sat_pid_calls(h->pid_calls + k - (h->step == 0 ? 1 : 0));
+  if (!h->plan.general && h->mode != kModeForce) h->pid_calls = sat_pid_calls(h->pid_calls + k - (steps_since_load(h) == 0 ? 1 : 0));
   h->step += (uint64_t)k;
   h->launches += (uint64_t)launches;
 }
@@ -80,7 +80,7 @@ static void set_weight_row(const cdpr_engine* h, StepArgs& a, int slot) {
 LaunchShape launch_shape(const cdpr_engine* h, int k, bool steady, const Schedule* sched) {
   LaunchShape s;
   s.steps = k;
-  s.first_world = h->step == 0;
+  s.first_world = steps_since_load(h) == 0;
   s.scheduled = sched != nullptr;
   s.steady = steady;
   return s;
@@ -114,7 +114,7 @@ StepKernel select_step_kernel(const cdpr_engine* h, int k, bool steady) { return
 // That kernel has no branch for anything but the steady state of a plain handle (cdpr_step_kernel_pair.hpp): every
 // condition below is one the general several-steps kernel tests per step instead (LaunchShape::steady).  CDPR_PAIR_STREAM=0: never (A/B).
 static bool pair_stream_steady(const cdpr_engine* h, const StepArgs& a, const Schedule* sched) {
-  return h->step != 0 && h->mode != kModeForce && a.pid_calls >= a.nbuf && h->cfg.publish_period == 0.0 && !a.dbg && !a.travel_on &&
+  return steps_since_load(h) != 0 && h->mode != kModeForce && a.pid_calls >= a.nbuf && h->cfg.publish_period == 0.0 && !a.dbg && !a.travel_on &&
          !(a.vel_limit > 0.f) && !a.unilateral && a.effort >= 0.f && a.clamp_cmd && !(sched && sched->ready);
 }
 // Can the handle's role-split launches ever take the steady-state kernel (cdpr_split_steady_kernel<N, VEL>, cdpr_onestep_kernel.hpp)?  What
@@ -128,7 +128,7 @@ static bool split_steady_handle(const cdpr_engine* h) {
 // tests per launch and these facts decide: such a handle in Velocity or Position mode, past world step 0, the derivative window full,
 // no `pid` topic, no travel flags.  Same bits either way (tested).
 static bool split_steady_launch(const cdpr_engine* h, const PlannedKernel& pk, const StepArgs& a) {
-  return pk.id == KernelId::Split && split_steady_handle(h) && h->step != 0 && h->mode != kModeForce && a.pid_calls != 0 &&
+  return pk.id == KernelId::Split && split_steady_handle(h) && steps_since_load(h) != 0 && h->mode != kModeForce && a.pid_calls != 0 &&
          a.pid_calls >= a.nbuf && !a.dbg && !a.travel_on;
 }
 uint32_t step_block_threads(const cdpr_engine* h, int k) { return planned_kernel(h->plan, launch_shape(h, k)).block; }
@@ -337,11 +337,7 @@ static int latch_pending(cdpr_engine* h, bool& reset_pid) {
 // General controller path: ONE launch per `per_launch` world steps (cdpr_general_step.hpp); with `record`, the observable
 // image of step j of the call goes to record + j * n_obs * stride.
 static int run_steps_general(cdpr_engine* h, int nsteps, int per_launch, void* record) {
-  if (h->step + (uint64_t)nsteps >= (1ull << 31)) {  // world-step stamps are int32 in the controller records
-    h->err = "general controller path: world-step counter would pass 2^31";
-    return CDPR_ERR_UNSUPPORTED;
-  }
-  StepArgs a = handle_args(h, record);
+  StepArgs a = handle_args(h, record);  // (run_steps has asked general_clock_check: world-step stamps are int32 in the controller records)
   a.cmd = nullptr;
   a.pid_calls = 0;
   copy_pid(h->pid_pos, a);  // unused
@@ -381,6 +377,7 @@ int run_steps(cdpr_engine* h, int nsteps, int per_launch, void* record, const Sc
   if (nsteps == 0) return CDPR_OK;
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
 
+  if (int rc = general_clock_check(h, (uint64_t)nsteps)) return rc;  // (in front of the latch: a refused update leaves pending commands pending)
   bool reset_pid = false;
   if (int rc = latch_pending(h, reset_pid)) return rc;
   if (h->plan.general) return run_steps_general(h, nsteps, per_launch, record);
@@ -489,6 +486,7 @@ int scheduled_update(cdpr_engine* h, uint32_t kind, int nsteps, int refresh_step
     return CDPR_ERR_INVALID;
   }
   if (nsteps == 0) return CDPR_OK;
+  if (int rc = general_clock_check(h, (uint64_t)nsteps)) return rc;  // (the whole schedule: no batch is staged, latched or stepped)
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
   if (d_ready && !h->h_fault) {  // the status word a mailbox that never delivers is reported through
     HIP_TRY(h, h->h_fault.alloc(sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
@@ -561,7 +559,7 @@ int scheduled_update(cdpr_engine* h, uint32_t kind, int nsteps, int refresh_step
       const int new_mode = (kind == CDPR_COMMAND_VELOCITY) ? kModeVelocity : kModePosition;
       const int nbuf = (kind == CDPR_COMMAND_VELOCITY) ? h->pid_vel.nbuf : h->pid_pos.nbuf;
       const int calls = (h->mode == new_mode) ? h->pid_calls : 0;  // (entering the mode resets the Pid)
-      const int fill = (calls >= nbuf ? 0 : nbuf - calls) + (h->step == 0 ? 1 : 0);
+      const int fill = (calls >= nbuf ? 0 : nbuf - calls) + (steps_since_load(h) == 0 ? 1 : 0);
       const int pre = ((fill + refresh_steps - 1) / refresh_steps) * refresh_steps;  // whole batches
       if (pre > 0 && pre < rest) rest = pre;
     }

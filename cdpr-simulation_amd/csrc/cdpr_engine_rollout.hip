@@ -18,10 +18,6 @@ static int rollout_enqueue(cdpr_engine* h, int samples, int horizon, const float
     }
     h->roll_rec_cols = std::max(cols, h->roll_rec_cols);  // (the records' column stride: never shrinks)
     HIP_TRY(h, h->d_roll_rec.ensure(h, h->glay.bytes(h->roll_rec_cols)));
-    if (h->step + (uint64_t)horizon >= (1ull << 31)) {
-      h->err = "general controller path: world-step counter would pass 2^31";
-      return CDPR_ERR_UNSUPPORTED;
-    }
     StepArgs a = h->base;
     a.state = h->d_state;
     a.obs = h->d_obs;
@@ -31,7 +27,7 @@ static int rollout_enqueue(cdpr_engine* h, int samples, int horizon, const float
     a.nsteps = horizon;
     a.publish_mask = 0;
     copy_pid(h->pid_vel, a);  // unused
-    a.flags = (h->step == 0) ? kFlagFirstWorldStep : 0u;
+    a.flags = (steps_since_load(h) == 0) ? kFlagFirstWorldStep : 0u;
     a.roll_cmd = d_commands;
     a.roll_ref = d_ref;
     a.roll_cost = d_cost;
@@ -64,7 +60,7 @@ static int rollout_enqueue(cdpr_engine* h, int samples, int horizon, const float
   a.publish_mask = 0;
   copy_pid(h->pid_vel, a);
   a.flags = kFlagActualIsVelocity;
-  if (h->step == 0) a.flags |= kFlagFirstWorldStep;
+  if (steps_since_load(h) == 0) a.flags |= kFlagFirstWorldStep;
   // a Joy on jointVelocities while in Position mode resets the velocity Pid (JFC.cpp:113-115); the handle's own
   // records stay untouched, the rollout starts from zeroed copies (per-robot handles: decided per lane from meta)
   if (!h->plan.per_robot && h->mode != kModeVelocity) a.flags |= kFlagRolloutResetPid;
@@ -99,6 +95,7 @@ static int rollout_check(cdpr_engine* h, int samples, int horizon, const void* d
     h->err = "rollout: too many trajectories";
     return CDPR_ERR_INVALID;
   }
+  if (int rc = general_clock_check(h, (uint64_t)horizon)) return rc;  // (the horizon's stamps are int32 too: refused before anything is staged)
   return set_device(h);
 }
 }  // namespace cdpr_host

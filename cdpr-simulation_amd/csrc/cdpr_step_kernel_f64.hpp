@@ -389,11 +389,15 @@ __device__ __forceinline__ void hold_tables_fill(const F64Args& a, uint32_t lane
 // A Pid call that needs nothing but the straight line: the Pid has been called since its reset and its window, with this call's
 // sample in it, is either a uniform one (the newest run of consecutive steps covers it) or still filling (derive() returns 0) -
 // the conditions of hold_finish64's first-call and fit branches, negated.
+// World steps reach the Pids as the low word of the 64-bit counter ((int)step: F64Args::step0, the stamps, the Pid word): differences
+// of two of them are taken modulo 2^32, so that they stay what they are across step 2^31 (where the int changes sign) and 2^32 (where
+// the low word wraps).  Below those steps: the plain int difference, bit for bit.
+__device__ __forceinline__ int steps_between(int now, int then) { return (int)((uint32_t)now - (uint32_t)then); }
 __device__ __forceinline__ bool hold_steady64(unsigned long long word, int now, int nbuf) {
   const int last = (int)(uint32_t)word, count_old = (int)(word >> kHwCount) & 63, run_old = (int)(word >> kHwRun) & 255;
   const bool was = ((word >> kHwWas) & 1ull) != 0ull;
   const int count = min(count_old + 1, nbuf);
-  const int run = (now == last + 1) ? min(run_old + 1, 255) : 1;
+  const int run = (steps_between(now, last) == 1) ? min(run_old + 1, 255) : 1;
   return was && !(run < nbuf && count >= nbuf);
 }
 // ... and that call: Pid::update (Pid.cpp:122-191) + JointForceCalculator's mLastPosition (JFC.cpp:68,75,87) without a branch - the
@@ -409,11 +413,11 @@ struct HoldFir64 {
 __device__ __forceinline__ HoldFir64 hold_fast_fir64(const HoldRows64& h, const double* wrot, double w0, int nbuf, double desired, double actual, int now, double dt) {
   HoldFir64 f;
   const int last = (int)(uint32_t)h.word, head_old = (int)(h.word >> kHwHead) & 63, count_old = (int)(h.word >> kHwCount) & 63, run_old = (int)(h.word >> kHwRun) & 255;
-  f.dts = (double)(now - last) * dt;
+  f.dts = (double)steps_between(now, last) * dt;
   f.error = desired - actual;
   f.head = (count_old == 0) ? 0 : ((head_old + 1 >= nbuf) ? 0 : head_old + 1);
   f.count = min(count_old + 1, nbuf);
-  f.run = (now == last + 1) ? min(run_old + 1, 255) : 1;
+  f.run = (steps_between(now, last) == 1) ? min(run_old + 1, 255) : 1;
   const double* const wr = wrot + f.head * kHoldWin;
   double acc = w0 * f.error;
 #pragma unroll
@@ -461,7 +465,7 @@ __device__ __forceinline__ double hold_finish64(double* R, size_t st, const Hold
   const double* const dc = velocity_pid ? a.dcoef[1] : a.dcoef[0];
   const int last = (int)(uint32_t)h.word, head_old = (int)(h.word >> kHwHead) & 63, count_old = (int)(h.word >> kHwCount) & 63, run_old = (int)(h.word >> kHwRun) & 255;
   const bool was = ((h.word >> kHwWas) & 1ull) != 0ull;  // Pid.cpp:123-126: the first call since reset returns 0 (and pushes no sample)
-  const double dts = (double)(now - last) * dt;
+  const double dts = (double)steps_between(now, last) * dt;
   const double error = desired - actual;
   double perr = error;
   if (FULL && a.any_cas) perr = hold_cascade64(R + (size_t)hold_cas_row(HW) * st, st, g.pcas, a.max_cas, pc, error, was && live);  // Pid.cpp:131
@@ -479,7 +483,7 @@ __device__ __forceinline__ double hold_finish64(double* R, size_t st, const Hold
   // Pid::derive: push the sample (dt > 0 always: a Pid is called at most once per world step)
   const int head = (count_old == 0) ? 0 : ((head_old + 1 >= g.nbuf) ? 0 : head_old + 1);
   const int count = min(count_old + 1, g.nbuf);
-  const int run = (now == last + 1) ? min(run_old + 1, 255) : 1;
+  const int run = (steps_between(now, last) == 1) ? min(run_old + 1, 255) : 1;
   // the uniform window's weights BY SLOT for this ring head (hold_tables_fill: the weight of the slot's age, 0 for the slot the new
   // sample goes to and for slots beyond nbuf - round 6: one LDS read and one fma per slot where the age, its wrap, its clamp, the
   // look-up and two selects were 13 instructions)
@@ -491,7 +495,7 @@ __device__ __forceinline__ double hold_finish64(double* R, size_t st, const Hold
   if (was && run < g.nbuf && count >= g.nbuf) {     // a full window with a gap in it: the fit on the real stamps
     double y[HW];
     int t[HW];
-    int t_old = now;
+    int t_old = 0;  // (the stamps go to the fit RELATIVE to this step, 0 = now: the oldest is the most negative on either side of 2^31 and 2^32)
     double stamp[HW];
 #pragma unroll
     for (int j = 0; j < HW; ++j) {
@@ -501,10 +505,10 @@ __device__ __forceinline__ double hold_finish64(double* R, size_t st, const Hold
 #pragma unroll
     for (int j = 0; j < HW; ++j) {
       y[j] = (j == head) ? error : h.y[j];
-      t[j] = (j == head) ? now : (int)stamp[j];
+      t[j] = (j == head) ? 0 : steps_between((int)stamp[j], now);
       t_old = (j < g.nbuf) ? min(t_old, t[j]) : t_old;
     }
-    derived = gen_fit<HW, double>(y, t, g.nbuf, g.degree, now, t_old) / dt;
+    derived = gen_fit<HW, double>(y, t, g.nbuf, g.degree, 0, t_old) / dt;
   }
   if (FULL && a.any_cas) derived = hold_cascade64(R + (size_t)(hold_cas_row(HW) + 4 * kHoldMaxCas) * st, st, g.dcas, a.max_cas, dc, derived, was && live);  // Pid.cpp:157
   const double d_term = g.kd * derived;
@@ -670,7 +674,7 @@ __global__ __launch_bounds__(64) void cdpr_step_kernel_f64(const F64Args a) {
               const double desired = vel_branch ? target : (hold ? hrows.held : target);
               bool ran = false;
               double tp = 0.0, ti = 0.0, td = 0.0;
-              force = hold_finish64<HOLD == 2, HW>(HR, st, hrows, &c_hold_rot[HOLD && vel_branch ? 1 : 0][0][0], pp[8], desired, vel_branch ? qd : q, (int)(a.step0 + step), a.dt, g, a, vel_branch, ran, tp, ti, td);
+              force = hold_finish64<HOLD == 2, HW>(HR, st, hrows, &c_hold_rot[HOLD && vel_branch ? 1 : 0][0][0], pp[8], desired, vel_branch ? qd : q, (int)((uint32_t)a.step0 + (uint32_t)step), a.dt, g, a, vel_branch, ran, tp, ti, td);
               if (i == 0 && ran) {
                 dbg_p = tp, dbg_i = ti, dbg_d = td;
                 dbg_ran = true;

@@ -203,7 +203,8 @@ class Engine:
                                                  C.c_void_p(d_counts) if d_counts else None))
 
     def episode_start(self) -> np.ndarray:
-        """uint32[B]: the world step (low 32 bits of step_count) of every robot's last model reset; 0 after create and reset()."""
+        """uint32[B]: the world step (low 32 bits of step_count) of every robot's last model reset; after create and reset() the low word of the
+        clock's origin (0 unless CDPR_STEP_ORIGIN was set at create: include/cdpr.h, cdpr_step_count)."""
         start = np.empty(self.B, dtype=np.uint32)
         self._check(lib().cdpr_get_episode_start(self._h, start.ctypes.data_as(C.POINTER(C.c_uint32))))
         return start

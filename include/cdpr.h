@@ -322,9 +322,9 @@ int cdpr_resample_device(cdpr_handle_t h, const cdpr_resample_spec_t *spec, cons
  *   mask[b]    reason[b] != 0, written as exactly 0 or 1: what cdpr_reset_robots_device takes.
  *   counts     uint32[CDPR_DONE_COUNTS]: counts[0] = robots done, counts[1 + k] = robots with reason bit k.  Zeroed on the stream in
  *              front of the kernel: consecutive calls do not accumulate.
- * Episode clock: every robot remembers the world step (low 32 bits of cdpr_step_count) of its last model reset - 0 after cdpr_create
- * and cdpr_reset, the step count at the call after cdpr_reset_robots[_device] / cdpr_reset_done_device took it; uniform handles keep
- * all zeros.  cdpr_get_episode_start reads it (uint32[B], waits for the stream).  CDPR_DONE_TIMEOUT compares
+ * Episode clock: every robot remembers the world step (low 32 bits of cdpr_step_count) of its last model reset - the low word of the
+ * origin (0 unless CDPR_STEP_ORIGIN was set, see cdpr_step_count) after cdpr_create and cdpr_reset, the step count at the call after cdpr_reset_robots[_device] / cdpr_reset_done_device took it; uniform handles keep
+ * that first value.  cdpr_get_episode_start reads it (uint32[B], waits for the stream).  CDPR_DONE_TIMEOUT compares
  * (uint32_t)(step_count - start) >= max_steps, which survives the wrap of the low word.
  * Any handle: uniform or per-robot commands, any kernel family, any cable count, both precisions (only platform and observable rows
  * are read, never a controller record).  These are not step launches: cdpr_kernel_name keeps naming the last step's kernel.
@@ -535,7 +535,23 @@ uint32_t cdpr_mapping(cdpr_handle_t h);              /* CDPR_MAP_* actually in u
 #define CDPR_PLAN_NOT_STEADY 8u
 int cdpr_plan_kernel(const cdpr_config_t *cfg, int steps_per_launch, uint32_t flags, char *name, size_t len);
 int cdpr_kernel_name(cdpr_handle_t h, char *name, size_t len);
-uint64_t cdpr_step_count(cdpr_handle_t h);           /* world steps since create/reset; sim time = count * dt */
+/* The world clock.  cdpr_step_count: the absolute world step, a 64-bit count; sim time = count * dt.  It starts at the handle's ORIGIN
+ * and returns there on cdpr_reset: 0, or what the environment variable CDPR_STEP_ORIGIN=<unsigned 64-bit decimal> held when cdpr_create
+ * ran (read once; tests and A/B runs put a handle late in the clock with it).  The origin is a pure relabelling of the world steps: a
+ * handle created at origin S does at step S + k what a handle created at origin 0 does at step k, to the bit; what names the absolute
+ * step differs - cdpr_step_count, the episode starts (the low word of the origin after create and cdpr_reset: age 0) - and where in a
+ * ring a sample sits.  "The first update since Load" (PLG.cpp:59: it only stores the joint positions) is step_count == origin.
+ * How far each path's clock goes (tests/test_gpu_late_clock.py runs every path across 2^24 and, where it crosses, 2^31 and 2^32):
+ *   register-resident paths (every fp32 handle off the general path, uniform or per-robot): cross 2^24, 2^31 and 2^32 - the kernels
+ *     see the ring slot alone, a 64-bit modulus taken on the host;
+ *   precision = 64, with or without the hold branch: cross 2^24, 2^31 and 2^32 - the Pids' stamps are the low word of the count and
+ *     every difference of two stamps is taken modulo 2^32;
+ *   general controller path (hold branch, cascades, long windows on fp32 handles) and its rollout: cross 2^24; world-step stamps are
+ *     int32 there, so a call that would take the count to 2^31 (step_count + nsteps >= 2^31; the rollout: + horizon) returns
+ *     CDPR_ERR_UNSUPPORTED ("general controller path: world-step counter would pass 2^31") before it latches a command or queues a
+ *     launch - the handle is bit for bit as it was, pending commands stay pending; cdpr_reset makes it step again;
+ *   the episode clock, CDPR_DONE_TIMEOUT and CDPR_OBS_AGE: the low word, differences modulo 2^32, across the wrap on every handle. */
+uint64_t cdpr_step_count(cdpr_handle_t h);
 
 /* Replaces publishJointStates (PLG.cpp:248-256): sensor_msgs/JointState
  * position / velocity / effort, float[B][n] each, as of the last published

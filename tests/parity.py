@@ -34,9 +34,10 @@ WORST64 = {}  # worst error per quantity over every compare64 of the session (te
 FULL_SIZE_SLICES = (slice(0, 128), slice(576, 704), slice(65408, 65536))
 
 # every CDPR_* name cdpr_select.hpp reads through env("...") (tests/test_support.py compares the list with the file), and
-# CDPR_STRIDE_PAD, which cdpr_create reads (the forced row-stride pad of tests/padded_stride.py: set around a create only)
+# CDPR_STRIDE_PAD, which cdpr_create reads (the forced row-stride pad of tests/padded_stride.py: set around a create only), and
+# CDPR_STEP_ORIGIN, which cdpr_create reads as well (the clock origin of tests/late_clock.py: set around a create only)
 ROUTING_OVERRIDES = ("CDPR_MAPPING", "CDPR_LOWREG", "CDPR_CHUNK", "CDPR_PERSIST", "CDPR_ONESTEP", "CDPR_SPLIT", "CDPR_PAIR_STREAM", "CDPR_GEN_SPLIT",
-                     "CDPR_GEN_LEAN", "CDPR_GEN_HOT", "CDPR_STRIDE_PAD")
+                     "CDPR_GEN_LEAN", "CDPR_GEN_HOT", "CDPR_STRIDE_PAD", "CDPR_STEP_ORIGIN")
 
 
 # ---- hermeticity ---------------------------------------------------------------------------------------------------------------
