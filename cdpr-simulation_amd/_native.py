@@ -108,6 +108,11 @@ def lib():
     L.cdpr_mapping.restype = C.c_uint32
     L.cdpr_plan_kernel.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_char_p, C.c_size_t]
     L.cdpr_kernel_name.argtypes = [H, C.c_char_p, C.c_size_t]
+    # debug exports outside the header (tests): is there an instantiation behind the planned kernel, and where
+    if hasattr(L, "cdpr_debug_plan_entry"):
+        L.cdpr_debug_plan_entry.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
+        L.cdpr_debug_plan_entry_address.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
+        L.cdpr_debug_plan_entry_address.restype = C.c_void_p
     L.cdpr_step_count.argtypes = [H]
     L.cdpr_step_count.restype = C.c_uint64
     L.cdpr_get_joint_states.argtypes = [H, fp, fp, fp]

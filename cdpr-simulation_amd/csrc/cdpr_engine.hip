@@ -384,6 +384,7 @@ int checked(cdpr_engine* h, int rc) { return rc != CDPR_OK ? rc : check_fault(h)
 // per-robot rows; then the path's own set-up (build_f64, build_general), the home state and the warm launch.
 static int build_handle(cdpr_engine* h) {
   const cdpr_config_t& cfg = h->cfg;
+  if (int rc = refuse_missing(h, missing_entry(h->plan))) return rc;  // (before anything is allocated: every kernel this plan can name has an instantiation)
   h->n = cfg.n_cables;
   h->batch = (uint32_t)cfg.batch;
   h->stride = (h->batch + 63u) & ~63u;
@@ -695,6 +696,16 @@ static int copy_name(const std::string& text, char* name, size_t len) {
   return CDPR_OK;
 }
 
+static LaunchShape shape_of_flags(int steps_per_launch, uint32_t flags) {
+  LaunchShape s;
+  s.steps = steps_per_launch;
+  s.first_world = (flags & CDPR_PLAN_FIRST_WORLD_STEP) != 0u;
+  s.scheduled = (flags & CDPR_PLAN_SCHEDULED) != 0u;
+  s.rollout = (flags & CDPR_PLAN_ROLLOUT) != 0u;
+  s.steady = (flags & CDPR_PLAN_NOT_STEADY) == 0u;
+  return s;
+}
+
 int cdpr_plan_kernel(const cdpr_config_t* cfg, int steps_per_launch, uint32_t flags, char* name, size_t len) {
   if (!cfg || !name || len == 0 || steps_per_launch < 1) return CDPR_ERR_INVALID;
   const KernelPlan plan = plan_kernels(*cfg);  // (no HIP call: works on a box without a GPU)
@@ -702,18 +713,29 @@ int cdpr_plan_kernel(const cdpr_config_t* cfg, int steps_per_launch, uint32_t fl
     copy_name(plan.error, name, len);
     return plan.rc;
   }
-  LaunchShape s;
-  s.steps = steps_per_launch;
-  s.first_world = (flags & CDPR_PLAN_FIRST_WORLD_STEP) != 0u;
-  s.scheduled = (flags & CDPR_PLAN_SCHEDULED) != 0u;
-  s.rollout = (flags & CDPR_PLAN_ROLLOUT) != 0u;
-  s.steady = (flags & CDPR_PLAN_NOT_STEADY) == 0u;
-  return copy_name(planned_kernel_name(plan, planned_kernel(plan, s)), name, len);
+  return copy_name(planned_kernel_name(planned_kernel(plan, shape_of_flags(steps_per_launch, flags))), name, len);
+}
+
+// Is there an instantiation behind the kernel cdpr_plan_kernel names for these arguments?  1: yes - in both modes and, where the kernel
+// has one, in its steady-state form too (missing_entry, cdpr_kernels.hpp); 0: a lookup came back empty; the refusal's code where the
+// configuration is refused.  From the configuration alone, no HIP call.  For tests, not part of the C-ABI header.
+int cdpr_debug_plan_entry(const cdpr_config_t* cfg, int steps_per_launch, uint32_t flags) {
+  if (!cfg || steps_per_launch < 1) return CDPR_ERR_INVALID;
+  const KernelPlan plan = plan_kernels(*cfg);
+  if (plan.rc != CDPR_OK) return plan.rc;
+  return missing_entry(plan, shape_of_flags(steps_per_launch, flags)).id == KernelId::None ? 1 : 0;
+}
+// ... and the entry point itself (of the form cdpr_plan_kernel names: Position mode, not the steady-state instantiation), null where
+// there is none or the configuration is refused: two cells run the same code exactly where these are equal
+const void* cdpr_debug_plan_entry_address(const cdpr_config_t* cfg, int steps_per_launch, uint32_t flags) {
+  if (!cfg || steps_per_launch < 1) return nullptr;
+  const KernelPlan plan = plan_kernels(*cfg);
+  return plan.rc != CDPR_OK ? nullptr : entry_address(planned_kernel(plan, shape_of_flags(steps_per_launch, flags)));
 }
 
 int cdpr_kernel_name(cdpr_handle_t h, char* name, size_t len) {
   if (!h) return CDPR_ERR_INVALID;
-  return copy_name(planned_kernel_name(h->plan, h->last_kernel), name, len);
+  return copy_name(planned_kernel_name(h->last_kernel), name, len);
 }
 
 uint32_t cdpr_mapping(cdpr_handle_t h) {
@@ -723,8 +745,8 @@ uint32_t cdpr_mapping(cdpr_handle_t h) {
 uint64_t cdpr_step_count(cdpr_handle_t h) { return h ? h->step : 0; }
 
 // Which instantiation the last step launch of run_steps took: 0 = the planned kernel as cdpr_kernel_name gives it, 1 = the role-split
-// kernel's steady-state controller wave (split_steady_launch).  Host-side state; for tests and A/B scripts, not part of the C-ABI header.
-int cdpr_debug_last_variant(cdpr_handle_t h) { return h ? h->last_variant : -1; }
+// kernel's steady-state instantiation (PlannedKernel::steady of h->last_kernel).  Host-side state; for tests and A/B scripts, not part of the C-ABI header.
+int cdpr_debug_last_variant(cdpr_handle_t h) { return h ? (h->last_kernel.steady ? 1 : 0) : -1; }
 
 #ifdef CDPR_STAMPS
 // diagnostic builds only: point the step kernel at a stamp buffer (uint64[blocks][8]); nullptr disables

@@ -184,24 +184,8 @@ static void f64_mode_args(const cdpr_engine* h, bool vel, bool frc, F64Args& a) 
   }
 }
 
-// the fp64 kernel a planned id stands for on this handle
-static F64Kernel f64_kernel_for(const cdpr_engine* h, const PlannedKernel& q) {
-  const uint32_t n = h->n;
-  const bool pr = h->plan.per_robot, hold_full = h->plan.hold_full;
-  switch (q.id) {
-    case KernelId::F64Split: return pick_f64_split_kernel(n, q.f64_lean);
-    case KernelId::F64SplitHold: return pick_f64_split_hold_kernel(n, q.f64_lean, hold_full);
-    case KernelId::F64Hold: return h->plan.hold_long ? pick_f64_hold_long_kernel(n, false, false) : pick_f64_hold_kernel(n, hold_full);
-    case KernelId::F64HoldPr: return h->plan.hold_long ? pick_f64_hold_long_kernel(n, true, false) : pick_f64_hold_pr_kernel(n, hold_full);
-    case KernelId::F64Tstop: return h->plan.hold_long ? pick_f64_hold_long_kernel(n, pr, true) : pick_f64_tstop_kernel(n, pr, h->plan.hold64 ? (hold_full ? 2 : 1) : 0);
-    case KernelId::F64Long: return pick_f64_long_kernel(n, pr, h->plan.tstop64);
-    case KernelId::F64Pr: return pick_f64_pr_kernel(n, q.f64_ring_lds);
-    default: return pick_f64_kernel(n, q.f64_ring_lds, q.f64_jcache);
-  }
-}
-
 // precision = 64: the same host logic (commands are latched by run_steps before this is reached), the fp64 kernel
-int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, void* record) {
+int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, void* record, const PlannedKernel& pk1, const PlannedKernel& pkk) {
   const uint32_t n = h->n;
   if (reset_pid && !h->plan.hold64) {  // Pid::reset (Pid.cpp:100-115): zero every controller row (hold branch live: the latch reset that Pid's own rows)
     h->pid_calls = 0;
@@ -213,27 +197,12 @@ int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, vo
   const bool vel = pr || h->mode == kModeVelocity, frc = !pr && h->mode == kModeForce;
   f64_mode_args(h, vel, frc, a);
   a.obs_step_stride = record ? (size_t)f64_obs_rows((int)n) * h->stride : 0;  // doubles per observable image
-  // the rings in LDS (64 KiB per wave at n = 8: two waves per CU) while the batch leaves CUs to spare
-  const int ring_env = [] { const char* v = std::getenv("CDPR_F64_RING_LDS"); return v ? atoi(v) : -1; }();  // (read per call: A/B in one process)
-  // ... and the structure-matrix rows too (112 KiB: one wave per CU) up to one workgroup per CU
-  const int jc_env = [] { const char* v = std::getenv("CDPR_F64_JCACHE"); return v ? atoi(v) : -1; }();  // (read per call: A/B in one process)
   a.travel_stop = h->plan.tstop64 ? (int)h->cfg.travel_stop : 0;
-  // one step per launch on FK + TD handles up to one workgroup per CU: estimator wave + controller wave (cdpr_split_kernel_f64)
-  const int sp_env = [] { const char* v = std::getenv("CDPR_F64_SPLIT"); return v ? atoi(v) : -1; }();  // (read per call: A/B in one process)
-  // (CDPR_F64_SPLIT = 0 never, 1 the LDS-cached build, 2 the lean build whatever the batch)
-  // The routing itself: planned_kernel (cdpr_select.hpp) for a one-step and for a several-steps launch of this handle
-  LaunchShape s1 = launch_shape(h, 1), sk = launch_shape(h, 2);
-  s1.f64_ring_lds = sk.f64_ring_lds = ring_env, s1.f64_jcache = sk.f64_jcache = jc_env, s1.f64_split = sk.f64_split = sp_env;
-  const PlannedKernel pk1 = planned_kernel(h->plan, s1), pkk = planned_kernel(h->plan, sk);
-  const bool split1 = pk1.id == KernelId::F64Split || pk1.id == KernelId::F64SplitHold;
-  F64Kernel split_kern = split1 ? f64_kernel_for(h, pk1) : nullptr;  // (per-robot handles: the one-wave kernel)
-  // up to one workgroup per CU the role-split kernel's one-step launches beat the one-wave kernel's multi-step ones
-  // (14.4 against 20.8 us per step at one robot x 8, same bits): a fused update then runs as one-step launches
-  const bool fused_as_single = pkk.id == KernelId::F64Split || pkk.id == KernelId::F64SplitHold;
-  if (fused_as_single) per_launch = 1;
-  PlannedKernel one_wave = pkk;  // the one-wave kernel of this handle (what a several-steps launch runs, or would run)
-  if (fused_as_single) { LaunchShape so = sk; so.f64_split = 0; one_wave = planned_kernel(h->plan, so); }
-  F64Kernel kern = f64_kernel_for(h, one_wave);
+  // The routing: pk1 and pkk, planned_kernel's answers (cdpr_select.hpp) for a one-step and for a several-steps launch of this call
+  // (run_steps made them in front of the latch).  One step per launch on FK + TD handles: estimator wave + controller wave
+  // (cdpr_split_kernel_f64); up to one workgroup per CU its one-step launches beat the one-wave kernel's several-steps ones (14.4
+  // against 20.8 us per step at one robot x 8, same bits): a fused update then runs as one-step launches
+  if (pkk.id == KernelId::F64Split || pkk.id == KernelId::F64SplitHold) per_launch = 1;
   const uint32_t mode_flags = pr ? 0u : (vel ? kFlagActualIsVelocity : (frc ? kFlagForceMode : 0u));
   return run_chain(h, nsteps, per_launch, record, h->d_obs64, [&](ChainStep& s) {
     a.nsteps = s.k;
@@ -243,13 +212,9 @@ int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, vo
     a.ring_slot = ring_slot_of(h->step, win64(h));
     a.step0 = (int)h->step;
     a.publish_mask = s.publish_mask;
-    if (s.k == 1 && split_kern) {
-      hipLaunchKernelGGL(split_kern, dim3((h->batch + 63u) / 64u), dim3(128), 0, h->stream, a);
-      h->last_kernel = pk1;
-    } else {
-      hipLaunchKernelGGL(kern, dim3((h->batch + 63u) / 64u), dim3(64), 0, h->stream, a);
-      h->last_kernel = one_wave;
-    }
+    const PlannedKernel& pk = s.k == 1 ? pk1 : pkk;
+    hipLaunchKernelGGL(f64_entry(pk), dim3(pk.grid(h->batch)), dim3(pk.block), 0, h->stream, a);
+    h->last_kernel = pk;
     HIP_TRY(h, hipGetLastError());
     return (int)CDPR_OK;
   });
@@ -300,7 +265,7 @@ int rollout_enqueue_f64(cdpr_engine* h, int samples, int horizon, const float* d
   LaunchShape shape = launch_shape(h, horizon);  // the handle's one-wave kernel, rings in memory (planned_kernel's rollout rule)
   shape.rollout = true;
   const PlannedKernel pk = planned_kernel(h->plan, shape);
-  F64Kernel kern = f64_kernel_for(h, pk);
+  const F64Kernel kern = f64_entry(pk);
   h->last_kernel = pk;
   a.travel_stop = h->plan.tstop64 ? (int)h->cfg.travel_stop : 0;
   int calls = reset ? 0 : h->pid_calls;  // (uniform handles; per-robot handles count in the meta bytes)
@@ -313,7 +278,7 @@ int rollout_enqueue_f64(cdpr_engine* h, int samples, int horizon, const float* d
     a.pid_calls = sat_pid_calls(calls);
     a.ring_slot = ring_slot_of(h->step + (uint64_t)k, win64(h));
     a.step0 = (int)(h->step + (uint64_t)k);
-    hipLaunchKernelGGL(kern, dim3((uint32_t)((traj + 63u) / 64u)), dim3(64), 0, h->stream, a);
+    hipLaunchKernelGGL(kern, dim3(pk.grid(traj)), dim3(pk.block), 0, h->stream, a);
     calls = sat_pid_calls(calls + (first_world ? 0 : 1));
     Roll64CostArgs q{};
     q.state = h->d_roll64, q.ref = d_ref, q.acc = h->d_roll64_acc, q.out = (k == horizon - 1) ? d_cost : nullptr, q.stride = (uint32_t)h->roll64_cols,

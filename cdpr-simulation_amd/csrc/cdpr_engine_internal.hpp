@@ -259,8 +259,7 @@ struct cdpr_engine {
   DevBuf<float> d_roll_rec;      // MPC rollout on the general path: every trajectory's private copy of the records
   size_t roll_rec_cols = 0;      // columns d_roll_rec can hold
   GraphCache graphs;          // chains of identical steady-state launches (run_steps)
-  PlannedKernel last_kernel;  // what the last step launch ran on (cdpr_kernel_name)
-  int last_variant = 0;       // ... and which instantiation of it (cdpr_debug_last_variant): 1 = the role-split kernel's steady-state controller wave
+  PlannedKernel last_kernel;  // what the last step launch ran on (cdpr_kernel_name; its `steady`: cdpr_debug_last_variant)
   bool split_steady = true;   // CDPR_SPLIT_STEADY=0: the role-split kernel always runs its generic instantiation
   int cus = 256;
   bool use_graphs = true;
@@ -444,9 +443,7 @@ GenCtl general_ctl(const cdpr_engine* h);
 // cdpr_engine_launch.hip
 double sim_time(uint64_t step, double dt);
 LaunchShape launch_shape(const cdpr_engine* h, int k, bool steady = false, const Schedule* sched = nullptr);
-StepKernel step_kernel_of(const cdpr_engine* h, const PlannedKernel& pk);
-StepKernel select_step_kernel(const cdpr_engine* h, int k, bool steady = false);
-uint32_t step_block_threads(const cdpr_engine* h, int k);
+int refuse_missing(cdpr_engine* h, const PlannedKernel& missing);  // CDPR_ERR_UNSUPPORTED "internal: no instantiation for <label>", or CDPR_OK for id None
 int warm_first_launch(cdpr_engine* h);
 uint64_t publish_mask(const cdpr_engine* h, int k, double& last);  // which of the next k world steps publish; `last`: the publish stamp after them
 void advance_clock(cdpr_engine* h, int k, int launches);            // k world steps were queued in `launches` launches
@@ -464,7 +461,7 @@ int ensure_done_scratch(cdpr_engine* h);                                        
 int build_f64(cdpr_engine* h);  // cdpr_create's part of a precision = 64 handle
 size_t state64_rows(const cdpr_engine* h);
 int upload_home64(cdpr_engine* h);
-int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, void* record);  // (its path of the chain; run_steps has latched the commands)
+int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, void* record, const PlannedKernel& pk1, const PlannedKernel& pkk);  // (its path of the chain; run_steps has latched the commands)
 int rollout_enqueue_f64(cdpr_engine* h, int samples, int horizon, const float* d_commands, const float* d_ref, float* d_cost);
 
 // The handle as the kernels that act on chosen robots see it (cdpr_robot_records.hpp), one builder per record layout: the only

@@ -76,40 +76,32 @@ static void set_weight_row(const cdpr_engine* h, StepArgs& a, int slot) {
 }
 
 // The kernel a launch uses: the routing is planned_kernel's (cdpr_select.hpp: a pure function of the handle's plan and the
-// launch's shape, the same one cdpr_plan_kernel answers from without a GPU); here its answer becomes a function pointer.
+// launch's shape, the same one cdpr_plan_kernel answers from without a GPU).  Its answer names one instantiation completely: a
+// launch site reads planned_kernel -> step_entry / gen_entry / f64_entry (cdpr_kernels.hpp) -> launch, grid and block from the answer.
 LaunchShape launch_shape(const cdpr_engine* h, int k, bool steady, const Schedule* sched) {
   LaunchShape s;
   s.steps = k;
   s.first_world = steps_since_load(h) == 0;
   s.scheduled = sched != nullptr;
   s.steady = steady;
+  s.vel = h->mode == kModeVelocity;
+  if (h->plan.fp64) {  // the per-call A/B overrides (read per call: A/B in one process)
+    const auto env_int = [](const char* key) { const char* v = std::getenv(key); return v ? atoi(v) : -1; };
+    s.f64_ring_lds = env_int("CDPR_F64_RING_LDS");  // the rings in LDS (64 KiB per wave at n = 8: two waves per CU) while the batch leaves CUs to spare
+    s.f64_jcache = env_int("CDPR_F64_JCACHE");      // ... and the structure-matrix rows too (112 KiB: one wave per CU) up to one workgroup per CU
+    s.f64_split = env_int("CDPR_F64_SPLIT");        // 0 never, 1 the LDS-cached build, 2 the lean build whatever the batch
+  }
   return s;
 }
-StepKernel step_kernel_of(const cdpr_engine* h, const PlannedKernel& pk) {
-  const uint32_t n = h->n;
-  switch (pk.id) {
-    case KernelId::StepSingle: return pick_step_kernel(true, n, h->plan.fk, h->plan.td);
-    case KernelId::StepMulti: return pick_step_kernel(false, n, h->plan.fk, h->plan.td);
-    case KernelId::Lowreg: return pick_lowreg_kernel(n, h->plan.td);
-    case KernelId::OnestepPersist: return pick_onestep_persist_kernel(n, h->plan.fk, h->plan.td);
-    case KernelId::Split: return pick_split_kernel(n);
-    case KernelId::Onestep: return pick_onestep_kernel(n, h->plan.fk, h->plan.td);
-    case KernelId::PhysStep: return pick_phys_kernel(n, h->plan.fk, h->plan.td, kPhysStep);
-    case KernelId::Rollout: return pick_rollout_kernel(n, h->plan.fk, h->plan.td);
-    case KernelId::PhysRollout: return pick_phys_kernel(n, h->plan.fk, h->plan.td, kPhysRollout);
-    case KernelId::PrSingle: return pick_pr_kernel(true, false, false, n, h->plan.fk, h->plan.td);
-    case KernelId::PrLowreg: return pick_pr_kernel(true, false, true, n, h->plan.fk, h->plan.td);
-    case KernelId::PrSplit: return pick_pr_split_kernel(n);
-    case KernelId::PrMulti: return pick_pr_kernel(false, false, false, n, h->plan.fk, h->plan.td);
-    case KernelId::PrRollout: return pick_pr_kernel(false, true, false, n, h->plan.fk, h->plan.td);
-    case KernelId::PairSingle: return pick_pair_kernel(true, n, h->plan.fk, h->plan.td);
-    case KernelId::PairMulti: return pick_pair_kernel(false, n, h->plan.fk, h->plan.td);
-    case KernelId::PairStream: return pick_pair_stream_kernel(n, h->mode == kModeVelocity);
-    case KernelId::Cable: return pick_cable_kernel(n, h->plan.fk, h->plan.td);
-    default: return nullptr;  // (general path and precision = 64: their own launch functions)
-  }
+// A kernel without an instantiation is refused, not launched (`missing`: missing_entry's answer, id None where nothing is missing).
+// Which kernels a handle's launches can take is a function of its plan alone: cdpr_create asks for every launch shape there is
+// (build_handle) and refuses the handle.  Only precision = 64 reads overrides per call: run_steps asks again for that call's two
+// kernels, in front of the latch.  No configuration gets here today.
+int refuse_missing(cdpr_engine* h, const PlannedKernel& missing) {
+  if (missing.id == KernelId::None) return CDPR_OK;
+  h->err = "internal: no instantiation for " + planned_kernel_name(missing);
+  return CDPR_ERR_UNSUPPORTED;
 }
-StepKernel select_step_kernel(const cdpr_engine* h, int k, bool steady) { return step_kernel_of(h, planned_kernel(h->plan, launch_shape(h, k, steady))); }
 // May a launch of k > 1 world steps with the arguments `a` (flags, pid_calls, pointers set) run on cdpr_pair_stream_kernel?
 // That kernel has no branch for anything but the steady state of a plain handle (cdpr_step_kernel_pair.hpp): every
 // condition below is one the general several-steps kernel tests per step instead (LaunchShape::steady).  CDPR_PAIR_STREAM=0: never (A/B).
@@ -124,14 +116,12 @@ static bool pair_stream_steady(const cdpr_engine* h, const StepArgs& a, const Sc
 static bool split_steady_handle(const cdpr_engine* h) {
   return h->split_steady && !h->plan.per_robot && h->cfg.publish_period == 0.0 && h->cfg.fk_tolerance == 0.0 && h->cfg.fk_max_iterations == 4;
 }
-// May a launch of the role-split kernel with the arguments `a` take it?  The steady kernel has no code for anything the generic one
-// tests per launch and these facts decide: such a handle in Velocity or Position mode, past world step 0, the derivative window full,
-// no `pid` topic, no travel flags.  Same bits either way (tested).
-static bool split_steady_launch(const cdpr_engine* h, const PlannedKernel& pk, const StepArgs& a) {
-  return pk.id == KernelId::Split && split_steady_handle(h) && steps_since_load(h) != 0 && h->mode != kModeForce && a.pid_calls != 0 &&
-         a.pid_calls >= a.nbuf && !a.dbg && !a.travel_on;
+// May a launch of the role-split kernel with the arguments `a` take it (LaunchShape::split_steady; planned_kernel asks it of that kernel
+// only)?  The steady kernel has no code for anything the generic one tests per launch and these facts decide: such a handle in Velocity
+// or Position mode, past world step 0, the derivative window full, no `pid` topic, no travel flags.  Same bits either way (tested).
+static bool split_steady_launch(const cdpr_engine* h, const StepArgs& a) {
+  return split_steady_handle(h) && steps_since_load(h) != 0 && h->mode != kModeForce && a.pid_calls != 0 && a.pid_calls >= a.nbuf && !a.dbg && !a.travel_on;
 }
-uint32_t step_block_threads(const cdpr_engine* h, int k) { return planned_kernel(h->plan, launch_shape(h, k)).block; }
 
 // What every launch over the handle's own state starts from: the constants, the state and observable rows, the `pid` topic's rows, the
 // geometry; with a trajectory record, one observable image per step (the chain points `obs` at the launch's first).
@@ -178,6 +168,7 @@ int warm_first_launch(cdpr_engine* h) {
   if (h->plan.general || h->plan.fp64) return CDPR_OK;
   if (const char* w = std::getenv("CDPR_NO_WARM_LAUNCH"))
     if (w[0] == '1') return CDPR_OK;
+  const PlannedKernel pk = planned_kernel(h->plan, launch_shape(h, 1));
   const uint32_t rows = 64;
   const std::vector<float4> s = home_state(h, rows);
   DevBuf st, ob, cm, mt;
@@ -194,7 +185,7 @@ int warm_first_launch(cdpr_engine* h) {
   a.cmd = cm.as<float>();
   a.dbg = nullptr;
   a.geom = h->d_geom;
-  a.batch = h->plan.lane_cable ? (h->n <= 4 ? 16u : 8u) : h->plan.lane_pair ? 32u : 64u;
+  a.batch = pk.robots_per_block;
   a.stride = rows;
   a.nsteps = 1;
   a.obs_step_stride = 0;
@@ -206,16 +197,18 @@ int warm_first_launch(cdpr_engine* h) {
   a.pid_calls = kCallSat;  // steady state: every branch of the step is taken, as in the launches that follow
   a.ring_slot = 0;
   set_weight_row(h, a, 0);
-  hipLaunchKernelGGL(select_step_kernel(h, 1), dim3(1), dim3(step_block_threads(h, 1)), 0, h->stream, a);
+  hipLaunchKernelGGL(step_entry(pk), dim3(1), dim3(pk.block), 0, h->stream, a);
   HIP_TRY(h, hipGetLastError());
   // ... and of the role-split kernel's steady-state instantiations, which the launches take from the step on that fills the window
   // (split_steady_launch): both modes' - a Joy of the other kind may arrive at any step
-  if (planned_kernel(h->plan, launch_shape(h, 1)).id == KernelId::Split && split_steady_handle(h)) {
-    for (const bool vel : {false, true}) {
-      copy_pid(vel ? h->pid_vel : h->pid_pos, a);
-      hipLaunchKernelGGL(pick_split_steady_kernel(h->n, vel), dim3(1), dim3(128), 0, h->stream, a);
-      HIP_TRY(h, hipGetLastError());
-    }
+  for (const bool vel : {false, true}) {
+    LaunchShape shape = launch_shape(h, 1);
+    shape.split_steady = split_steady_handle(h), shape.vel = vel;
+    const PlannedKernel steady = planned_kernel(h->plan, shape);
+    if (!steady.steady) break;
+    copy_pid(vel ? h->pid_vel : h->pid_pos, a);
+    hipLaunchKernelGGL(step_entry(steady), dim3(1), dim3(steady.block), 0, h->stream, a);
+    HIP_TRY(h, hipGetLastError());
   }
   HIP_TRY(h, wait_stream(h));
   return CDPR_OK;
@@ -224,7 +217,7 @@ int warm_first_launch(cdpr_engine* h) {
 // One step-kernel launch over the whole batch, or (h->plan.chunk) the same launch cut into contiguous blocks of robots issued
 // back to back on the handle's stream: every pointer that is indexed by robot moves to the block's first robot, the row
 // stride stays.  Robots are independent, so the results are bit-identical to the single launch (tested).  Returns the launches queued.
-static int launch_step(cdpr_engine* h, StepKernel kern, uint32_t robots_per_block, dim3 block, const StepArgs& a, uint32_t max_grid = 0) {
+static int launch_step(cdpr_engine* h, StepKernel kern, const PlannedKernel& pk, const StepArgs& a, uint32_t max_grid = 0) {
   const uint32_t B = a.batch;
   const uint32_t chunk = (h->plan.chunk && B > h->plan.chunk) ? h->plan.chunk : B;
   const uint32_t pieces = (B + chunk - 1u) / chunk;
@@ -238,9 +231,9 @@ static int launch_step(cdpr_engine* h, StepKernel kern, uint32_t robots_per_bloc
     if (a.cmd) c.cmd = a.cmd + (size_t)first * h->n;
     if (a.dbg) c.dbg = a.dbg + (size_t)first * CDPR_PID_DEBUG_AXES;
     if (a.meta) c.meta = a.meta + first;
-    uint32_t grid = (c.batch + robots_per_block - 1u) / robots_per_block;
+    uint32_t grid = pk.grid(c.batch);
     if (max_grid && grid > max_grid) grid = max_grid;  // persistent kernel: the waves walk over the blocks
-    hipLaunchKernelGGL(kern, dim3(grid), block, 0, h->stream, c);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(pk.block), 0, h->stream, c);
   }
   return launches;
 }
@@ -350,15 +343,13 @@ static int run_steps_general(cdpr_engine* h, int nsteps, int per_launch, void* r
     // one step per launch on FK + TD handles up to two workgroups per CU: the role-split form (cdpr_general_split.hpp), beyond: the
     // lean role-split kernel (two waves per SIMD; the rare controller paths by call) - planned_kernel, cdpr_select.hpp
     const PlannedKernel pk = planned_kernel(h->plan, launch_shape(h, s.k));
-    const bool gsplit = pk.id == KernelId::GenSplit, glean = pk.id == KernelId::GenLean;
-    GenKernel kern = gsplit ? pick_gen_split11(h->n) : glean ? pick_gen_lean11(h->n) : pick_gen_kernel(h->n, h->plan.fk, h->plan.td, false, h->glay.nb > 11, pk.id == KernelId::GenOne);
     h->last_kernel = pk;
     a.nsteps = s.k;
     a.flags = s.first_flag;
     g.now_step = (int)h->step;
     if (s.record) a.obs = static_cast<float4*>(s.record);
     a.publish_mask = s.publish_mask;
-    hipLaunchKernelGGL(kern, dim3((h->batch + 63u) / 64u), dim3((gsplit || glean) ? 128 : 64), 0, h->stream, a, g);
+    hipLaunchKernelGGL(gen_entry(pk), dim3(pk.grid(h->batch)), dim3(pk.block), 0, h->stream, a, g);
     HIP_TRY(h, hipGetLastError());
     return (int)CDPR_OK;
   });
@@ -378,10 +369,16 @@ int run_steps(cdpr_engine* h, int nsteps, int per_launch, void* record, const Sc
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
 
   if (int rc = general_clock_check(h, (uint64_t)nsteps)) return rc;  // (in front of the latch: a refused update leaves pending commands pending)
+  PlannedKernel f64_kernels[2];  // precision = 64: the kernels of this call's one-step and several-steps launches (its overrides are read per call)
+  if (h->plan.fp64)
+    for (int i = 0; i < 2; ++i) {
+      f64_kernels[i] = planned_kernel(h->plan, launch_shape(h, i + 1));
+      if (!f64_entry(f64_kernels[i])) return refuse_missing(h, f64_kernels[i]);
+    }
   bool reset_pid = false;
   if (int rc = latch_pending(h, reset_pid)) return rc;
   if (h->plan.general) return run_steps_general(h, nsteps, per_launch, record);
-  if (h->plan.fp64) return run_steps_f64(h, nsteps, per_launch, reset_pid, record);
+  if (h->plan.fp64) return run_steps_f64(h, nsteps, per_launch, reset_pid, record, f64_kernels[0], f64_kernels[1]);
 
   if (reset_pid) {  // Pid::reset (Pid.cpp:100-115): zero every controller record; rare, so done outside the step kernel
     h->pid_calls = 0;
@@ -390,8 +387,6 @@ int run_steps(cdpr_engine* h, int nsteps, int per_launch, void* record, const Sc
   }
   StepArgs a = fast_path_args(h, record, sched);
   const uint32_t mode_flags = a.flags;
-  const uint32_t robots_per_block = h->plan.lane_cable ? (h->n <= 4 ? 16u : 8u) : h->plan.lane_pair ? 32u : 64u;
-  const dim3 grid((h->batch + robots_per_block - 1u) / robots_per_block);
 
   return run_chain(h, nsteps, per_launch, record, h->d_obs, [&](ChainStep& s) {
     const int k = s.k;
@@ -403,11 +398,10 @@ int run_steps(cdpr_engine* h, int nsteps, int per_launch, void* record, const Sc
     a.ring_slot = ring_slot_of(h->step);
     // a launch over a command schedule always runs on the several-steps kernel, even for one step: only that one reads the
     // schedule, its mailbox and kFlagPublishAll
-    const PlannedKernel pk = planned_kernel(h->plan, launch_shape(h, sched ? std::max(k, 2) : k, pair_stream_steady(h, a, sched), sched));
-    StepKernel kern = step_kernel_of(h, pk);
-    // the role-split kernel keeps its identity (pk, cdpr_kernel_name) whichever instantiation of its controller wave a launch takes
-    h->last_variant = split_steady_launch(h, pk, a) ? 1 : 0;
-    if (h->last_variant) kern = pick_split_steady_kernel(h->n, h->mode == kModeVelocity);
+    LaunchShape shape = launch_shape(h, sched ? std::max(k, 2) : k, pair_stream_steady(h, a, sched), sched);
+    shape.split_steady = split_steady_launch(h, a);
+    const PlannedKernel pk = planned_kernel(h->plan, shape);
+    const StepKernel kern = step_entry(pk);
     h->last_kernel = pk;
     // steady state of a plain lane-pair handle: the branch-free several-steps kernel, which reads the weights by AGE from row 0
     const bool stream = pk.id == KernelId::PairStream;
@@ -433,7 +427,7 @@ int run_steps(cdpr_engine* h, int nsteps, int per_launch, void* record, const Sc
             StepArgs aj = a;  // each node carries its own ring position
             aj.ring_slot = (a.ring_slot + j * k) % kWin;
             set_weight_row(h, aj, stream ? 0 : aj.ring_slot);
-            hipLaunchKernelGGL(kern, grid, dim3(pk.block), 0, h->stream, aj);
+            hipLaunchKernelGGL(kern, dim3(pk.grid(h->batch)), dim3(pk.block), 0, h->stream, aj);
             launched = launched && (hipGetLastError() == hipSuccess);
           }
           return launched;
@@ -445,7 +439,7 @@ int run_steps(cdpr_engine* h, int nsteps, int per_launch, void* record, const Sc
       }
       h->use_graphs = false;  // ... and this chunk, like every later one, is launched eagerly
     }
-    s.launches = launch_step(h, kern, robots_per_block, dim3(pk.block), a, (h->plan.persist && k == 1 && !h->plan.per_robot) ? h->persist_grid : 0u);
+    s.launches = launch_step(h, kern, pk, a, pk.persist ? h->persist_grid : 0u);
     HIP_TRY(h, hipGetLastError());
     return (int)CDPR_OK;
   });

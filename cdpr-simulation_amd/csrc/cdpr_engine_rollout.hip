@@ -39,12 +39,12 @@ static int rollout_enqueue(cdpr_engine* h, int samples, int horizon, const float
     g.rstride = (uint32_t)h->roll_rec_cols;
     g.rec_bytes = (uint32_t)h->glay.bytes(h->roll_rec_cols);
     g.now_step = (int)h->step;
-    GenKernel kern = pick_gen_kernel(h->n, h->plan.fk, h->plan.td, true, h->glay.nb > 11, false);
-    hipLaunchKernelGGL(kern, dim3((uint32_t)((traj + 63u) / 64u)), dim3(64), 0, h->stream, a, g);
-    HIP_TRY(h, hipGetLastError());
     LaunchShape rs = launch_shape(h, horizon);
     rs.rollout = true;
-    h->last_kernel = planned_kernel(h->plan, rs);
+    const PlannedKernel pk = planned_kernel(h->plan, rs);
+    hipLaunchKernelGGL(gen_entry(pk), dim3(pk.grid(traj)), dim3(pk.block), 0, h->stream, a, g);
+    HIP_TRY(h, hipGetLastError());
+    h->last_kernel = pk;
     ++h->launches;
     return CDPR_OK;
   }
@@ -78,8 +78,7 @@ static int rollout_enqueue(cdpr_engine* h, int samples, int horizon, const float
   LaunchShape rs = launch_shape(h, horizon);
   rs.rollout = true;
   const PlannedKernel pk = planned_kernel(h->plan, rs);
-  StepKernel kern = step_kernel_of(h, pk);
-  hipLaunchKernelGGL(kern, dim3((uint32_t)((traj + 63u) / 64u)), dim3(64), 0, h->stream, a);
+  hipLaunchKernelGGL(step_entry(pk), dim3(pk.grid(traj)), dim3(pk.block), 0, h->stream, a);
   HIP_TRY(h, hipGetLastError());
   h->last_kernel = pk;
   ++h->launches;

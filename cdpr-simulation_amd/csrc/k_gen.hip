@@ -1,14 +1,17 @@
-// picks among the general-path kernel families (each instantiated in a translation unit of its own: k_gen_*.hip)
+// cdpr_gen_step_kernel<N, FK, TD, ROLLOUT, NBMAX, SINGLE>: the one-wave general-path kernel is instantiated in five translation
+// units (k_gen_one / _step / _roll / _step32 / _roll32.hip, one per (ROLLOUT, NBMAX, SINGLE) it exists in); this picks the unit
 #include "cdpr_kernels.hpp"
 namespace cdpr {
-GenKernel pick_gen_one11(uint32_t n, bool fk, bool td);
-GenKernel pick_gen_step11(uint32_t n, bool fk, bool td);
-GenKernel pick_gen_roll11(uint32_t n, bool fk, bool td);
-GenKernel pick_gen_step32(uint32_t n, bool fk, bool td);
-GenKernel pick_gen_roll32(uint32_t n, bool fk, bool td);
-GenKernel pick_gen_kernel(uint32_t n, bool fk, bool td, bool rollout, bool long_window, bool single) {
-  if (long_window) return rollout ? pick_gen_roll32(n, fk, td) : pick_gen_step32(n, fk, td);
-  if (rollout) return pick_gen_roll11(n, fk, td);
-  return single ? pick_gen_one11(n, fk, td) : pick_gen_step11(n, fk, td);
+GenKernel gen_one11_entry(const PlannedKernel& k);
+GenKernel gen_step11_entry(const PlannedKernel& k);
+GenKernel gen_roll11_entry(const PlannedKernel& k);
+GenKernel gen_step32_entry(const PlannedKernel& k);
+GenKernel gen_roll32_entry(const PlannedKernel& k);
+GenKernel gen_step_kernel_entry(const PlannedKernel& k) {
+  if (k.rollout && k.single) return nullptr;
+  if (k.nbmax == kGenMaxBuf) return k.rollout ? gen_roll32_entry(k) : k.single ? nullptr : gen_step32_entry(k);  // (long windows: no one-step build)
+  if (k.nbmax != 11) return nullptr;
+  if (k.rollout) return gen_roll11_entry(k);
+  return k.single ? gen_one11_entry(k) : gen_step11_entry(k);
 }
 }  // namespace cdpr

@@ -3,8 +3,12 @@
 #include "cdpr_general_step.hpp"
 namespace cdpr {
 namespace {
+// cdpr_gen_step_kernel<N, FK, TD, ROLLOUT, NBMAX, SINGLE>
 #define K_GEN(N, FK, TD) cdpr_gen_step_kernel<N, FK, TD, true, 11, false>
 template <int N> GenKernel gen_n(bool fk, bool td) { CDPR_PICK_STAGES(N, K_GEN); }
 }  // namespace
-GenKernel pick_gen_roll11(uint32_t n, bool fk, bool td) { CDPR_PICK_CABLES(gen_n, fk, td); }
+GenKernel gen_roll11_entry(const PlannedKernel& k) {
+  const uint32_t n = k.n;
+  CDPR_PICK_CABLES(gen_n, k.fk, k.td);
+}
 }  // namespace cdpr

@@ -3,36 +3,40 @@
 #include "cdpr_onestep_kernel.hpp"
 namespace cdpr {
 namespace {
-#define K_ONE(N, FK, TD) cdpr_onestep_kernel<N, FK, TD>
+// cdpr_onestep_kernel<N, FK, TD, PERSIST>; PERSIST: one wave per SIMD walking over blocks of 64 robots
+#define K_ONE(N, FK, TD) cdpr_onestep_kernel<N, FK, TD, false>
 #define K_ONE_PERSIST(N, FK, TD) cdpr_onestep_kernel<N, FK, TD, true>
 template <int N> StepKernel one_n(bool fk, bool td) { CDPR_PICK_STAGES(N, K_ONE); }
 template <int N> StepKernel one_persist_n(bool fk, bool td) { CDPR_PICK_STAGES(N, K_ONE_PERSIST); }
 }  // namespace
-StepKernel pick_onestep_kernel(uint32_t n, bool fk, bool td) { CDPR_PICK_CABLES(one_n, fk, td); }
-StepKernel pick_onestep_persist_kernel(uint32_t n, bool fk, bool td) { CDPR_PICK_CABLES(one_persist_n, fk, td); }
-StepKernel pick_split_kernel(uint32_t n) {
-  switch (n) {
-    case 6: return cdpr_split_kernel<6>;
-    case 7: return cdpr_split_kernel<7>;
-    case 8: return cdpr_split_kernel<8>;
+StepKernel onestep_kernel_entry(const PlannedKernel& k) {
+  const uint32_t n = k.n;
+  if (!k.single || k.per_robot) return nullptr;
+  if (!k.persist) {
+    CDPR_PICK_CABLES(one_n, k.fk, k.td);
   }
-  return nullptr;
+  CDPR_PICK_CABLES(one_persist_n, k.fk, k.td);
 }
-// the role-split kernel with the controller wave's steady-state instantiation (cdpr_split_steady_kernel<N, VEL>)
-StepKernel pick_split_steady_kernel(uint32_t n, bool vel) {
-  switch (n) {
-    case 6: return vel ? cdpr_split_steady_kernel<6, true> : cdpr_split_steady_kernel<6, false>;
-    case 7: return vel ? cdpr_split_steady_kernel<7, true> : cdpr_split_steady_kernel<7, false>;
-    case 8: return vel ? cdpr_split_steady_kernel<8, true> : cdpr_split_steady_kernel<8, false>;
+// The role-split kernels, six to eight cables (FK + TD handles): cdpr_split_kernel<N, PR> and, for a uniform handle's steady-state
+// launches, the same kernel with both waves' steady-state instantiations, cdpr_split_steady_kernel<N, VEL>
+#define CDPR_PICK_SPLIT(K)  \
+  switch (k.n) {            \
+    case 6: return K(6);    \
+    case 7: return K(7);    \
+    case 8: return K(8);    \
+  }                         \
+  return nullptr
+#define K_SPLIT(N) cdpr_split_kernel<N, false>
+#define K_SPLIT_STEADY(N) (k.vel ? cdpr_split_steady_kernel<N, true> : cdpr_split_steady_kernel<N, false>)
+#define K_SPLIT_PR(N) cdpr_split_kernel<N, true>
+StepKernel split_kernel_entry(const PlannedKernel& k) {
+  if (!k.per_robot && !k.steady) {
+    CDPR_PICK_SPLIT(K_SPLIT);
   }
-  return nullptr;
-}
-StepKernel pick_pr_split_kernel(uint32_t n) {
-  switch (n) {
-    case 6: return cdpr_split_kernel<6, true>;
-    case 7: return cdpr_split_kernel<7, true>;
-    case 8: return cdpr_split_kernel<8, true>;
+  if (!k.per_robot) {
+    CDPR_PICK_SPLIT(K_SPLIT_STEADY);
   }
-  return nullptr;
+  if (k.steady) return nullptr;
+  CDPR_PICK_SPLIT(K_SPLIT_PR);
 }
 }  // namespace cdpr

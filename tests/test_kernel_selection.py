@@ -4,8 +4,10 @@ pure functions of the configuration, exposed without a GPU through cdpr_plan_ker
   x handle {uniform, per-robot, general (hold branch live), precision = 64} x launch {1 step, 10 steps, MPC rollout}
 (FK / TD from six cables on; a refused combination is pinned as its return code and reason) is pinned to the kernel name in tests/golden/kernel_selection.json (regenerate: python tests/test_kernel_selection.py --write,
 and review the diff: a changed cell is a changed routing decision).  The engine takes its kernels from the same function
-(cdpr_engine.hip, cdpr_engine_f64.hip: planned_kernel -> step_kernel_of), and tests/test_gpu_full_size.py checks on the GPU that the kernel a
-handle really launched (cdpr_kernel_name) is the planned one."""
+(planned_kernel names one instantiation; its label and its entry point are read from that descriptor alone, csrc/cdpr_kernels.hpp), and
+tests/test_gpu_full_size.py checks on the GPU that the kernel a handle really launched (cdpr_kernel_name) is the planned one.  Whether
+an instantiation stands behind every cell, and a different one exactly where the name differs, is checked here without a GPU
+(cdpr_debug_plan_entry)."""
 import ctypes as C
 import json
 import os
@@ -38,8 +40,16 @@ def plan(pkg, cfg, steps=1, flags=0):
     return rc, buf.value.decode()
 
 
-def table(pkg):
-    out = {}
+def plan_entry(cfg, steps=1, flags=0):
+    """(1 = an instantiation behind every variant of the planned kernel | 0 | the refusal's code, the entry point's address)."""
+    from cdpr_simulation_amd._native import lib
+
+    s = cfg.to_struct()
+    return lib().cdpr_debug_plan_entry(C.byref(s), steps, flags), lib().cdpr_debug_plan_entry_address(C.byref(s), steps, flags)
+
+
+def cells(pkg):
+    """(cell name, Config, steps per launch, flags) of the matrix."""
     for n in CABLES:
         for sname, stages in STAGES.items():
             if stages and n < 6:
@@ -54,8 +64,14 @@ def table(pkg):
                     elif handle == "fp64":
                         kw["precision"] = 64
                     for steps, flags, cell in ((1, 0, "k1"), (10, 0, "k10"), (10, ROLLOUT, "rollout")):
-                        rc, name = plan(pkg, pkg.Config(**kw), steps, flags)
-                        out[f"n{n} {sname} b{batch} {handle} {cell}"] = name if rc == 0 else f"rc {rc}: {name}"
+                        yield f"n{n} {sname} b{batch} {handle} {cell}", pkg.Config(**kw), steps, flags
+
+
+def table(pkg):
+    out = {}
+    for key, cfg, steps, flags in cells(pkg):
+        rc, name = plan(pkg, cfg, steps, flags)
+        out[key] = name if rc == 0 else f"rc {rc}: {name}"
     return out
 
 
@@ -81,6 +97,41 @@ def test_auto_routing_table_is_pinned(pkg, clean_env):
     assert got["n8 none b1 fp64 k10"] == "cdpr_step_kernel_f64<8, RING_LDS, JCACHE>" and got["n8 none b1 fp64 rollout"] == "cdpr_step_kernel_f64<8>"
     assert got["n8 fk+td b4096 uniform rollout"] == "cdpr_step_kernel<8, true, true, ROLLOUT>"  # config 5
     assert got["n12 none b1 general k1"].startswith("rc -3: more than 8 cables")  # (refused by name, not served by another path)
+
+
+def test_every_selectable_cell_has_a_kernel(pkg, clean_env):
+    """Every cell the golden names a kernel for has an instantiation behind it - in both modes and, for the role-split kernel, in its
+    steady-state form (cdpr_debug_plan_entry tries them) - and a refused cell is refused with the golden's code.  Over the matrix a
+    kernel name and an entry point stand for each other: two cells share the entry exactly where they share the name."""
+    want = json.load(open(GOLDEN))
+    by_name, by_entry, entry_of = {}, {}, {}
+    for key, cfg, steps, flags in cells(pkg):
+        ok, address = plan_entry(cfg, steps, flags)
+        if want[key].startswith("rc "):
+            assert ok == int(want[key][3:].split(":")[0]) and not address, (key, ok)
+            continue
+        assert ok == 1 and address, (key, want[key], ok)
+        by_name.setdefault(want[key], set()).add(address)
+        by_entry.setdefault(address, set()).add(want[key])
+        entry_of[key] = address
+    assert all(len(v) == 1 for v in by_name.values()), [k for k, v in by_name.items() if len(v) != 1]
+    assert all(len(v) == 1 for v in by_entry.values()), [v for v in by_entry.values() if len(v) != 1]
+    assert len(by_name) > 150  # (the matrix reaches that many instantiations)
+    # only the batch differs, within one regime: the same code
+    assert entry_of["n8 fk+td b4096 uniform k1"] == entry_of["n8 fk+td b65536 uniform k1"]      # the role-split kernel
+    assert entry_of["n8 fk+td b1 fp64 k1"] == entry_of["n8 fk+td b4096 fp64 k1"]                # cdpr_split_kernel_f64<8>
+    assert entry_of["n8 fk+td b1 general k1"] == entry_of["n8 fk+td b32768 general k1"]         # cdpr_gen_split_kernel<8>
+    assert entry_of["n4 none b1 uniform k10"] == entry_of["n4 none b65536 uniform k10"]         # cdpr_pair_stream_kernel<4>
+    # ... and where the name differs, so does the code: across a routing threshold, the launch form, the stages, the cable count
+    assert entry_of["n8 fk+td b65536 uniform k1"] != entry_of["n8 fk+td b131072 uniform k1"]    # role-split -> LOWREG
+    assert entry_of["n8 fk+td b4096 fp64 k1"] != entry_of["n8 fk+td b65536 fp64 k1"]            # -> LEAN
+    assert entry_of["n8 fk+td b32768 general k1"] != entry_of["n8 fk+td b65536 general k1"]     # role-split -> lean
+    assert entry_of["n8 fk+td b65536 uniform k1"] != entry_of["n8 fk+td b65536 uniform k10"] != entry_of["n8 fk+td b65536 uniform rollout"]
+    assert entry_of["n8 fk b65536 uniform k1"] != entry_of["n8 fk+td b65536 uniform k1"] != entry_of["n7 fk+td b65536 uniform k1"]
+    assert entry_of["n8 fk+td b65536 uniform k1"] != entry_of["n8 fk+td b65536 per_robot k1"]   # <8, false> / <8, true>
+    # the per-launch variants that share a name are instantiations of their own
+    c2 = pkg.Config(batch=4096)
+    assert plan_entry(c2, 10, NOT_STEADY)[1] != plan_entry(c2, 10)[1] and plan_entry(c2, 10, FIRST)[1] == plan_entry(c2, 10, NOT_STEADY)[1]
 
 
 def test_launch_flags_and_overrides(pkg, clean_env, monkeypatch):
