@@ -165,3 +165,39 @@ class ResampleSpec(C.Structure):
 
     def __init__(self, group_size=0, ess_gate=2.0, flags=0):
         super().__init__(C.sizeof(ResampleSpec), int(group_size), float(ess_gate), int(flags))
+
+
+MPPI_NOMINAL_FIRST, MPPI_CLAMP, MPPI_SHIFT = 1, 2, 4  # cdpr_mppi_spec_t.flags
+MPPI_STATUS = 3  # cdpr_mppi_update_device's d_status: [robots updated, robots degenerate, bad costs]
+
+
+class MppiSpec(C.Structure):
+    """cdpr_mppi_spec_t: what Engine.mppi_sample[_device] and Engine.mppi_update[_device] compute.  samples S and horizon H shape the
+    command batch float[B][H][S][n]; sigma scales the noise, cmd_min / cmd_max bound the commands under MPPI_CLAMP, temperature divides
+    the cost differences of the update; (seed_lo, seed_hi) is the Philox key and robot_offset the global index of the handle's robot 0
+    (a shard of a larger batch).  struct_size is filled in."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("samples", C.c_uint32),
+        ("horizon", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("sigma", C.c_float),
+        ("cmd_min", C.c_float),
+        ("cmd_max", C.c_float),
+        ("temperature", C.c_float),
+        ("seed_lo", C.c_uint32),
+        ("seed_hi", C.c_uint32),
+        ("robot_offset", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+    def __init__(self, samples=1, horizon=1, flags=0, sigma=0.0, cmd_min=0.0, cmd_max=0.0, temperature=1.0, seed=0, robot_offset=0):
+        super().__init__(C.sizeof(MppiSpec), int(samples), int(horizon), int(flags), float(sigma), float(cmd_min), float(cmd_max), float(temperature),
+                         int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF, int(robot_offset) & 0xFFFFFFFF, 0)
+
+    def with_offset(self, robot_offset):
+        """a copy whose robot 0 has the global index robot_offset more (modulo 2^32): the spec of a shard"""
+        s = MppiSpec.from_buffer_copy(self)
+        s.robot_offset = (self.robot_offset + int(robot_offset)) & 0xFFFFFFFF
+        return s

@@ -19,6 +19,7 @@ EXPORTS = [
     "cdpr_done_rule_size", "cdpr_evaluate_done_device", "cdpr_evaluate_done", "cdpr_reset_done_device", "cdpr_get_episode_start",
     "cdpr_env_spec_size", "cdpr_observation_width", "cdpr_observe_device", "cdpr_env_evaluate_device",
     "cdpr_copy_robots", "cdpr_copy_robots_device", "cdpr_resample_spec_size", "cdpr_resample_map_device", "cdpr_resample_device",
+    "cdpr_mppi_spec_size", "cdpr_mppi_sample_device", "cdpr_mppi_update_device",
     "cdpr_set_velocity_command", "cdpr_set_position_command", "cdpr_set_velocity_command_device",
     "cdpr_set_position_command_device", "cdpr_bind_velocity_command_device", "cdpr_bind_position_command_device",
     "cdpr_set_velocity_command_masked", "cdpr_set_position_command_masked", "cdpr_set_force_command", "cdpr_set_force_command_device",
@@ -88,6 +89,11 @@ def lib():
         L.cdpr_resample_spec_size.restype = C.c_size_t
         for name in ("cdpr_resample_map_device", "cdpr_resample_device"):
             getattr(L, name).argtypes = [H, C.POINTER(_abi.ResampleSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    # ... and MPPI around the rollout: the sampler of the command batch and the update of the plan
+    if hasattr(L, "cdpr_mppi_spec_size"):
+        L.cdpr_mppi_spec_size.restype = C.c_size_t
+        L.cdpr_mppi_sample_device.argtypes = [H, C.POINTER(_abi.MppiSpec), C.c_uint32, C.c_void_p, C.c_void_p]
+        L.cdpr_mppi_update_device.argtypes = [H, C.POINTER(_abi.MppiSpec)] + [C.c_void_p] * 7
     for name in ("cdpr_set_velocity_command", "cdpr_set_position_command", "cdpr_set_force_command"):
         getattr(L, name).argtypes = [H, fp, C.c_size_t]
     for name in ("cdpr_set_velocity_command_device", "cdpr_set_position_command_device", "cdpr_bind_velocity_command_device",
@@ -149,5 +155,7 @@ def lib():
         raise ImportError("cdpr_env_spec_t layout mismatch between include/cdpr.h and _abi.py")
     if hasattr(L, "cdpr_resample_spec_size") and L.cdpr_resample_spec_size() != C.sizeof(_abi.ResampleSpec):
         raise ImportError("cdpr_resample_spec_t layout mismatch between include/cdpr.h and _abi.py")
+    if hasattr(L, "cdpr_mppi_spec_size") and L.cdpr_mppi_spec_size() != C.sizeof(_abi.MppiSpec):
+        raise ImportError("cdpr_mppi_spec_t layout mismatch between include/cdpr.h and _abi.py")
     _lib = L
     return L

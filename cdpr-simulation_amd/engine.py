@@ -171,6 +171,57 @@ class Engine:
 
         return self._with_scratch([4 * self.B, None if u is None else 4 * G, 4 * self.B, 4 * G, 4 * _abi.RESAMPLE_STATUS], body)
 
+    # -- MPPI around the rollout: the command batch from the plan, the costs into the next plan, on the device
+    def mppi_sample_device(self, spec: _abi.MppiSpec, iteration: int, d_nominal: int, d_commands: int) -> None:
+        """The perturbed command batch float[B][H][S][n] rollout_velocity_device reads, from the nominal plan float[B][H][n]
+        (cdpr_mppi_sample_device): Philox normals scaled by spec.sigma around every nominal command, clamped under MPPI_CLAMP, sample 0
+        the nominal itself under MPPI_NOMINAL_FIRST.  Device buffers; queued on the engine's stream, nothing copied or waited for."""
+        vp = lambda x: C.c_void_p(x) if x else None  # noqa: E731
+        self._check(lib().cdpr_mppi_sample_device(self._h, C.byref(spec), int(iteration) & 0xFFFFFFFF, vp(d_nominal), vp(d_commands)))
+
+    def mppi_update_device(self, spec: _abi.MppiSpec, d_cost: int, d_commands: int, d_nominal: int, d_action: int = 0, d_weights: int = 0,
+                           d_ess: int = 0, d_status: int = 0) -> None:
+        """The rollout's costs float[B][S] folded into the plan (cdpr_mppi_update_device): d_nominal float[B][H][n] becomes the
+        exp(-(c - c_min) / temperature)-weighted mean of the commands (moved one step on under MPPI_SHIFT), d_action float[B][n] its
+        first row - what set_velocity_command_device takes; d_weights float[B][S], d_ess float[B], d_status uint32[_abi.MPPI_STATUS]; 0 =
+        not wanted.  Queued on the engine's stream, nothing copied or waited for."""
+        vp = lambda x: C.c_void_p(x) if x else None  # noqa: E731
+        self._check(lib().cdpr_mppi_update_device(self._h, C.byref(spec), vp(d_cost), vp(d_commands), vp(d_nominal), vp(d_action), vp(d_weights),
+                                                  vp(d_ess), vp(d_status)))
+
+    def mppi_sample(self, nominal, spec: _abi.MppiSpec, iteration: int) -> np.ndarray:
+        """commands float32[B, H, S, n] on the host: the nominal plan [B, H, n] goes up, mppi_sample_device runs into a scratch buffer, the
+        batch comes down."""
+        H, S = int(spec.horizon), int(spec.samples)
+        u = np.ascontiguousarray(nominal, dtype=np.float32).reshape(self.B, H, self.n)
+
+        def body(ptrs):
+            self.device_upload_into(ptrs[0], u)
+            self.mppi_sample_device(spec, iteration, ptrs[0], ptrs[1])
+            return self.device_download(ptrs[1], (self.B, H, S, self.n), np.float32)
+
+        return self._with_scratch([u.nbytes, 4 * self.B * H * S * self.n], body)
+
+    def mppi_update(self, cost, commands, nominal, spec: _abi.MppiSpec):
+        """(nominal float32[B, H, n], action float32[B, n], weights float32[B, S], ess float32[B], status uint32[_abi.MPPI_STATUS]) on the
+        host: cost [B, S], commands [B, H, S, n] and the nominal plan go up, mppi_update_device runs on scratch buffers, the results come
+        down."""
+        H, S = int(spec.horizon), int(spec.samples)
+        c = np.ascontiguousarray(cost, dtype=np.float32).reshape(self.B, S)
+        v = np.ascontiguousarray(commands, dtype=np.float32).reshape(self.B, H, S, self.n)
+        u = np.ascontiguousarray(nominal, dtype=np.float32).reshape(self.B, H, self.n)
+
+        def body(ptrs):
+            d_c, d_v, d_u, d_action, d_w, d_ess, d_status = ptrs
+            for d, a in ((d_c, c), (d_v, v), (d_u, u)):
+                self.device_upload_into(d, a)
+            self.mppi_update_device(spec, d_c, d_v, d_u, d_action, d_w, d_ess, d_status)
+            return (self.device_download(d_u, (self.B, H, self.n), np.float32), self.device_download(d_action, (self.B, self.n), np.float32),
+                    self.device_download(d_w, (self.B, S), np.float32), self.device_download(d_ess, self.B, np.float32),
+                    self.device_download(d_status, _abi.MPPI_STATUS, np.uint32))
+
+        return self._with_scratch([c.nbytes, v.nbytes, u.nbytes, 4 * self.B * self.n, c.nbytes, 4 * self.B, 4 * _abi.MPPI_STATUS], body)
+
     # -- done rules: who should be put back, decided on the device
     @staticmethod
     def _rule(rule):

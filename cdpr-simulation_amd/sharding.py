@@ -113,6 +113,26 @@ class ShardedEngine:
         source = np.concatenate([np.where(p[0] >= 0, p[0] + lo, -1).astype(np.int32) for p, (lo, _) in zip(parts, self.spans)])
         return source, np.concatenate([p[1] for p in parts]), np.sum([p[2] for p in parts], axis=0, dtype=np.uint32)
 
+    def mppi_sample(self, nominal, spec, iteration):
+        """Engine.mppi_sample over the shards: the plan split by shard_range, every shard's spec with robot_offset moved on by its first
+        robot, so the batch is to the bit what one engine of the whole batch writes."""
+        import numpy as np
+
+        u = np.asarray(nominal, dtype=np.float32).reshape(self.B, int(spec.horizon), self.n)
+        return np.concatenate([e.mppi_sample(u[lo:hi], spec.with_offset(lo), iteration) for e, (lo, hi) in zip(self.engines, self.spans)])
+
+    def mppi_update(self, cost, commands, nominal, spec):
+        """Engine.mppi_update over the shards (the update is per robot): rows split by shard_range, plan, action, weights and ess
+        concatenated in shard order, status summed."""
+        import numpy as np
+
+        H, S = int(spec.horizon), int(spec.samples)
+        c = np.asarray(cost, dtype=np.float32).reshape(self.B, S)
+        v = np.asarray(commands, dtype=np.float32).reshape(self.B, H, S, self.n)
+        u = np.asarray(nominal, dtype=np.float32).reshape(self.B, H, self.n)
+        parts = [e.mppi_update(c[lo:hi], v[lo:hi], u[lo:hi], spec) for e, (lo, hi) in zip(self.engines, self.spans)]
+        return tuple(np.concatenate([p[k] for p in parts]) for k in range(4)) + (np.sum([p[4] for p in parts], axis=0, dtype=np.uint32),)
+
     def evaluate_done(self, rule):
         """Engine.evaluate_done over the shards: masks and reasons concatenated in shard_range order, counts summed."""
         import numpy as np

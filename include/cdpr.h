@@ -39,7 +39,8 @@ extern "C" {
 /* The environment view (cdpr_env_spec_t, cdpr_env_spec_size, cdpr_observation_width, cdpr_observe_device, cdpr_env_evaluate_device) came
  * after 8 as new exports only: no struct or call that existed changed, so the number stays 8.  A caller discovers the feature by those
  * symbols and checks its cdpr_env_spec_t against cdpr_env_spec_size().  So did the fork (cdpr_copy_robots*) and the resampler
- * (cdpr_resample_spec_t, cdpr_resample_spec_size, cdpr_resample_map_device, cdpr_resample_device). */
+ * (cdpr_resample_spec_t, cdpr_resample_spec_size, cdpr_resample_map_device, cdpr_resample_device) and MPPI (cdpr_mppi_spec_t, cdpr_mppi_spec_size, cdpr_mppi_sample_device,
+ * cdpr_mppi_update_device). */
 #define CDPR_ABI_VERSION 8u   /* 8 = 7 + cdpr_done_rule_t, cdpr_evaluate_done, cdpr_evaluate_done_device, cdpr_reset_done_device, cdpr_get_episode_start, cdpr_done_rule_size; 7 = 6 + cdpr_reset_robots, cdpr_reset_robots_device; 6 = 5 + cdpr_plan_kernel, cdpr_kernel_name, CDPR_MAX_CABLES 8 -> 12 (cdpr_config_t's anchor arrays grow); 5 = 4 + cdpr_update_scheduled_kind, cdpr_device_pci_bus_id, cdpr_decode_observables_f64 */
 #define CDPR_MAX_CABLES 12u         /* PLG.h:20 fixes 4 (kCableCount); cube.yaml:21-29 is a free-length `points` list: the engine takes 1..12
                                       (9..12: uniform-mode fp32 handles on the lane-per-robot kernels, FK and TD included; see cdpr_create) */
@@ -307,6 +308,61 @@ int cdpr_resample_map_device(cdpr_handle_t h, const cdpr_resample_spec_t *spec, 
                              int32_t *d_source, float *d_ess, uint32_t *d_status);
 int cdpr_resample_device(cdpr_handle_t h, const cdpr_resample_spec_t *spec, const float *d_weights, const uint32_t *d_words,
                          int32_t *d_source, float *d_ess, uint32_t *d_status);
+
+/* MPPI on the device: the two calls around cdpr_rollout_velocity_device that keep a sampling MPC loop on the GPU.  cdpr_mppi_sample_device
+ * writes the perturbed command batch float[B][H][S][n] the rollout reads from a nominal plan float[B][H][n]; cdpr_mppi_update_device
+ * folds the rollout's costs float[B][S] into the next plan and the action to apply (what cdpr_set_velocity_command_device takes).
+ * Neither reads robot state or touches a step kernel; the handle supplies B, n (its cable count) and the stream.  New exports after ABI 8,
+ * no struct changes.  tests/mppi_oracle.py restates the definition in numpy.
+ *
+ * Sample.  Robot b has the global index g = robot_offset + b (modulo 2^32).  Element e = (t * S + s) * n + i of its block of
+ * E = H * S * n floats belongs to group j = e >> 2, lane k = e & 3.  The random words are
+ *   (x0 .. x3) = Philox4x32-10(counter = (j, g, iteration, 0), key = (seed_lo, seed_hi))
+ * with the published constants (multipliers D2511F53, CD9E8D57; key increments 9E3779B9, BB67AE85; one round is
+ * c' = (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)), then the key moves on).  The normals are Box-Muller in float:
+ *   u1 = (float)((x >> 9) + 1) * 2^-23 in (0, 1],  a = (float)(y >> 8) * 2^-23 in [0, 2)  (both exact),  r = sqrtf(-2 * logf(u1)),
+ *   (z0, z1) = r * (cos pi a, sin pi a) from (x0, x1) with one sincospif, (z2, z3) likewise from (x2, x3);  |z| <= 5.65.
+ * The command is v = fmaf(sigma, z_k, U[b][t][i]); with CDPR_MPPI_CLAMP then v = fminf(fmaxf(v, cmd_min), cmd_max) (a NaN becomes
+ * cmd_min); with CDPR_MPPI_NOMINAL_FIRST sample s = 0 is the (clamped) nominal without noise.  Only d_commands[0, B * E) is written.  A
+ * robot's stream depends on (g, iteration, key) and on nothing else: a shard with robot_offset reproduces its rows of the unsharded batch.
+ *
+ * Update, per robot.  A cost is usable iff it is finite; any other has weight 0 and is counted BAD.  No usable cost: the robot is
+ * DEGENERATE and counted - U' is the old nominal, the weights are 0, ess is 0.  Otherwise c_min is the least usable cost and
+ *   w_s = expf((c_min - c_s) / temperature)   (one float subtraction, one float division),   eta = sum w_s,   ess = eta^2 / sum w_s^2,
+ *   U'[t][i] = (sum_s w_s * V[t][s][i]) / eta.
+ * A sample whose weight is exactly 0 is selected out, not multiplied: a NaN command behind it does not reach the plan (the rule of the
+ * environment view's zero reward weights).  Sums are float, in a fixed order: the same inputs give the same bits on every run; against
+ * the definition evaluated in double the results agree within the rounding bounds tests/mppi_oracle.py derives.
+ * d_action[b][i] = U'[0][i].  The plan written to d_nominal is U'; with CDPR_MPPI_SHIFT it is out[t] = U'[t + 1], the last row repeated
+ * (receding horizon).  In place: a robot's rows are all read before any of them is written.
+ * d_weights float[B][S], d_ess float[B], d_action float[B][n], d_status uint32[3] = [robots updated, robots degenerate, bad costs] (zeroed on
+ * the stream in front of the kernel): each may be NULL.  All device buffers; they must stay valid until the stream has passed the call.
+ *
+ * Both calls: any handle - uniform or per-robot, every kernel family, both precisions.  Stream-ordered behind everything queued; they
+ * copy nothing and wait for nothing.  Not step launches: cdpr_kernel_name, cdpr_plan_kernel and the launch counter do not see them.
+ * Refusals (a refused call queues nothing): CDPR_ERR_INVALID for a NULL handle, a NULL spec, a NULL required buffer (sample: d_nominal,
+ * d_commands; update: d_cost, d_commands, d_nominal), struct_size != sizeof(cdpr_mppi_spec_t), an unknown flag bit, reserved != 0,
+ * samples == 0, horizon == 0, a sigma that is negative or not finite, a temperature that is not finite or not > 0 (the update),
+ * CDPR_MPPI_CLAMP with bounds that are not finite or with cmd_min > cmd_max;
+ * CDPR_ERR_UNSUPPORTED for E > 2^34, B * S > 2^30 (the rollout's own limit). */
+#define CDPR_MPPI_NOMINAL_FIRST 1u   /* sample 0 of every robot is the (clamped) nominal itself          */
+#define CDPR_MPPI_CLAMP         2u   /* commands clamped to [cmd_min, cmd_max] (finite, cmd_min <= cmd_max) */
+#define CDPR_MPPI_SHIFT         4u   /* update: the plan moves one step towards now (receding horizon)    */
+
+typedef struct cdpr_mppi_spec {
+  uint32_t struct_size, samples /*S*/, horizon /*H*/, flags;
+  float sigma, cmd_min, cmd_max, temperature;
+  uint32_t seed_lo, seed_hi;       /* Philox key                                      */
+  uint32_t robot_offset;           /* global index of the handle's robot 0 (shards)   */
+  uint32_t reserved;               /* 0                                               */
+} cdpr_mppi_spec_t;
+
+size_t cdpr_mppi_spec_size(void);                    /* sizeof(cdpr_mppi_spec_t) as compiled */
+int cdpr_mppi_sample_device(cdpr_handle_t h, const cdpr_mppi_spec_t *spec, uint32_t iteration,
+                            const float *d_nominal /*[B][H][n]*/, float *d_commands /*[B][H][S][n]*/);
+int cdpr_mppi_update_device(cdpr_handle_t h, const cdpr_mppi_spec_t *spec, const float *d_cost /*[B][S]*/,
+                            const float *d_commands, float *d_nominal /*in/out*/, float *d_action /*[B][n] or NULL*/,
+                            float *d_weights /*[B][S] or NULL*/, float *d_ess /*[B] or NULL*/, uint32_t *d_status /*[3] or NULL*/);
 
 /* Done rules: which robots a loop should put back, decided on the device.  cdpr_reset_robots_device takes a "done" mask that lives
  * on the GPU; these calls compute it there, from the state the handle already holds, so that a Monte-Carlo sweep, an RL-style
