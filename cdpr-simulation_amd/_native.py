@@ -119,6 +119,9 @@ def lib():
         L.cdpr_debug_plan_entry.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
         L.cdpr_debug_plan_entry_address.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
         L.cdpr_debug_plan_entry_address.restype = C.c_void_p
+    # ... and the bytes of the argument records a launch copies, from the configuration alone (tests/test_launch_args.py)
+    if hasattr(L, "cdpr_debug_launch_args"):
+        L.cdpr_debug_launch_args.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
     L.cdpr_step_count.argtypes = [H]
     L.cdpr_step_count.restype = C.c_uint64
     L.cdpr_get_joint_states.argtypes = [H, fp, fp, fp]

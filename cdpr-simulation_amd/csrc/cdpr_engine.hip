@@ -12,119 +12,8 @@ thread_local std::string g_create_error;
 
 namespace cdpr_host {
 
-// ---------------------------------------------------------------------------------
-// Least-squares end-point derivative weights on a uniform grid: the closed form of
-// Pid::derive + fitPolynomial (Pid.cpp:193-247) when samples are one step apart.
-// ---------------------------------------------------------------------------------
-int derivative_weights(uint32_t n, uint32_t degree, double* w) {
-  if (n < 2 || n > CDPR_MAX_D_BUFFER || degree < 1 || degree > CDPR_MAX_D_DEGREE || degree >= n) return CDPR_ERR_INVALID;
-  const int m = (int)degree + 1;
-  long double a[5][10];  // [XtX | I], centred abscissae x_j = j - (n-1)/2
-  for (int i = 0; i < m; ++i)
-    for (int j = 0; j < 2 * m; ++j) a[i][j] = 0.0L;
-  std::vector<long double> x(n);
-  for (uint32_t j = 0; j < n; ++j) x[j] = (long double)j - (long double)(n - 1) / 2.0L;
-  for (int i = 0; i < m; ++i) {
-    for (int k = 0; k < m; ++k) {
-      long double s = 0;
-      for (uint32_t j = 0; j < n; ++j) s += powl(x[j], i + k);
-      a[i][k] = s;
-    }
-    a[i][m + i] = 1.0L;
-  }
-  for (int col = 0; col < m; ++col) {  // Gauss-Jordan, partial pivoting
-    int piv = col;
-    for (int r = col + 1; r < m; ++r)
-      if (fabsl(a[r][col]) > fabsl(a[piv][col])) piv = r;
-    if (piv != col)
-      for (int k = 0; k < 2 * m; ++k) std::swap(a[piv][k], a[col][k]);
-    long double d = a[col][col];
-    for (int k = 0; k < 2 * m; ++k) a[col][k] /= d;
-    for (int r = 0; r < m; ++r) {
-      if (r == col) continue;
-      long double f = a[r][col];
-      for (int k = 0; k < 2 * m; ++k) a[r][k] -= f * a[col][k];
-    }
-  }
-  // derivative at the newest sample x_e: sum_k k x_e^(k-1) c_k, c = (XtX)^-1 Xt y
-  const long double xe = x[n - 1];
-  for (uint32_t j = 0; j < n; ++j) {
-    long double wj = 0;
-    for (int k = 1; k < m; ++k) {
-      long double ck = 0;  // row k of (XtX)^-1 Xt, column j
-      for (int i = 0; i < m; ++i) ck += a[k][m + i] * powl(x[j], i);
-      wj += (long double)k * powl(xe, k - 1) * ck;
-    }
-    w[j] = (double)wj;
-  }
-  return CDPR_OK;
-}
-
-// (mat3_inverse_sym, validate_config, fast_path_obstacle: cdpr_select.hpp - pure functions, shared with cdpr_plan_kernel)
-
-void fill_pid(const cdpr_pid_params_t& p, double dt, StepArgs& k, float* wtab_host) {
-  k.kf = (float)p.forward_gain;
-  k.kp = (float)p.p_gain;
-  k.ki = (float)p.i_gain;
-  k.kd = (float)p.d_gain;
-  k.inv_ki = (p.i_gain != 0.0) ? (float)(1.0 / p.i_gain) : 0.f;
-  k.imax = (float)std::fabs(p.i_limit);  // Pid.cpp:70-73 (abs -> fabs)
-  k.imin = -(float)std::fabs(p.i_limit);
-  k.cmax = (float)std::fabs(p.cmd_limit);
-  k.cmin = -(float)std::fabs(p.cmd_limit);
-  k.inv_dt = (float)(1.0 / dt);
-  k.nbuf = (int)p.d_buffer_length;
-  k.clamp_cmd = k.cmax > k.cmin;
-  rotated_weights(p, kWin, wtab_host);
-}
-
-void copy_pid(const StepArgs& src, StepArgs& dst) {
-  dst.kf = src.kf; dst.kp = src.kp; dst.ki = src.ki; dst.kd = src.kd; dst.inv_ki = src.inv_ki;
-  dst.imax = src.imax; dst.imin = src.imin; dst.cmax = src.cmax; dst.cmin = src.cmin; dst.inv_dt = src.inv_dt;
-  dst.wtab = src.wtab;
-  dst.nbuf = src.nbuf; dst.clamp_cmd = src.clamp_cmd;
-}
-
-// per-robot kernels: the position Pid rides along as StepArgs::alt (the primary fields hold the velocity Pid)
-void copy_pid_alt(const StepArgs& src, PidSet& dst) {
-  dst.kf = src.kf; dst.kp = src.kp; dst.ki = src.ki; dst.kd = src.kd; dst.inv_ki = src.inv_ki;
-  dst.imax = src.imax; dst.imin = src.imin; dst.cmax = src.cmax; dst.cmin = src.cmin;
-  dst.clamp_cmd = src.clamp_cmd;
-}
-
-void fill_consts(const cdpr_config_t& c, StepArgs& k) {
-  fill_physics<float>(c, k);
-  k.dt_inv_mass = (float)(c.dt / c.mass);
-  k.travel_stop = k.travel_on ? (int)c.travel_stop : 0;
-  k.split_swap = 0x9;  // measured on MI355X (65 536 x 8): masks 0 .. 0xf8 give 10.8-11.3 us/step, 0x9 the best; bits 8-9 (the
-                       // workgroups that share a CU) make it 12.8: the dispatcher already alternates the SIMD pairs there
-  if (const char* sw = std::getenv("CDPR_SPLIT_SWAP")) k.split_swap = (uint32_t)strtoul(sw, nullptr, 0);
-}
-
-// BiQuad::SetFc(fc, fs = 1.0, q), Filter.h:130-140, in double: a0 a1 a2 b1 b2
-void biquad_coefficients(const cdpr_filter_params_t& f, double co[5]) {
-  const double k = std::tan(M_PI * f.rel_cutoff / 1.0);
-  const double den = k * k + k / f.quality + 1.0;
-  co[0] = k * k / den, co[1] = 2.0 * co[0], co[2] = co[0];
-  co[3] = 2.0 * (k * k - 1.0) / den, co[4] = (k * k - k / f.quality + 1.0) / den;
-}
-
-void fill_gen_pid(const cdpr_pid_params_t& p, GenPid& g) {
-  g.kf = (float)p.forward_gain; g.kp = (float)p.p_gain; g.ki = (float)p.i_gain; g.kd = (float)p.d_gain;
-  g.imax = (float)std::fabs(p.i_limit); g.imin = -(float)std::fabs(p.i_limit);
-  g.cmax = (float)std::fabs(p.cmd_limit); g.cmin = -(float)std::fabs(p.cmd_limit);
-  g.nbuf = (int)p.d_buffer_length; g.degree = (int)p.d_degree;
-  g.pcas = (int)p.p_filter.cascade; g.dcas = (int)p.d_filter.cascade;
-  g.clamp = g.cmax > g.cmin ? 1 : 0;
-  auto biquad = [](const cdpr_filter_params_t& f, float& a0, float& a1, float& a2, float& b1, float& b2) {
-    double co[5];
-    biquad_coefficients(f, co);
-    a0 = (float)co[0], a1 = (float)co[1], a2 = (float)co[2], b1 = (float)co[3], b2 = (float)co[4];
-  };
-  g.pa0 = g.pa1 = g.pa2 = g.pb1 = g.pb2 = g.da0 = g.da1 = g.da2 = g.db1 = g.db2 = 0.f;
-  if (g.pcas) biquad(p.p_filter, g.pa0, g.pa1, g.pa2, g.pb1, g.pb2);
-  if (g.dcas) biquad(p.d_filter, g.da0, g.da1, g.da2, g.db1, g.db2);
-}
+// (mat3_inverse_sym, validate_config, fast_path_obstacle: cdpr_select.hpp; derivative_weights, biquad_coefficients, the Pids and every
+// kernel argument: cdpr_launch_args.hpp - pure functions, shared with cdpr_plan_kernel, cdpr_debug_launch_args and the stand-alone checks)
 
 // Cable geometry as the kernel wants it in LDS: per cable pair
 // [ax0 ax1 ay0 ay1 | az0 az1 bx0 bx1 | by0 by1 bz0 bz1 | l00 l01 mask0 mask1].
@@ -186,7 +75,7 @@ int upload_home(cdpr_engine* h) {
   if (h->d_dbg) HIP_TRY(h, hipMemsetAsync(h->d_dbg, 0, (size_t)h->batch * CDPR_PID_DEBUG_AXES * sizeof(float), h->stream));
   for (int i = 0; i < 2; ++i)  // latched and pending Joy buffers: target 0 after Load / reset
     for (CmdChannel& c : h->cmd) HIP_TRY(h, hipMemsetAsync(c.d[i], 0, (size_t)h->stride * h->n * sizeof(float), h->stream));
-  if (h->d_rec) HIP_TRY(h, hipMemsetAsync(h->d_rec, 0, h->glay.bytes(h->stride), h->stream));
+  if (h->d_rec) HIP_TRY(h, hipMemsetAsync(h->d_rec, 0, h->args.glay.bytes(h->stride), h->stream));
   if (h->d_mode) HIP_TRY(h, hipMemsetAsync(h->d_mode, kModePosition, h->batch, h->stream));  // PLG.cpp:153-157 (call count 0)
   if (h->d_target) HIP_TRY(h, hipMemsetAsync(h->d_target, 0, (size_t)h->stride * h->n * sizeof(float), h->stream));  // target 0 after Load
   HIP_TRY(h, wait_stream(h));
@@ -271,77 +160,38 @@ int stage_command(cdpr_engine* h, int kind, const float* src, size_t count, bool
   return CDPR_OK;
 }
 
-// cdpr_create's part of a general-path handle: the layout of the controller records, the records, the two Pids' parameter table
-// and their FIR weights by ring head.
+// cdpr_create's part of a general-path handle: the controller records, sized by the layout launch_args made, and its two tables.
 static int build_general(cdpr_engine* h) {
-  const cdpr_config_t& cfg = h->cfg;
-  h->glay.n = (int)h->n;
-  h->glay.nb = (int)std::max(cfg.velocity_pid.d_buffer_length, cfg.position_pid.d_buffer_length);
-  h->glay.ncas = (int)std::max(std::max(cfg.velocity_pid.p_filter.cascade, cfg.velocity_pid.d_filter.cascade),
-                               std::max(cfg.position_pid.p_filter.cascade, cfg.position_pid.d_filter.cascade));
-  const size_t rec_bytes = h->glay.bytes(h->stride);
+  const size_t rec_bytes = h->args.glay.bytes(h->stride);
   if (rec_bytes >= (1ull << 32)) {  // the record buffer is addressed with 32-bit offsets (one buffer resource)
     h->err = "general controller path: the controller records of this batch pass 4 GiB; split the batch over several handles";
     return CDPR_ERR_UNSUPPORTED;
   }
   CREATE_TRY(h, "hipMalloc(rec)", h->d_rec.alloc(rec_bytes));
-  fill_gen_pid(cfg.position_pid, h->gpid[0]);
-  fill_gen_pid(cfg.velocity_pid, h->gpid[1]);
-  // FIR weights by ring head: when the newest sample sits in slot `head`, slot j holds the sample of age (head - j) mod
-  // nbuf, whose end-point LS weight (oldest first) is w[nbuf - 1 - age]; slots >= nbuf weigh nothing.  The head slot itself
-  // weighs nothing in the table: the newest sample is still in a register when the FIR runs, its weight rides in the Pid
-  // table (last float)
-  const int nbmax = h->glay.nb > 11 ? kGenMaxBuf : 11, nbp = gen_nbp(nbmax);
-  std::vector<float> wt((size_t)2 * nbmax * nbp, 0.f);
-  const cdpr_pid_params_t* pp[2] = {&cfg.position_pid, &cfg.velocity_pid};
-  float w_new[2] = {0.f, 0.f};
-  for (int p = 0; p < 2; ++p) {
-    double w[CDPR_MAX_D_BUFFER];
-    const int nb = (int)pp[p]->d_buffer_length;
-    if (derivative_weights((uint32_t)nb, pp[p]->d_degree, w) != CDPR_OK) continue;
-    for (int head = 0; head < nb; ++head)
-      for (int j = 0; j < nb; ++j) wt[((size_t)p * nbmax + head) * nbp + j] = (j == head) ? 0.f : (float)w[nb - 1 - (((head - j) % nb + nb) % nb)];
-    w_new[p] = (float)w[nb - 1];
-  }
-  float pt[2 * kGenPidFloats];
-  gen_pid_table(h->gpid[0], pt);
-  gen_pid_table(h->gpid[1], pt + kGenPidFloats);
-  pt[kGenPidFloats - 1] = w_new[0], pt[2 * kGenPidFloats - 1] = w_new[1];
-  if (int rc = upload_table(h, h->d_gptab, pt, sizeof pt, "gptab")) return rc;
-  return upload_table(h, h->d_gwtab, wt.data(), wt.size() * sizeof(float), "gwtab");
+  if (int rc = upload_table(h, h->d_gptab, h->args.ptab.data(), h->args.ptab.size() * sizeof(float), "gptab")) return rc;
+  return upload_table(h, h->d_gwtab, h->args.gwtab.data(), h->args.gwtab.size() * sizeof(float), "gwtab");
 }
 
-// The controller half of a general-path launch: records, latched commands, gains.
-GenCtl general_ctl(const cdpr_engine* h) {
-  GenCtl g{};
-  g.rec = h->d_rec;
-  g.rstride = h->stride;
-  g.rec_bytes = (uint32_t)h->glay.bytes(h->stride);
-  const float* latched[kCmdKinds];
-  for (int k = 0; k < kCmdKinds; ++k) latched[k] = h->cmd[k].have ? h->cmd[k].latched() : nullptr;
-  g.vel_cmd = latched[CDPR_COMMAND_VELOCITY], g.pos_cmd = latched[CDPR_COMMAND_POSITION], g.frc_cmd = latched[CDPR_COMMAND_FORCE];
-  g.mode_arr = h->plan.per_robot ? h->d_mode : nullptr;
-  g.wtab = h->d_gwtab;
-  g.mode = h->mode;
-  // JFC.cpp:72 compares the Joy axis (a float32) promoted to double with the double epsilon.  The kernels compare in float32: with the
-  // largest float32 that is not above epsilon, t > g.eps holds for a float32 t exactly when (double)t > epsilon.  (float)epsilon
-  // alone may round UP (0.001, 0.004): a target equal to it would then hold position where the reference runs the velocity Pid.
-  g.eps = (float)h->cfg.velocity_epsilon;
-  if ((double)g.eps > h->cfg.velocity_epsilon) g.eps = nextafterf(g.eps, -INFINITY);
-  g.dt = (float)h->cfg.dt;
-  g.lay = h->glay;
-  g.ptab = h->d_gptab;
-  g.pcas_max = std::max(h->gpid[0].pcas, h->gpid[1].pcas);
-  g.dcas_max = std::max(h->gpid[0].dcas, h->gpid[1].dcas);
-  g.nbuf0 = h->gpid[0].nbuf, g.nbuf1 = h->gpid[1].nbuf;
-  g.hot = h->plan.gen_hot ? 1 : 0;
-  {
-    const GenPid &p0 = h->gpid[0], &p1 = h->gpid[1];
-    const bool same_window = p0.nbuf == p1.nbuf && p0.degree == p1.degree;
-    const bool clamps = p0.cmax > p0.cmin && p1.cmax > p1.cmin && p0.imax >= p0.imin && p1.imax >= p1.imin;
-    g.simple_ok = (same_window && clamps && g.pcas_max == 0 && g.dcas_max == 0) ? 1 : 0;
+// The handle's device pointers, batch and stride into every argument record, once, after the allocations (the list of what a launch
+// still assigns: cdpr_launch_args.hpp).
+static void bind_args(cdpr_engine* h) {
+  for (int rec = 0; rec < kArgsRecords; ++rec) {
+    const bool pr = rec == kArgsPerRobot, vel = pr || rec == kModeVelocity;
+    StepArgs& a = h->args.step[rec];
+    a.state = h->d_state, a.obs = h->d_obs, a.dbg = h->d_dbg, a.geom = h->d_geom;
+    a.batch = h->batch, a.stride = h->stride;
+    if (h->d_wtab) a.wtab = h->d_wtab + (vel ? 0 : kWin * (kWin + 2));
+    if (pr && !h->plan.general) a.cmd = h->d_target, a.meta = h->d_mode;  // the robots' ACTIVE target rows, their mode / call-count bytes
+    GenCtl& g = h->args.gen[rec];
+    g.rec = h->d_rec, g.rstride = h->stride, g.rec_bytes = (uint32_t)h->args.glay.bytes(h->stride);
+    g.mode_arr = pr ? h->d_mode.p : nullptr;
+    g.wtab = h->d_gwtab, g.ptab = h->d_gptab;
+    F64Args& f = h->args.f64[rec];
+    f.state = h->d_state64, f.obs = h->d_obs64, f.dbg = h->d_dbg64, f.geom = h->d_geom64;
+    f.batch = h->batch, f.stride = h->stride;
+    if (h->d_wtab64) f.wtab = h->d_wtab64 + (vel ? 0 : win64(h->plan) * (win64(h->plan) + 2));
+    if (pr) f.cmd = h->d_target, f.meta = h->d_mode;
   }
-  return g;
 }
 
 // Wait for the handle's stream with the host in the loop in mind (update -> synchronize -> read observables, every
@@ -380,8 +230,9 @@ int check_fault(cdpr_engine* h) {
 // cdpr_device_download return CDPR_ERR_DEVICE until cdpr_reset - the fp64 read-outs and the FK / TD / limit / debug getters too)
 int checked(cdpr_engine* h, int rc) { return rc != CDPR_OK ? rc : check_fault(h); }
 
-// What every kind of handle gets in cdpr_create: sizes, constants, stream and events, the command buffers, the fp32 tables, the
-// per-robot rows; then the path's own set-up (build_f64, build_general), the home state and the warm launch.
+// What every kind of handle gets in cdpr_create: sizes, the argument records (launch_args), stream and events, the command buffers, the
+// fp32 tables, the per-robot rows and the path's own set-up (build_f64, build_general); then the device pointers go into the records
+// (bind_args), the home state is uploaded and the warm launch runs.
 static int build_handle(cdpr_engine* h) {
   const cdpr_config_t& cfg = h->cfg;
   if (int rc = refuse_missing(h, missing_entry(h->plan))) return rc;  // (before anything is allocated: every kernel this plan can name has an instantiation)
@@ -403,10 +254,7 @@ static int build_handle(cdpr_engine* h) {
   }
   h->n_state = h->plan.general ? plat_slots(h->plan.fk) : state_slots((int)h->n, h->plan.fk);
   h->n_obs = obs_slots((int)h->n);
-  memset(&h->base, 0, sizeof h->base);
-  fill_consts(cfg, h->base);
-  fill_pid(cfg.velocity_pid, cfg.dt, h->pid_vel, h->wtab_host[0]);
-  fill_pid(cfg.position_pid, cfg.dt, h->pid_pos, h->wtab_host[1]);
+  h->args = launch_args(cfg, h->plan);
   engine_reset_host(h);
   {
     if (const char* ss = std::getenv("CDPR_SPLIT_STEADY")) h->split_steady = !(ss[0] == '0');
@@ -431,9 +279,8 @@ static int build_handle(cdpr_engine* h) {
       CREATE_TRY(h, "hipMalloc(cmd)", c.d[i].alloc(cmd_bytes));
       (void)hipMemset(c.d[i], 0, cmd_bytes);
     }
-  if (int rc = upload_table(h, h->d_wtab, h->wtab_host, sizeof h->wtab_host, "wtab")) return rc;
-  h->pid_vel.wtab = h->d_wtab;
-  h->pid_pos.wtab = h->d_wtab + kWin * (kWin + 2);
+  if (!h->args.wtab.empty())
+    if (int rc = upload_table(h, h->d_wtab, h->args.wtab.data(), h->args.wtab.size() * sizeof(float), "wtab")) return rc;
   {
     std::vector<float> g = geom_pairs(cfg);
     if (int rc = upload_table(h, h->d_geom, g.data(), g.size() * sizeof(float), "geom")) return rc;
@@ -447,6 +294,7 @@ static int build_handle(cdpr_engine* h) {
   }
   CREATE_TRY(h, "hipMalloc(episode)", h->d_episode.alloc((size_t)h->stride * sizeof(uint32_t)));
   if (h->dbg && !h->plan.fp64) CREATE_TRY(h, "hipMalloc(dbg)", h->d_dbg.alloc((size_t)h->batch * CDPR_PID_DEBUG_AXES * sizeof(float)));
+  bind_args(h);
   if (upload_home(h) != CDPR_OK || warm_first_launch(h) != CDPR_OK) return CDPR_ERR_DEVICE;
   return CDPR_OK;
 }
@@ -725,6 +573,17 @@ int cdpr_debug_plan_entry(const cdpr_config_t* cfg, int steps_per_launch, uint32
   if (plan.rc != CDPR_OK) return plan.rc;
   return missing_entry(plan, shape_of_flags(steps_per_launch, flags)).id == KernelId::None ? 1 : 0;
 }
+// The bytes of the argument records a launch of a handle of this configuration copies in `mode` (0 Force, 1 Position, 2 Velocity), pointers
+// null and the per-launch fields zero, the path's uploaded tables appended (launch_args_image, cdpr_launch_args.hpp): written to buf where
+// len suffices; returns their count, or the refusal's code.  From the configuration alone, no HIP call.  For tests, not part of the C-ABI header.
+int cdpr_debug_launch_args(const cdpr_config_t* cfg, int mode, void* buf, size_t len) {
+  if (!cfg || mode < kModeForce || mode > kModeVelocity) return CDPR_ERR_INVALID;
+  const KernelPlan plan = plan_kernels(*cfg);
+  if (plan.rc != CDPR_OK) return plan.rc;
+  const std::vector<unsigned char> image = launch_args_image(launch_args(*cfg, plan), plan, mode);
+  if (buf && len >= image.size()) memcpy(buf, image.data(), image.size());
+  return (int)image.size();
+}
 // ... and the entry point itself (of the form cdpr_plan_kernel names: Position mode, not the steady-state instantiation), null where
 // there is none or the configuration is refused: two cells run the same code exactly where these are equal
 const void* cdpr_debug_plan_entry_address(const cdpr_config_t* cfg, int steps_per_launch, uint32_t flags) {
@@ -752,7 +611,7 @@ int cdpr_debug_last_variant(cdpr_handle_t h) { return h ? (h->last_kernel.steady
 // diagnostic builds only: point the step kernel at a stamp buffer (uint64[blocks][8]); nullptr disables
 int cdpr_debug_set_stamps(cdpr_handle_t h, unsigned long long* d_stamps) {
   if (!h) return CDPR_ERR_INVALID;
-  h->base.stamps = d_stamps;
+  for (int rec = 0; rec < kArgsRecords; ++rec) h->args.step[rec].stamps = h->args.f64[rec].stamps = d_stamps;  // every record a later launch copies
   return CDPR_OK;
 }
 #endif

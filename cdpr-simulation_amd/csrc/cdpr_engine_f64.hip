@@ -1,5 +1,6 @@
 // cdpr_engine_f64.hip - host side of cdpr_config_t.precision = 64: the handle's set-up (build_f64), the fp64 step kernels' path of the
-// launch chain (cdpr_step_kernel_f64.hpp), and the rollout by composition.  Reference paths as in cdpr_engine.hip.
+// launch chain (cdpr_step_kernel_f64.hpp), and the rollout by composition; both start from h->args.f64 (cdpr_launch_args.hpp: every
+// constant of a launch, hold branch included, is made once by cdpr_create).  Reference paths as in cdpr_engine.hip.
 #include "cdpr_engine_internal.hpp"
 
 namespace cdpr {
@@ -74,17 +75,16 @@ static __global__ __launch_bounds__(256) void cdpr_roll64_cost_kernel(const Roll
 namespace cdpr_host {
 
 // rows of an fp64 handle's state: platform, FK estimate, one Pid's rows per cable - and, hold branch live, both Pids' records
-size_t state64_rows(const cdpr_engine* h) { return (size_t)f64_state_rows((int)h->n, win64(h)) + (h->plan.hold64 ? (size_t)f64_hold_rows((int)h->n, hold_win(h)) : 0); }
+size_t state64_rows(const cdpr_engine* h) { return (size_t)f64_state_rows((int)h->n, win64(h->plan)) + (h->plan.hold64 ? (size_t)f64_hold_rows((int)h->n, hold_win(h->plan)) : 0); }
 
 // cdpr_create's part of a precision = 64 handle: state and observables in double, the cable geometry, the two Pids' rotated weight
-// tables for the ring of this handle's kernels (10, or 31 with windows of 12 .. 32 samples), the debug rows, the constants of a launch
+// tables for the ring of this handle's kernels (10, or 31 with windows of 12 .. 32 samples; launch_args made them), the debug rows
 int build_f64(cdpr_engine* h) {
   const cdpr_config_t& cfg = h->cfg;
   const size_t row = (size_t)h->stride * sizeof(double);
   CREATE_TRY(h, "hipMalloc(state64)", h->d_state64.alloc(row * state64_rows(h)));
   CREATE_TRY(h, "hipMalloc(obs64)", h->d_obs64.alloc(row * f64_obs_rows((int)h->n)));
-  const int W = win64(h);
-  std::vector<double> g((size_t)h->n * 7), wt((size_t)2 * W * (W + 2), 0.0);
+  std::vector<double> g((size_t)h->n * 7);
   for (uint32_t i = 0; i < h->n; ++i) {
     for (int k = 0; k < 3; ++k) {
       g[(size_t)i * 7 + k] = cfg.frame_anchor[i][k];
@@ -92,17 +92,9 @@ int build_f64(cdpr_engine* h) {
     }
     g[(size_t)i * 7 + 6] = cfg.cable_ref_length[i];
   }
-  rotated_weights(cfg.velocity_pid, W, &wt[0]);
-  rotated_weights(cfg.position_pid, W, &wt[(size_t)W * (W + 2)]);
   if (int rc = upload_table(h, h->d_geom64, g.data(), g.size() * sizeof(double), "geom64")) return rc;
-  if (int rc = upload_table(h, h->d_wtab64, wt.data(), wt.size() * sizeof(double), "wtab64")) return rc;
+  if (int rc = upload_table(h, h->d_wtab64, h->args.wtab64.data(), h->args.wtab64.size() * sizeof(double), "wtab64")) return rc;
   if (h->dbg) CREATE_TRY(h, "hipMalloc(dbg64)", h->d_dbg64.alloc((size_t)h->batch * CDPR_PID_DEBUG_AXES * sizeof(double)));
-  F64Args& b = h->base64;
-  memset(&b, 0, sizeof b);
-  b.state = h->d_state64; b.obs = h->d_obs64; b.dbg = h->d_dbg64; b.geom = h->d_geom64;
-  b.batch = h->batch; b.stride = h->stride;
-  b.fk = h->plan.fk ? 1 : 0; b.td = h->plan.td ? 1 : 0;
-  fill_physics<double>(cfg, b);
   return CDPR_OK;
 }
 
@@ -127,89 +119,28 @@ int upload_home64(cdpr_engine* h) {
   return CDPR_OK;
 }
 
-void fill_pid64(const cdpr_pid_params_t& p, double dt, F64Args& k) {
-  k.kf = p.forward_gain; k.kp = p.p_gain; k.ki = p.i_gain; k.kd = p.d_gain;
-  k.imax = std::fabs(p.i_limit); k.imin = -std::fabs(p.i_limit);  // Pid.cpp:70-73 (abs -> fabs)
-  k.cmax = std::fabs(p.cmd_limit); k.cmin = -std::fabs(p.cmd_limit);
-  k.inv_dt = 1.0 / dt;
-  k.nbuf = (int)p.d_buffer_length;
-  k.clamp_cmd = k.cmax > k.cmin;
-}
-
-// The arguments of a launch that depend on the handle's mode, not on the step: the Pid(s), the command buffer, the weight table; per-robot
-// handles: both Pids and the meta row; HOLD handles: both Pids, the hold branch's parameters, the cascades' coefficients
-static void f64_mode_args(const cdpr_engine* h, bool vel, bool frc, F64Args& a) {
-  const bool pr = h->plan.per_robot;
-  fill_pid64(vel ? h->cfg.velocity_pid : h->cfg.position_pid, h->cfg.dt, a);
-  a.cmd = pr ? h->d_target : h->cmd[frc ? CDPR_COMMAND_FORCE : vel ? CDPR_COMMAND_VELOCITY : CDPR_COMMAND_POSITION].latched();
-  a.wtab = h->d_wtab64 + (vel ? 0 : win64(h) * (win64(h) + 2));
-  if (pr) {  // mode, Pid call count and so the Pid per lane: the velocity Pid in the primary fields, the position Pid in alt_*
-    F64Args p = h->base64;
-    fill_pid64(h->cfg.position_pid, h->cfg.dt, p);
-    a.alt_kf = p.kf, a.alt_kp = p.kp, a.alt_ki = p.ki, a.alt_kd = p.kd;
-    a.alt_imax = p.imax, a.alt_imin = p.imin, a.alt_cmax = p.cmax, a.alt_cmin = p.cmin, a.alt_clamp_cmd = p.clamp_cmd;
-    a.meta = h->d_mode;
-  }
-  if (h->plan.hold64) {  // both Pids alive: the velocity Pid in the primary fields, the position Pid in alt_*
-    F64Args v = h->base64, p = h->base64;
-    fill_pid64(h->cfg.velocity_pid, h->cfg.dt, v);
-    fill_pid64(h->cfg.position_pid, h->cfg.dt, p);
-    a.kf = v.kf, a.kp = v.kp, a.ki = v.ki, a.kd = v.kd, a.imax = v.imax, a.imin = v.imin, a.cmax = v.cmax, a.cmin = v.cmin, a.nbuf = v.nbuf, a.clamp_cmd = v.clamp_cmd;
-    a.alt_kf = p.kf, a.alt_kp = p.kp, a.alt_ki = p.ki, a.alt_kd = p.kd, a.alt_imax = p.imax, a.alt_imin = p.imin, a.alt_cmax = p.cmax, a.alt_cmin = p.cmin;
-    a.alt_clamp_cmd = p.clamp_cmd, a.alt_nbuf = p.nbuf;
-    a.degree = (int)h->cfg.velocity_pid.d_degree, a.alt_degree = (int)h->cfg.position_pid.d_degree;
-    a.hold_eps = h->cfg.velocity_epsilon;
-    a.hold_mode = frc ? 0 : (vel ? 2 : 1);
-    const cdpr_pid_params_t* pids[2] = {&h->cfg.position_pid, &h->cfg.velocity_pid};
-    a.any_cas = a.max_cas = 0;
-    a.any_noclamp = (!v.clamp_cmd || !p.clamp_cmd) ? 1 : 0;
-    for (int t = 0; t < 2; ++t) {  // the cascades' coefficients (biquad_coefficients), zero where a filter has no stage
-      const cdpr_filter_params_t* fl[2] = {&pids[t]->p_filter, &pids[t]->d_filter};
-      double* co[2] = {a.pcoef[t], a.dcoef[t]};
-      for (int f = 0; f < 2; ++f) {
-        for (int c = 0; c < 5; ++c) co[f][c] = 0.0;
-        if (fl[f]->cascade) biquad_coefficients(*fl[f], co[f]);
-      }
-      a.pcas[t] = (int)std::min<uint32_t>(pids[t]->p_filter.cascade, (uint32_t)kHoldMaxCas);
-      a.dcas[t] = (int)std::min<uint32_t>(pids[t]->d_filter.cascade, (uint32_t)kHoldMaxCas);
-      a.max_cas = std::max(a.max_cas, std::max(a.pcas[t], a.dcas[t]));
-    }
-    a.any_cas = a.max_cas > 0 ? 1 : 0;
-    for (int t = 0; t < 2; ++t) {  // uniform-grid weights by age of the sample (derivative_weights: oldest first)
-      double w[CDPR_MAX_D_BUFFER];
-      const uint32_t nb = pids[t]->d_buffer_length;
-      if (derivative_weights(nb, pids[t]->d_degree, w) == CDPR_OK)
-        for (uint32_t age = 0; age < nb && age < (uint32_t)hold_win(h); ++age) a.hold_w[t][age] = w[nb - 1 - age];
-    }
-  }
-}
-
 // precision = 64: the same host logic (commands are latched by run_steps before this is reached), the fp64 kernel
 int run_steps_f64(cdpr_engine* h, int nsteps, int per_launch, bool reset_pid, void* record, const PlannedKernel& pk1, const PlannedKernel& pkk) {
   const uint32_t n = h->n;
   if (reset_pid && !h->plan.hold64) {  // Pid::reset (Pid.cpp:100-115): zero every controller row (hold branch live: the latch reset that Pid's own rows)
     h->pid_calls = 0;
-    HIP_TRY(h, hipMemsetAsync(h->d_state64 + (size_t)kF64StateCtrl * h->stride, 0, (size_t)(win64(h) + 1) * n * h->stride * sizeof(double), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_state64 + (size_t)kF64StateCtrl * h->stride, 0, (size_t)(win64(h->plan) + 1) * n * h->stride * sizeof(double), h->stream));
   }
-  F64Args a = h->base64;
-  a.stamps = h->base.stamps;
-  const bool pr = h->plan.per_robot;
-  const bool vel = pr || h->mode == kModeVelocity, frc = !pr && h->mode == kModeForce;
-  f64_mode_args(h, vel, frc, a);
+  F64Args a = h->args.f64[args_index(h)];
+  if (!h->plan.per_robot) a.cmd = h->cmd[cmd_kind_of_mode(h->mode)].latched();
   a.obs_step_stride = record ? (size_t)f64_obs_rows((int)n) * h->stride : 0;  // doubles per observable image
-  a.travel_stop = h->plan.tstop64 ? (int)h->cfg.travel_stop : 0;
   // The routing: pk1 and pkk, planned_kernel's answers (cdpr_select.hpp) for a one-step and for a several-steps launch of this call
   // (run_steps made them in front of the latch).  One step per launch on FK + TD handles: estimator wave + controller wave
   // (cdpr_split_kernel_f64); up to one workgroup per CU its one-step launches beat the one-wave kernel's several-steps ones (14.4
   // against 20.8 us per step at one robot x 8, same bits): a fused update then runs as one-step launches
   if (pkk.id == KernelId::F64Split || pkk.id == KernelId::F64SplitHold) per_launch = 1;
-  const uint32_t mode_flags = pr ? 0u : (vel ? kFlagActualIsVelocity : (frc ? kFlagForceMode : 0u));
+  const uint32_t mode_flags = a.flags;
   return run_chain(h, nsteps, per_launch, record, h->d_obs64, [&](ChainStep& s) {
     a.nsteps = s.k;
     a.flags = mode_flags | s.first_flag;
     if (s.record) a.obs = static_cast<double*>(s.record);
     a.pid_calls = sat_pid_calls(h->pid_calls);
-    a.ring_slot = ring_slot_of(h->step, win64(h));
+    a.ring_slot = ring_slot_of(h->step, win64(h->plan));
     a.step0 = (int)h->step;
     a.publish_mask = s.publish_mask;
     const PlannedKernel& pk = s.k == 1 ? pk1 : pkk;
@@ -242,41 +173,36 @@ int rollout_enqueue_f64(cdpr_engine* h, int samples, int horizon, const float* d
   e.src = h->d_state64, e.dst = h->d_roll64, e.src_stride = h->stride, e.dst_stride = (uint32_t)h->roll64_cols, e.rows = rows, e.batch = h->batch,
   e.samples = (uint32_t)samples, e.zero_from = (reset && !h->plan.hold64) ? (uint32_t)kF64StateCtrl : rows;
   if (h->plan.hold64 && reset) {  // ... there the velocity Pid's own record of every cable is what the Joy resets
-    e.hold_base = (uint32_t)f64_state_rows((int)n), e.hold_cable_rows = (uint32_t)hold_cable_rows(hold_win(h)), e.hold_pid_rows = (uint32_t)hold_pid_rows(hold_win(h));
+    e.hold_base = (uint32_t)f64_state_rows((int)n), e.hold_cable_rows = (uint32_t)hold_cable_rows(hold_win(h->plan)), e.hold_pid_rows = (uint32_t)hold_pid_rows(hold_win(h->plan));
     e.hold_zero_pid = 2u;  // 1 + the Pid's index
   }
   if (pr) e.meta_src = h->d_mode, e.meta_dst = h->d_roll64_meta;
   hipLaunchKernelGGL(cdpr_roll64_expand_kernel, dim3(blocks), dim3(256), 0, h->stream, e);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemsetAsync(h->d_roll64_acc, 0, cols * sizeof(double), h->stream));
-  F64Args a = h->base64;
-  f64_mode_args(h, true, false, a);  // Velocity mode (hold branch live: both Pids, the branch's parameters)
+  F64Args a = h->args.f64[args_index(h->plan, kModeVelocity)];  // Velocity mode, whatever mode the handle is in (nothing is published: publish_mask = 0)
   a.state = h->d_roll64;
-  a.obs = h->d_obs64;  // (nothing is published: publish_mask = 0)
   a.dbg = nullptr;
   a.cmd = h->d_roll64_cmd;  // (per-robot handles: the trajectory's ACTIVE target row)
   if (pr) a.meta = h->d_roll64_meta;
-  a.wtab = h->d_wtab64;
   a.batch = (uint32_t)traj;
   a.stride = (uint32_t)h->roll64_cols;
   a.nsteps = 1;
-  a.publish_mask = 0;
-  a.obs_step_stride = 0;
   LaunchShape shape = launch_shape(h, horizon);  // the handle's one-wave kernel, rings in memory (planned_kernel's rollout rule)
   shape.rollout = true;
   const PlannedKernel pk = planned_kernel(h->plan, shape);
   const F64Kernel kern = f64_entry(pk);
   h->last_kernel = pk;
-  a.travel_stop = h->plan.tstop64 ? (int)h->cfg.travel_stop : 0;
+  const uint32_t mode_flags = a.flags;
   int calls = reset ? 0 : h->pid_calls;  // (uniform handles; per-robot handles count in the meta bytes)
   for (int k = 0; k < horizon; ++k) {
     Roll64CmdArgs c{};
     c.commands = d_commands, c.out = h->d_roll64_cmd, c.batch = h->batch, c.samples = (uint32_t)samples, c.horizon = (uint32_t)horizon, c.n = n, c.k = (uint32_t)k;
     hipLaunchKernelGGL(cdpr_roll64_cmd_kernel, dim3((uint32_t)((traj * n + 255u) / 256u)), dim3(256), 0, h->stream, c);
     const bool first_world = (steps_since_load(h) + (uint64_t)k) == 0;
-    a.flags = (pr ? 0u : kFlagActualIsVelocity) | (first_world ? kFlagFirstWorldStep : 0u);
+    a.flags = mode_flags | (first_world ? kFlagFirstWorldStep : 0u);
     a.pid_calls = sat_pid_calls(calls);
-    a.ring_slot = ring_slot_of(h->step + (uint64_t)k, win64(h));
+    a.ring_slot = ring_slot_of(h->step + (uint64_t)k, win64(h->plan));
     a.step0 = (int)(h->step + (uint64_t)k);
     hipLaunchKernelGGL(kern, dim3(pk.grid(traj)), dim3(pk.block), 0, h->stream, a);
     calls = sat_pid_calls(calls + (first_world ? 0 : 1));

@@ -1,8 +1,8 @@
 // cdpr_engine_internal.hpp - what the translation units of the host side share: the owners of device and pinned memory and of the
 // captured graphs (DevBuf, PinnedBuf, StagePair, GraphCache), the views of a per-robot handle's records with the one launch helper
 // of the kernels over chosen robots (fast_records / gen_records / f64_records, launch_per_robot), the handle (struct cdpr_engine: its routing is h->plan and nothing else, its
-// buffers are owner members that go with it), the error macros and the helpers one unit defines and another calls.  Units:
-// cdpr_engine.hip (create / destroy, the general path's set-up, the command setters, the extern "C" wrappers), cdpr_engine_readout.hip (the getters,
+// buffers are owner members that go with it, its kernel arguments are h->args: cdpr_launch_args.hpp), the error macros and the helpers one unit defines and another calls.  Units:
+// cdpr_engine.hip (create / destroy with bind_args, the general path's set-up, the command setters, the extern "C" wrappers), cdpr_engine_readout.hip (the getters,
 // the image decoders and cdpr_set_platform_state* on the column table of cdpr_readout.hpp: one gather kernel, read_blocks),
 // cdpr_engine_launch.hip (what turns "advance n world steps" into launches: the latch, the chain and its clock, the fp32 and
 // general paths, schedules), cdpr_engine_f64.hip (precision = 64: set-up, its path of the chain), cdpr_engine_rollout.hip (cdpr_rollout_velocity*), cdpr_engine_solvers.hip (cdpr_solve_ik / fk / td), cdpr_engine_reset.hip
@@ -24,8 +24,7 @@
 #include <vector>
 
 #include "../../include/cdpr.h"
-#include "cdpr_kernels.hpp"
-#include "cdpr_select.hpp"
+#include "cdpr_launch_args.hpp"
 #include "cdpr_robot_records.hpp"
 #include "cdpr_solvers.hpp"
 #include "cdpr_readout.hpp"
@@ -33,8 +32,6 @@
 using namespace cdpr;
 
 namespace cdpr_host {
-
-enum Mode { kModeForce = 0, kModePosition = 1, kModeVelocity = 2 };  // JFC.h:35-37
 
 #define HIP_TRY(h, expr)                                                                         \
   do {                                                                                           \
@@ -249,8 +246,6 @@ struct cdpr_engine {
   DevBuf<float> d_rec;       // record rows: [mLastPosition per cable][position Pid rows][velocity Pid rows], one column per robot
   DevBuf<float> d_gwtab;     // FIR weights by ring head, [pid][head][slot]
   DevBuf<float> d_gptab;     // the two Pids' parameters as the kernel stages them in LDS (gen_pid_table)
-  GenPid gpid[2]{};
-  GenLayout glay{};          // rows of a Pid block: sized by the configured window length and cascade count
   // MPC rollout on a precision = 64 handle: the trajectories' state rows, their cost accumulators, the step's Joy batch,
   // per-robot handles: every trajectory's mode / Pid call count byte.  Grow-only, sized together for roll64_cols columns (their row stride)
   DevBuf<double> d_roll64, d_roll64_acc;
@@ -274,10 +269,8 @@ struct cdpr_engine {
   uint64_t step = 0;
   uint64_t origin = 0;           // the world step a fresh or reset handle stands at (CDPR_STEP_ORIGIN, read once by cdpr_create; default 0)
   double prev_publish = 0.0;
-  StepArgs base{};               // world/body/FK/TD constants, pointers; Pid fields filled per launch
-  StepArgs pid_vel{}, pid_pos{};  // only the Pid fields of these are used
-  DevBuf<float> d_wtab;           // [velocity | position] rotated derivative-weight tables, kWin * (kWin + 2) floats each
-  float wtab_host[2][kWin * (kWin + 2)]{};  // the same tables on the host: one-step launches take their row by value
+  LaunchArgs args;                // every kernel argument that outlives a launch (cdpr_launch_args.hpp): made by cdpr_create, device pointers bound in (bind_args)
+  DevBuf<float> d_wtab;           // register-resident path: args.wtab on the device
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   uint64_t launches = 0, launches_mark = 0;
   // read-out (read_blocks, cdpr_engine_readout.hip): device scratch the gather writes where it does not store to the host itself
@@ -309,78 +302,11 @@ struct cdpr_engine {
   DevBuf<double> d_geom64;       // [n][7]
   DevBuf<double> d_wtab64;       // [velocity | position] x [10][12]
   DevBuf<double> d_dbg64;
-  F64Args base64{};
   std::string err;
 };
 
 namespace cdpr_host {
 
-// precision = 64: prior errors kept per cable (the ring of the handle's kernels), and the samples a HOLD record's window holds
-inline int win64(const cdpr_engine* h) { return h->plan.long64 ? kWinLong : kWin; }
-inline int hold_win(const cdpr_engine* h) { return h->plan.hold_long ? kHoldWinLong : kHoldWin; }
-
-int derivative_weights(uint32_t n, uint32_t degree, double* w);  // cdpr_engine.hip
-
-// A Pid's end-point LS derivative weights rotated per ring position, as T, for a ring of W errors: row ws (W + 2 entries) serves the
-// launch whose new error goes to slot ws.  Slot (ws - j) mod W then holds the error of j steps ago (j = 1 .. W; j = W is slot ws
-// itself, the sample about to be overwritten), whose weight is wpad[W - j]; entry W is the weight of the new error itself.
-template <typename T>
-void rotated_weights(const cdpr_pid_params_t& p, int W, T* tab) {
-  double w[CDPR_MAX_D_BUFFER];
-  std::vector<T> wpad((size_t)W + 1, (T)0);  // oldest..newest, zero padded at the old end to W + 1 entries
-  if (derivative_weights(p.d_buffer_length, p.d_degree, w) == CDPR_OK && p.d_buffer_length <= (uint32_t)W + 1)
-    for (uint32_t j = 0; j < p.d_buffer_length; ++j) wpad[(size_t)W + 1 - p.d_buffer_length + j] = (T)w[j];
-  for (int ws = 0; ws < W; ++ws) {
-    for (int s = 0; s < W; ++s) {
-      int j = ((ws - s) % W + W) % W;
-      if (j == 0) j = W;
-      tab[ws * (W + 2) + s] = wpad[(size_t)W - j];
-    }
-    tab[ws * (W + 2) + W] = wpad[(size_t)W];
-    tab[ws * (W + 2) + W + 1] = (T)0;
-  }
-}
-
-// The world / body / FK / TD constants StepArgs (T = float) and F64Args (T = double) share: every value is computed in double
-// and then cast.
-template <typename T, typename Args>
-void fill_physics(const cdpr_config_t& c, Args& k) {
-  k.dt = (T)c.dt;
-  k.half_dt = (T)(0.5 * c.dt);
-  k.inv_mass = (T)(1.0 / c.mass);
-  k.fgx = (T)(c.mass * c.gravity[0]);
-  k.fgy = (T)(c.mass * c.gravity[1]);
-  k.fgz = (T)(c.mass * c.gravity[2]);
-  double inv[6];
-  mat3_inverse_sym(c.inertia, inv);
-  for (int i = 0; i < 6; ++i) {
-    k.ib[i] = (T)c.inertia[i];
-    k.ibinv[i] = (T)inv[i];
-  }
-  k.damping = (T)c.joint_damping;
-  k.effort = (T)c.effort_limit;
-  k.vel_limit = (T)c.velocity_limit;
-  k.unilateral = c.unilateral_cables ? 1 : 0;
-  k.travel_lo = (T)c.travel_lower;
-  k.travel_hi = (T)c.travel_upper;
-  k.travel_on = (c.travel_lower != 0.0 || c.travel_upper != 0.0) ? 1 : 0;
-  k.ph_lumped = lumped_legs_on(c) ? 1 : 0;
-  k.ph_c = (T)c.passive_damping;
-  k.ph_jleg = (T)c.leg_inertia;
-  k.ph_max = (T)c.cable_axial_mass;
-  k.ph_mpt = (T)c.anchor_point_mass;
-  k.ph_iadd_total = (T)(c.anchor_inertia * (double)c.n_cables);
-  k.ph_mass = (T)c.mass;
-  k.gx = (T)c.gravity[0];
-  k.gy = (T)c.gravity[1];
-  k.gz = (T)c.gravity[2];
-  k.fk_lambda = (T)c.fk_lambda;
-  k.fk_tol = (T)c.fk_tolerance;
-  k.fk_iters = (int)c.fk_max_iterations;
-  k.td_min = (T)c.td_f_min;
-  k.td_max = (T)c.td_f_max;
-  k.td_mid = (T)(0.5 * (c.td_f_min + c.td_f_max));
-}
 
 // a device copy of a host table (cdpr_create)
 template <typename T>
@@ -392,6 +318,15 @@ int upload_table(cdpr_engine* h, DevBuf<T>& d, const void* src, size_t bytes, co
 
 // the kind whose latched command a uniform handle in `mode` reads
 inline int cmd_kind_of_mode(int mode) { return mode == kModeVelocity ? (int)CDPR_COMMAND_VELOCITY : mode == kModeForce ? (int)CDPR_COMMAND_FORCE : (int)CDPR_COMMAND_POSITION; }
+
+// The argument record of the handle's current mode; the controller half of a general-path launch with the latched commands (null: none yet, target 0)
+inline int args_index(const cdpr_engine* h) { return args_index(h->plan, h->mode); }
+inline GenCtl general_ctl(const cdpr_engine* h) {
+  GenCtl g = h->args.gen[args_index(h)];
+  const auto latched = [h](int kind) { return h->cmd[kind].have ? h->cmd[kind].latched() : nullptr; };
+  g.vel_cmd = latched(CDPR_COMMAND_VELOCITY), g.pos_cmd = latched(CDPR_COMMAND_POSITION), g.frc_cmd = latched(CDPR_COMMAND_FORCE);
+  return g;
+}
 
 constexpr int kCallSat = 64;  // Pid call counts saturate here on the host (the kernels ask "0?", ">= nbuf?")
 inline int sat_pid_calls(int calls) { return calls < kCallSat ? calls : kCallSat; }
@@ -436,11 +371,7 @@ int set_device(cdpr_engine* h);
 int drain_copy_stream(cdpr_engine* h);
 int check_fault(cdpr_engine* h);
 int checked(cdpr_engine* h, int rc);
-void biquad_coefficients(const cdpr_filter_params_t& f, double co[5]);  // a0 a1 a2 b1 b2
 std::vector<float4> home_state(const cdpr_engine* h, uint32_t rows);
-void copy_pid(const StepArgs& src, StepArgs& dst);
-void copy_pid_alt(const StepArgs& src, PidSet& dst);
-GenCtl general_ctl(const cdpr_engine* h);
 // cdpr_engine_launch.hip
 double sim_time(uint64_t step, double dt);
 LaunchShape launch_shape(const cdpr_engine* h, int k, bool steady = false, const Schedule* sched = nullptr);
@@ -482,7 +413,7 @@ inline FastRecords fast_records(const cdpr_engine* h) {
 inline GenRecords gen_records(const cdpr_engine* h) {
   GenRecords v{};
   v.plat = plat_rows(h);
-  v.rec = h->d_rec, v.lay = h->glay;
+  v.rec = h->d_rec, v.lay = h->args.glay;
   v.mode = h->d_mode, v.episode_start = h->d_episode;
   for (int k = 0; k < kCmdKinds; ++k) v.latched[k] = h->cmd[k].d[0];
   v.batch = h->batch, v.n = h->n;
@@ -494,7 +425,7 @@ inline F64Records f64_records(const cdpr_engine* h) {
   v.meta = h->d_mode, v.target = h->d_target, v.episode_start = h->d_episode;
   v.stride = h->stride, v.state_rows = (uint32_t)state64_rows(h), v.obs_rows = (uint32_t)f64_obs_rows((int)h->n);
   v.batch = h->batch, v.n = h->n;
-  v.hold = h->plan.hold64 ? 1u : 0u, v.hold_win = (uint32_t)hold_win(h), v.win = (uint32_t)win64(h);
+  v.hold = h->plan.hold64 ? 1u : 0u, v.hold_win = (uint32_t)hold_win(h->plan), v.win = (uint32_t)win64(h->plan);
   for (int c = 0; c < 7; ++c) v.home[c] = h->cfg.home_pose[c];
   return v;
 }

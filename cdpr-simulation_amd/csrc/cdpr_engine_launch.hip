@@ -1,7 +1,8 @@
 // cdpr_engine_launch.hip - what turns "advance n world steps" into launches: the latch of the pending commands, the clock of the chain
 // the three paths share (run_chain, cdpr_engine_internal.hpp: publish_mask, advance_clock), the register-resident path's launches with their hipGraph replay
 // (run_steps), the general controller path's (run_steps_general; precision = 64: run_steps_f64, cdpr_engine_f64.hip), and command
-// schedules (scheduled_update).  Reference paths as in cdpr_engine.hip.
+// schedules (scheduled_update).  Every launch copies the handle's argument record of the current mode (h->args, cdpr_launch_args.hpp) and
+// assigns the per-launch fields listed at the top of that header.  Reference paths as in cdpr_engine.hip.
 #include "cdpr_engine_internal.hpp"
 
 namespace cdpr {
@@ -72,7 +73,8 @@ void advance_clock(cdpr_engine* h, int k, int launches) {
 // Weights of ring position `slot`, copied into a launch's arguments (see StepArgs::wrow).
 static void set_weight_row(const cdpr_engine* h, StepArgs& a, int slot) {
   // (per-robot handles: both Pids share one window, so the velocity Pid's table serves every lane)
-  memcpy(a.wrow, &h->wtab_host[(h->plan.per_robot || h->mode == kModeVelocity) ? 0 : 1][slot * (kWin + 2)], sizeof a.wrow);
+  const int table = (h->plan.per_robot || h->mode == kModeVelocity) ? 0 : kWin;  // first row of [velocity | position]
+  memcpy(a.wrow, &h->args.wtab[(size_t)(table + slot) * (kWin + 2)], sizeof a.wrow);
 }
 
 // The kernel a launch uses: the routing is planned_kernel's (cdpr_select.hpp: a pure function of the handle's plan and the
@@ -123,34 +125,13 @@ static bool split_steady_launch(const cdpr_engine* h, const StepArgs& a) {
   return split_steady_handle(h) && steps_since_load(h) != 0 && h->mode != kModeForce && a.pid_calls != 0 && a.pid_calls >= a.nbuf && !a.dbg && !a.travel_on;
 }
 
-// What every launch over the handle's own state starts from: the constants, the state and observable rows, the `pid` topic's rows, the
-// geometry; with a trajectory record, one observable image per step (the chain points `obs` at the launch's first).
-static StepArgs handle_args(const cdpr_engine* h, const void* record) {
-  StepArgs a = h->base;
-  a.state = h->d_state;
-  a.obs = h->d_obs;
-  a.dbg = h->dbg ? h->d_dbg : nullptr;
-  a.geom = h->d_geom;
-  a.batch = h->batch;
-  a.stride = h->stride;
-  a.obs_step_stride = record ? (size_t)h->n_obs * h->stride : 0;
-  return a;
-}
-
-// ... and what the register-resident path adds for a whole call: the Pid(s), the command rows, the mode's flags; with a schedule (a whole
-// one in one launch; publish_period == 0, every step but world step 0 is published) its batches, mailbox and status word.
+// What the register-resident path adds to the record of the handle's mode for a whole call: the latched command rows (per-robot handles:
+// the active target rows are bound in the record), a trajectory record's stride; with a schedule (a whole one in one launch;
+// publish_period == 0, every step but world step 0 is published) its batches, mailbox and status word.
 static StepArgs fast_path_args(const cdpr_engine* h, const void* record, const Schedule* sched) {
-  StepArgs a = handle_args(h, record);
-  if (h->plan.per_robot) {
-    copy_pid(h->pid_vel, a);
-    copy_pid_alt(h->pid_pos, a.alt);
-    a.cmd = h->d_target;
-    a.meta = h->d_mode;
-  } else {
-    copy_pid(h->mode == kModeVelocity ? h->pid_vel : h->pid_pos, a);  // (Force mode: unused, no Pid runs)
-    a.cmd = h->cmd[cmd_kind_of_mode(h->mode)].latched();  // position: all zeros until the first jointPositions message: target 0 (PLG.cpp:153-157)
-    a.flags = h->mode == kModeVelocity ? kFlagActualIsVelocity : h->mode == kModeForce ? kFlagForceMode : 0u;
-  }
+  StepArgs a = h->args.step[args_index(h)];
+  if (!h->plan.per_robot) a.cmd = h->cmd[cmd_kind_of_mode(h->mode)].latched();  // position: all zeros until the first jointPositions message: target 0 (PLG.cpp:153-157)
+  a.obs_step_stride = record ? (size_t)h->n_obs * h->stride : 0;
   if (sched) {
     a.flags |= kFlagPublishAll;
     a.sched_refresh = sched->refresh;
@@ -179,34 +160,24 @@ int warm_first_launch(cdpr_engine* h) {
   HIP_TRY(h, cm.alloc((size_t)rows * h->n * sizeof(float)));
   HIP_TRY(h, hipMemcpyAsync(st.p, s.data(), s.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemsetAsync(cm.p, 0, (size_t)rows * h->n * sizeof(float), h->stream));
-  StepArgs a = h->base;
-  a.state = st.as<float4>();
-  a.obs = ob.as<float4>();
-  a.cmd = cm.as<float>();
-  a.dbg = nullptr;
-  a.geom = h->d_geom;
-  a.batch = pk.robots_per_block;
-  a.stride = rows;
+  StepArgs a = h->args.step[args_index(h)];  // Position mode, where a fresh handle stands, over the scratch robots
+  a.state = st.as<float4>(), a.obs = ob.as<float4>(), a.cmd = cm.as<float>(), a.meta = mt.as<uint8_t>(), a.dbg = nullptr;
+  a.batch = pk.robots_per_block, a.stride = rows;
   a.nsteps = 1;
-  a.obs_step_stride = 0;
-  a.flags = 0u;
   a.publish_mask = 1ull;
-  copy_pid(h->plan.per_robot ? h->pid_vel : h->pid_pos, a);
-  copy_pid_alt(h->pid_pos, a.alt);
-  a.meta = mt.as<uint8_t>();
   a.pid_calls = kCallSat;  // steady state: every branch of the step is taken, as in the launches that follow
   a.ring_slot = 0;
   set_weight_row(h, a, 0);
   hipLaunchKernelGGL(step_entry(pk), dim3(1), dim3(pk.block), 0, h->stream, a);
   HIP_TRY(h, hipGetLastError());
   // ... and of the role-split kernel's steady-state instantiations, which the launches take from the step on that fills the window
-  // (split_steady_launch): both modes' - a Joy of the other kind may arrive at any step
+  // (split_steady_launch): both modes' - a Joy of the other kind may arrive at any step (the mode is the instantiation's, the gains do
+  // not matter to a launch whose results are dropped)
   for (const bool vel : {false, true}) {
     LaunchShape shape = launch_shape(h, 1);
     shape.split_steady = split_steady_handle(h), shape.vel = vel;
     const PlannedKernel steady = planned_kernel(h->plan, shape);
     if (!steady.steady) break;
-    copy_pid(vel ? h->pid_vel : h->pid_pos, a);
     hipLaunchKernelGGL(step_entry(steady), dim3(1), dim3(steady.block), 0, h->stream, a);
     HIP_TRY(h, hipGetLastError());
   }
@@ -241,12 +212,12 @@ static int launch_step(cdpr_engine* h, StepKernel kern, const PlannedKernel& pk,
 // the general path's hot rows back into the H slots (cdpr_gen_flush_hot_kernel) before a Pid's records are reset or latched over
 static void flush_hot(cdpr_engine* h) {
   if (!h->d_rec || !h->plan.gen_hot) return;
-  hipLaunchKernelGGL(cdpr_gen_flush_hot_kernel, robot_grid(h), dim3(kRobotBlock), 0, h->stream, std::max(h->gpid[0].nbuf, 1), gen_records(h));
+  hipLaunchKernelGGL(cdpr_gen_flush_hot_kernel, robot_grid(h), dim3(kRobotBlock), 0, h->stream, std::max(h->args.pid[kPidPosition].nbuf, 1), gen_records(h));
 }
 
 // Pid::reset of one Pid of every cable (general path): its slots, its rows
 static hipError_t reset_block(cdpr_engine* h, int which) {
-  const GenLayout& L = h->glay;
+  const GenLayout& L = h->args.glay;
   flush_hot(h);
   hipError_t e1 = hipMemsetAsync(h->d_rec + (size_t)L.block_a(which, 0) * h->stride * 4, 0, (size_t)L.pid_slots() * h->stride * 16, h->stream);
   if (e1 != hipSuccess || L.pid_rows() == 0) return e1;
@@ -256,7 +227,7 @@ static hipError_t reset_block(cdpr_engine* h, int which) {
 // precision = 64 with the hold branch: Pid::reset of one Pid of every cable (its rows behind the state)
 static hipError_t reset_block64(cdpr_engine* h, int which) {
   for (uint32_t i = 0; i < h->n; ++i) {
-    hipError_t e1 = hipMemsetAsync(h->d_state64 + (size_t)f64_hold_row((int)h->n, (int)i, which, hold_win(h)) * h->stride, 0, (size_t)hold_pid_rows(hold_win(h)) * h->stride * sizeof(double),
+    hipError_t e1 = hipMemsetAsync(h->d_state64 + (size_t)f64_hold_row((int)h->n, (int)i, which, hold_win(h->plan)) * h->stride, 0, (size_t)hold_pid_rows(hold_win(h->plan)) * h->stride * sizeof(double),
                                    h->stream);
     if (e1 != hipSuccess) return e1;
   }
@@ -330,10 +301,8 @@ static int latch_pending(cdpr_engine* h, bool& reset_pid) {
 // General controller path: ONE launch per `per_launch` world steps (cdpr_general_step.hpp); with `record`, the observable
 // image of step j of the call goes to record + j * n_obs * stride.
 static int run_steps_general(cdpr_engine* h, int nsteps, int per_launch, void* record) {
-  StepArgs a = handle_args(h, record);  // (run_steps has asked general_clock_check: world-step stamps are int32 in the controller records)
-  a.cmd = nullptr;
-  a.pid_calls = 0;
-  copy_pid(h->pid_pos, a);  // unused
+  StepArgs a = h->args.step[args_index(h)];  // (run_steps has asked general_clock_check: world-step stamps are int32 in the controller records)
+  a.obs_step_stride = record ? (size_t)h->n_obs * h->stride : 0;
   GenCtl g = general_ctl(h);
   // where the role-split one-step kernel serves the handle, its launches beat the one-wave kernel's multi-step ones
   // (16 384 x 8: 9.2 against 13.7 us per step, 32 768: 10.1 against 21.6; same bits): fused updates and the trajectory
@@ -551,7 +520,7 @@ int scheduled_update(cdpr_engine* h, uint32_t kind, int nsteps, int refresh_step
     int rest = nsteps - done;
     if (h->plan.lane_pair && h->plan.pair_stream && !h->plan.fk && !h->plan.td && kind != CDPR_COMMAND_FORCE) {
       const int new_mode = (kind == CDPR_COMMAND_VELOCITY) ? kModeVelocity : kModePosition;
-      const int nbuf = (kind == CDPR_COMMAND_VELOCITY) ? h->pid_vel.nbuf : h->pid_pos.nbuf;
+      const int nbuf = h->args.pid[kind == CDPR_COMMAND_VELOCITY ? kPidVelocity : kPidPosition].nbuf;
       const int calls = (h->mode == new_mode) ? h->pid_calls : 0;  // (entering the mode resets the Pid)
       const int fill = (calls >= nbuf ? 0 : nbuf - calls) + (steps_since_load(h) == 0 ? 1 : 0);
       const int pre = ((fill + refresh_steps - 1) / refresh_steps) * refresh_steps;  // whole batches

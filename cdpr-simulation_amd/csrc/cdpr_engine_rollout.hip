@@ -1,84 +1,52 @@
 // cdpr_engine_rollout.hip - cdpr_rollout_velocity*: the MPC fan-out (BASELINE config 5) on register-resident, general-path and
-// precision = 64 handles.
+// precision = 64 handles, from the handle's argument record of Velocity mode (cdpr_launch_args.hpp).
 #include "cdpr_engine_internal.hpp"
 
 namespace cdpr_host {
 
 static int rollout_enqueue(cdpr_engine* h, int samples, int horizon, const float* d_commands, const float* d_ref, float* d_cost) {
   if (h->plan.fp64) return rollout_enqueue_f64(h, samples, horizon, d_commands, d_ref, d_cost);
+  const uint64_t traj = (uint64_t)h->batch * (uint64_t)samples;
+  LaunchShape rs = launch_shape(h, horizon);
+  rs.rollout = true;
+  const PlannedKernel pk = planned_kernel(h->plan, rs);
+  // the record of Velocity mode, whatever mode the handle is in (per-robot handles: the mode per lane; general path: the mode rides in
+  // GenCtl); the commands come from roll_cmd, nothing is published
+  StepArgs a = h->args.step[args_index(h->plan, kModeVelocity)];
+  a.cmd = nullptr;
+  a.dbg = nullptr;
+  a.nsteps = horizon;
+  if (steps_since_load(h) == 0) a.flags |= kFlagFirstWorldStep;
+  a.roll_cmd = d_commands;
+  a.roll_ref = d_ref;
+  a.roll_cost = d_cost;
+  a.roll_samples = (uint32_t)samples;
   if (h->plan.general) {
     // every trajectory steps a private copy of its robot's controller records (both Pids of every cable: the hold branch
     // switches between them from step to step): one column per trajectory in a persistent, grow-only scratch
-    const uint64_t traj = (uint64_t)h->batch * (uint64_t)samples;
     const size_t cols = (size_t)((traj + 63u) & ~(uint64_t)63u);
-    const size_t bytes = h->glay.bytes(cols);
-    if (bytes >= (1ull << 32)) {
+    if (h->args.glay.bytes(cols) >= (1ull << 32)) {
       h->err = "rollout on the general controller path: the trajectories' controller records pass 4 GiB; use fewer samples per call";
       return CDPR_ERR_UNSUPPORTED;
     }
     h->roll_rec_cols = std::max(cols, h->roll_rec_cols);  // (the records' column stride: never shrinks)
-    HIP_TRY(h, h->d_roll_rec.ensure(h, h->glay.bytes(h->roll_rec_cols)));
-    StepArgs a = h->base;
-    a.state = h->d_state;
-    a.obs = h->d_obs;
-    a.geom = h->d_geom;
-    a.batch = h->batch;
-    a.stride = h->stride;
-    a.nsteps = horizon;
-    a.publish_mask = 0;
-    copy_pid(h->pid_vel, a);  // unused
-    a.flags = (steps_since_load(h) == 0) ? kFlagFirstWorldStep : 0u;
-    a.roll_cmd = d_commands;
-    a.roll_ref = d_ref;
-    a.roll_cost = d_cost;
-    a.roll_samples = (uint32_t)samples;
+    HIP_TRY(h, h->d_roll_rec.ensure(h, h->args.glay.bytes(h->roll_rec_cols)));
     GenCtl g = general_ctl(h);
     g.src_rec = h->d_rec;
     g.src_rstride = h->stride;
     g.rec = h->d_roll_rec;
     g.rstride = (uint32_t)h->roll_rec_cols;
-    g.rec_bytes = (uint32_t)h->glay.bytes(h->roll_rec_cols);
+    g.rec_bytes = (uint32_t)h->args.glay.bytes(h->roll_rec_cols);
     g.now_step = (int)h->step;
-    LaunchShape rs = launch_shape(h, horizon);
-    rs.rollout = true;
-    const PlannedKernel pk = planned_kernel(h->plan, rs);
     hipLaunchKernelGGL(gen_entry(pk), dim3(pk.grid(traj)), dim3(pk.block), 0, h->stream, a, g);
-    HIP_TRY(h, hipGetLastError());
-    h->last_kernel = pk;
-    ++h->launches;
-    return CDPR_OK;
+  } else {
+    // a Joy on jointVelocities while in Position mode resets the velocity Pid (JFC.cpp:113-115); the handle's own
+    // records stay untouched, the rollout starts from zeroed copies (per-robot handles: decided per lane from meta)
+    if (!h->plan.per_robot && h->mode != kModeVelocity) a.flags |= kFlagRolloutResetPid;
+    a.pid_calls = (h->mode == kModeVelocity) ? sat_pid_calls(h->pid_calls) : 0;
+    a.ring_slot = ring_slot_of(h->step);
+    hipLaunchKernelGGL(step_entry(pk), dim3(pk.grid(traj)), dim3(pk.block), 0, h->stream, a);
   }
-  StepArgs a = h->base;
-  a.state = h->d_state;
-  a.obs = h->d_obs;
-  a.cmd = nullptr;
-  a.dbg = nullptr;
-  a.geom = h->d_geom;
-  a.batch = h->batch;
-  a.stride = h->stride;
-  a.nsteps = horizon;
-  a.publish_mask = 0;
-  copy_pid(h->pid_vel, a);
-  a.flags = kFlagActualIsVelocity;
-  if (steps_since_load(h) == 0) a.flags |= kFlagFirstWorldStep;
-  // a Joy on jointVelocities while in Position mode resets the velocity Pid (JFC.cpp:113-115); the handle's own
-  // records stay untouched, the rollout starts from zeroed copies (per-robot handles: decided per lane from meta)
-  if (!h->plan.per_robot && h->mode != kModeVelocity) a.flags |= kFlagRolloutResetPid;
-  a.pid_calls = (h->mode == kModeVelocity) ? sat_pid_calls(h->pid_calls) : 0;
-  a.ring_slot = ring_slot_of(h->step);
-  if (h->plan.per_robot) {
-    copy_pid_alt(h->pid_pos, a.alt);
-    a.meta = h->d_mode;
-  }
-  a.roll_cmd = d_commands;
-  a.roll_ref = d_ref;
-  a.roll_cost = d_cost;
-  a.roll_samples = (uint32_t)samples;
-  const uint64_t traj = (uint64_t)h->batch * (uint64_t)samples;
-  LaunchShape rs = launch_shape(h, horizon);
-  rs.rollout = true;
-  const PlannedKernel pk = planned_kernel(h->plan, rs);
-  hipLaunchKernelGGL(step_entry(pk), dim3(pk.grid(traj)), dim3(pk.block), 0, h->stream, a);
   HIP_TRY(h, hipGetLastError());
   h->last_kernel = pk;
   ++h->launches;

@@ -112,9 +112,9 @@ int cdpr_solve_fk(cdpr_handle_t h, const float* lengths, const float* seed7, flo
   a.pose_out = dp.as<float>();
   a.residual = dr.as<float>();
   a.iters = di.as<int32_t>();
-  a.fk_lambda = h->base.fk_lambda;
-  a.fk_tol = h->base.fk_tol;
-  a.fk_iters = h->base.fk_iters > 0 ? h->base.fk_iters : 4;
+  a.fk_lambda = h->args.step[0].fk_lambda;
+  a.fk_tol = h->args.step[0].fk_tol;
+  a.fk_iters = h->args.step[0].fk_iters > 0 ? h->args.step[0].fk_iters : 4;
   hipLaunchKernelGGL(k, dim3((h->batch + 63u) / 64u), dim3(64), 0, h->stream, a);
   HIP_TRY(h, hipGetLastError());
   DOWN(pose7, dp, B * 7, float);
@@ -149,9 +149,9 @@ int cdpr_solve_td(cdpr_handle_t h, const float* pose7, const float* wrench6, flo
   a.wrench6 = dw.as<float>();
   a.tension = dt.as<float>();
   a.flag = df.as<int32_t>();
-  a.td_min = h->base.td_min;
-  a.td_max = h->base.td_max;
-  a.td_mid = h->base.td_mid;
+  a.td_min = h->args.step[0].td_min;
+  a.td_max = h->args.step[0].td_max;
+  a.td_mid = h->args.step[0].td_mid;
   hipLaunchKernelGGL(k, dim3((h->batch + 63u) / 64u), dim3(64), 0, h->stream, a);
   HIP_TRY(h, hipGetLastError());
   DOWN(tension, dt, B * n, float);
