@@ -507,7 +507,61 @@ __global__ __launch_bounds__(64, 1) void cdpr_onestep_kernel(const StepArgs a_in
 #ifndef CDPR_STEADY_NEWTON_WRITTEN_OUT
 #define CDPR_STEADY_NEWTON_WRITTEN_OUT 1  // 1 = the steady kernel's Newton stage is four iterations written out; 0 = the generic loop (A/B of the two items)
 #endif
+#ifndef CDPR_EST_PIN_FACTOR
+#define CDPR_EST_PIN_FACTOR 1  // 1 = the estimator wave (every instantiation) holds the tension distribution's factor in front of barrier #1 by an empty asm;
+#endif                         //     0 = the compiler places it (A/B: scripts/build_variants.sh pin0)
+#ifndef CDPR_STEADY_SHARED_ROT
+#define CDPR_STEADY_SHARED_ROT 1  // 1 = with the shared IK the estimator wave hands the true state's rotation matrix over as well (nine rows through LDS)
+#endif                            //     and the controller wave's world step takes it; 0 = the controller wave evaluates it behind barrier #2
 constexpr int kIkRows = 7;  // v2f rows per cable pair of that hand-over: L, u (3), (R b) x u (3)
+constexpr bool kSteadySharedRot = CDPR_STEADY_SHARED_IK && CDPR_STEADY_SHARED_ROT;
+
+// The orientation of the estimator wave's pose estimate through the Newton stage, held as the pairs (x, y), (z, w) that quat_to_rot_pk and
+// quat_apply_rotvec_pk work on (CDPR_QUAT_PK = 0: the scalar stages on the halves).  Row 4 of the state keeps its layout.
+struct EstQuat {
+  v2f a, b;
+};
+CDPR_DEV EstQuat est_quat(const float4& v) { return EstQuat{(v2f){v.x, v.y}, (v2f){v.z, v.w}}; }
+CDPR_DEV float4 est_quat_row(const EstQuat& q) { return make_float4(q.a.x, q.a.y, q.b.x, q.b.y); }
+template <int N>
+CDPR_DEV void est_ik(const float* geo, float x, float y, float z, const EstQuat& q, v2f (&len)[cable_pairs(N)], v2f (&jac)[cable_pairs(N)][6],
+                     v2f (&l0)[cable_pairs(N)]) {
+#if CDPR_QUAT_PK
+  ik_pairs_pk<N, false>(geo, x, y, z, quat_to_rot_pk(q.a, q.b), len, jac, l0);
+#else
+  ik_pairs<N, false>(geo, x, y, z, q.a.x, q.a.y, q.b.x, q.b.y, len, jac, l0);
+#endif
+}
+CDPR_DEV void est_rotate(EstQuat& q, float tx, float ty, float tz) {
+#if CDPR_QUAT_PK
+  quat_apply_rotvec_pk(q.a, q.b, tx, ty, tz);
+#else
+  float x = q.a.x, y = q.a.y, z = q.b.x, w = q.b.y;
+  quat_apply_rotvec(x, y, z, w, tx, ty, tz);
+  q = EstQuat{(v2f){x, y}, (v2f){z, w}};
+#endif
+}
+// The rotation matrix of the TRUE state's quaternion (rows 0 and 1 of the state) as the role-split waves form it, and the IK rows at the
+// true state with it: the world step (integrate_velocity) takes the same matrix.
+CDPR_DEV Rot true_state_rot(float qx, float qy, float qz, float qw) {
+#if CDPR_QUAT_PK
+  return unpack_rot(quat_to_rot_pk((v2f){qx, qy}, (v2f){qz, qw}));
+#else
+  return quat_to_rot(qx, qy, qz, qw);
+#endif
+}
+template <int N, bool WANT_L0>
+CDPR_DEV Rot true_state_ik(const float* geo, float px, float py, float pz, float qx, float qy, float qz, float qw, v2f (&len)[cable_pairs(N)],
+                           v2f (&jac)[cable_pairs(N)][6], v2f (&l0)[cable_pairs(N)]) {
+#if CDPR_QUAT_PK
+  const RotPk r = quat_to_rot_pk((v2f){qx, qy}, (v2f){qz, qw});
+  ik_pairs_pk<N, WANT_L0>(geo, px, py, pz, r, len, jac, l0);
+  return unpack_rot(r);
+#else
+  ik_pairs<N, WANT_L0>(geo, px, py, pz, qx, qy, qz, qw, len, jac, l0);
+  return quat_to_rot(qx, qy, qz, qw);  // (ik_pairs' own evaluation: the compiler keeps one)
+#endif
+}
 #ifdef CDPR_STAMPS
 #define CDPR_SPLIT_STAMP(i)                                                                                          \
   do {                                                                                                               \
@@ -540,13 +594,23 @@ constexpr int kIkRows = 7;  // v2f rows per cable pair of that hand-over: L, u (
 //     issues its row loads, goes to #0 (it is there first: this wave does not wait) and reads the rows instead of calling ik_pairs; L0
 //     comes from its geometry table.  The generic kernel evaluates them in both waves (the estimator needs the lengths only, so the
 //     compiler drops its unit vectors and cross products there).
-// Static counts of both waves, before and after: scripts/split_ctl_counts.py, profiles/r11_split_est_instruction_counts.txt.
+//  3. (CDPR_STEADY_SHARED_ROT, with 2) The rotation matrix of the true state's quaternion, which that IK evaluation forms, goes the same way: nine
+//     float rows of 64 lanes (x_rot: r00 r01 r02 r10 .. r22, 2.25 KiB) written next to the IK rows in front of barrier #0.  The controller wave
+//     reads them behind barrier #2 and gives them to integrate_velocity's overload instead of evaluating quat_to_rot in its tail.
+//  4. The iteration count is not handed over: steady launches run four iterations, every one counts, so the controller wave publishes the
+//     literal 4 and x_est row 4 is not written.
+// In EVERY instantiation (CDPR_QUAT_PK) the orientation estimate is held through the Newton stage as the pairs (x, y), (z, w) (EstQuat) and the
+// stages on it are the pair forms of cdpr_step_kernel.hpp - quat_to_rot_pk, ik_rows_pk, quat_apply_rotvec_pk: the scalar stages' operations on
+// the same operands, bit for bit (tests/test_gpu_quat_stages.py holds them against the one-wave kernel, which keeps the scalar stages) - and the
+// tension distribution's factor is pinned in front of barrier #1 (CDPR_EST_PIN_FACTOR, see there).
+// Static counts of both waves, before and after: scripts/split_ctl_counts.py, profiles/r11_split_est_instruction_counts.txt (items 1, 2),
+// profiles/r22_split_quat_instruction_counts.txt (item 3 and the pair forms).
 // Measured per item (profiles/r11_headline_steady_estimator_ab.txt): 2 is the gain; 1 ALONE is no faster than the generic loop (the compiler then
 // moves the tension distribution's factor behind barrier #1) and worth 0.1 us per step on top of 2.
 template <int N, int XS, int ES, bool RAISED = true, bool STEADY = false>
 CDPR_DEV void split_estimator_wave(const StepArgs& a, float* geo, float gval, uint32_t lane, bool live, size_t st, uint32_t off, uint32_t woff,
                                    const float4& p0, const float4& p1, const float4& p3, const v2f* x_force, v2f* x_tension, float* x_est,
-                                   v2f* x_ik = nullptr) {
+                                   v2f* x_ik = nullptr, float* x_rot = nullptr) {
   constexpr int NP = cable_pairs(N);
 #if defined(CDPR_STAMPS) && defined(CDPR_STAMPS_CLOCK)  // the shader clock over this wave: s_memtime ticks between entry and stamp 3, into slot 7
   const unsigned long long clk0 = __builtin_amdgcn_s_memtime();
@@ -561,12 +625,24 @@ CDPR_DEV void split_estimator_wave(const StepArgs& a, float* geo, float gval, ui
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  float fkx = p3.y, fky = p3.z, fkz = p3.w, fkqx = p4.x, fkqy = p4.y, fkqz = p4.z, fkqw = p4.w;
+  float fkx = p3.y, fky = p3.z, fkz = p3.w;
+  EstQuat fkq = est_quat(p4);
   v2f len[NP];
   {
     v2f jac[NP][6], l0[NP];  // only the measured lengths L* are kept of the true-state evaluation
-    ik_pairs<N, false>(geo, p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, len, jac, l0);
+    float tqx = p0.w, tqy = p1.x, tqz = p1.y, tqw = p1.z;
+#if CDPR_QUAT_PK
+    // (the rows arrive in the kernel's prologue, which both waves run: left free, the compiler lines these four up as pairs THERE, and the
+    //  controller wave carries two registers more through its PID stage, its register peak)
+    asm volatile("" : "+v"(tqx), "+v"(tqy), "+v"(tqz), "+v"(tqw));
+#endif
+    const Rot r = true_state_ik<N, false>(geo, p0.x, p0.y, p0.z, tqx, tqy, tqz, tqw, len, jac, l0);
     if (STEADY && CDPR_STEADY_SHARED_IK) {  // ... and the whole of it goes to the controller wave, which evaluates none itself
+      if (kSteadySharedRot) {  // ... with the matrix itself, which its world step needs (integrate_velocity)
+        x_rot[0 * 64 + lane] = r.r00, x_rot[1 * 64 + lane] = r.r01, x_rot[2 * 64 + lane] = r.r02;
+        x_rot[3 * 64 + lane] = r.r10, x_rot[4 * 64 + lane] = r.r11, x_rot[5 * 64 + lane] = r.r12;
+        x_rot[6 * 64 + lane] = r.r20, x_rot[7 * 64 + lane] = r.r21, x_rot[8 * 64 + lane] = r.r22;
+      }
 #pragma unroll
       for (int k = 0; k < NP; ++k) {
         x_ik[(kIkRows * k) * 64 + lane] = len[k];
@@ -588,7 +664,7 @@ CDPR_DEV void split_estimator_wave(const StepArgs& a, float* geo, float gval, ui
       // and counts in every iteration - the four iterations written out, without the test, the mask and the counter
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
-        ik_pairs<N, false>(geo, fkx, fky, fkz, fkqx, fkqy, fkqz, fkqw, elen, jest, unused);
+        est_ik<N>(geo, fkx, fky, fkz, fkq, elen, jest, unused);
         v2f res[NP];
 #pragma unroll
         for (int k = 0; k < NP; ++k) res[k] = len[k] - elen[k];
@@ -598,10 +674,10 @@ CDPR_DEV void split_estimator_wave(const StepArgs& a, float* geo, float gval, ui
         fkx += g[0];
         fky += g[1];
         fkz += g[2];
-        quat_apply_rotvec(fkqx, fkqy, fkqz, fkqw, g[3], g[4], g[5]);
+        est_rotate(fkq, g[3], g[4], g[5]);
 #ifdef CDPR_STAMPS_ITER
         if (it < 3) {
-          asm volatile("" ::"v"(fkqw));
+          asm volatile("" ::"v"(est_quat_row(fkq).w));
           __builtin_amdgcn_sched_barrier(0);
           if (a.stamps && lane == 0) a.stamps[(size_t)blockIdx.x * 8 + 4 + it] = __builtin_amdgcn_s_memrealtime();
           __builtin_amdgcn_sched_barrier(0);
@@ -612,7 +688,7 @@ CDPR_DEV void split_estimator_wave(const StepArgs& a, float* geo, float gval, ui
     } else {
       bool active = true;
       for (int it = 0; it < a.fk_iters; ++it) {
-        ik_pairs<N, false>(geo, fkx, fky, fkz, fkqx, fkqy, fkqz, fkqw, elen, jest, unused);
+        est_ik<N>(geo, fkx, fky, fkz, fkq, elen, jest, unused);
         v2f res[NP];
         v2f rm = splat(0.f);
 #pragma unroll
@@ -628,12 +704,12 @@ CDPR_DEV void split_estimator_wave(const StepArgs& a, float* geo, float gval, ui
           fkx += g[0];
           fky += g[1];
           fkz += g[2];
-          quat_apply_rotvec(fkqx, fkqy, fkqz, fkqw, g[3], g[4], g[5]);
+          est_rotate(fkq, g[3], g[4], g[5]);
           ++fk_it;
         }
 #ifdef CDPR_STAMPS_ITER
         if (it < 3) {
-          asm volatile("" ::"v"(fkqw));
+          asm volatile("" ::"v"(est_quat_row(fkq).w));
           __builtin_amdgcn_sched_barrier(0);
           if (a.stamps && lane == 0) a.stamps[(size_t)blockIdx.x * 8 + 4 + it] = __builtin_amdgcn_s_memrealtime();
           __builtin_amdgcn_sched_barrier(0);
@@ -641,19 +717,25 @@ CDPR_DEV void split_estimator_wave(const StepArgs& a, float* geo, float gval, ui
 #endif
       }
     }
-    ik_pairs<N, false>(geo, fkx, fky, fkz, fkqx, fkqy, fkqz, fkqw, elen, jest, unused);
+    est_ik<N>(geo, fkx, fky, fkz, fkq, elen, jest, unused);
     v2f rm = splat(0.f);
 #pragma unroll
     for (int k = 0; k < NP; ++k) rm = max2(rm, abs2(len[k] - elen[k]));
     fk_res = fmaxf(rm.x, rm.y);
   }
-  if (live) store_slot_aux<CDPR_SPLIT_PLAT_AUX>(a.state, st, 4, woff, make_float4(fkqx, fkqy, fkqz, fkqw));
+  if (live) store_slot_aux<CDPR_SPLIT_PLAT_AUX>(a.state, st, 4, woff, est_quat_row(fkq));
   CDPR_SPLIT_STAMP(1);
   // the tension distribution's matrix and its factor need no forces: done while the controller wave may still be busy
   v2f td_l[6][3];
   float td_invd[6];
   normal_matrix_pk<NP, false>(jest, 0.f, td_l);
   chol_factor_pk(td_l, td_invd);
+#if CDPR_EST_PIN_FACTOR
+  // (pinned in front of the barrier: the last pivot has the whole factor and the closing evaluation's structure matrix upstream, the
+  //  residual its lengths.  Left free, the compiler is at liberty to sink both behind barrier #1, onto the path after the force hand-off;
+  //  with the pair forms in it does, in every instantiation: 131 -> 391 vector instructions between #1 and #2 at n = 8.)
+  asm volatile("" ::"v"(td_invd[5]), "v"(fk_res));
+#endif
   __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): nothing of this wave's LDS traffic is pending
   __builtin_amdgcn_s_barrier();        // #1: the controller wave's forces are in x_force
   CDPR_SPLIT_STAMP(2);
@@ -686,7 +768,7 @@ CDPR_DEV void split_estimator_wave(const StepArgs& a, float* geo, float gval, ui
   x_est[1 * ES + lane] = fky;
   x_est[2 * ES + lane] = fkz;
   x_est[3 * ES + lane] = fk_res;
-  x_est[4 * ES + lane] = (float)fk_it;
+  if (!STEADY) x_est[4 * ES + lane] = (float)fk_it;  // (steady launches run four iterations: the controller wave knows)
   x_est[5 * ES + lane] = (float)td_flag;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -711,10 +793,14 @@ CDPR_DEV void split_estimator_wave(const StepArgs& a, float* geo, float gval, ui
 // rows through a buffer descriptor instead of a 64-bit address each, 0.2 us per step slower.  The clamps stay
 // max(min()) pairs: v_med3_f32 returns the LOWER bound for a NaN operand where the pair returns the upper one, so it is not bit-equal
 // for any of the bounds in use.
+// The world step takes the rotation matrix of the true quaternion from where it was formed (integrate_velocity's overload): the generic
+// instantiation from its own IK (true_state_ik: the pair form under CDPR_QUAT_PK; nine registers live across the PID stage, 247 -> 244 VGPRs
+// at n = 8), the steady one from the estimator wave's nine x_rot rows behind barrier #2 (CDPR_STEADY_SHARED_ROT; = 0: it forms the matrix in its
+// tail, as before).  STEADY: the iteration count it publishes is the literal 4 (the estimator wave hands none over).
 template <int N, bool PR, bool STEADY, bool VEL>
 CDPR_DEV void split_controller_wave(const StepArgs& a, float* geo, float gval, uint32_t lane, uint32_t r, uint32_t rr, bool live, size_t st, uint32_t off,
                                     uint32_t woff, const float4& p0, const float4& p1, const float4& p2, const float4& p3, v2f* x_force, const v2f* x_tension,
-                                    const float* x_est, const v2f* x_ik = nullptr) {
+                                    const float* x_est, const v2f* x_ik = nullptr, const float* x_rot = nullptr) {
   static_assert(!(STEADY && PR), "the steady instantiation serves uniform handles");
   constexpr int NP = cable_pairs(N);
   constexpr int P = plat_slots(true);
@@ -764,9 +850,11 @@ CDPR_DEV void split_controller_wave(const StepArgs& a, float* geo, float gval, u
 
   // ---- IK on the state at t_k; the structure matrix stays alive for the world step (this wave runs no Newton stage)
   v2f len[NP], q[NP], qd[NP], jac[NP][6];
+  constexpr bool kOwnIk = !(STEADY && CDPR_STEADY_SHARED_IK);
+  Rot rot;  // of the true state's quaternion: the IK's, kept for the world step
   {
     v2f l0[NP];
-    if (STEADY && CDPR_STEADY_SHARED_IK) {  // the estimator wave's rows (same function, same operands: same bits), L0 from the geometry table
+    if (!kOwnIk) {  // the estimator wave's rows (same function, same operands: same bits), L0 from the geometry table
       __builtin_amdgcn_s_barrier();         // #0: reached with nothing but the row loads issued, so the estimator wave never waits here
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 #pragma unroll
@@ -777,7 +865,7 @@ CDPR_DEV void split_controller_wave(const StepArgs& a, float* geo, float gval, u
         l0[k] = *reinterpret_cast<const v2f*>(geo + k * kGeomFloatsPerPair + 12);
       }
     } else {
-      ik_pairs<N, true>(geo, s.px, s.py, s.pz, s.qx, s.qy, s.qz, s.qw, len, jac, l0);
+      rot = true_state_ik<N, true>(geo, s.px, s.py, s.pz, s.qx, s.qy, s.qz, s.qw, len, jac, l0);
     }
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
@@ -879,7 +967,15 @@ CDPR_DEV void split_controller_wave(const StepArgs& a, float* geo, float gval, u
 #pragma unroll
   for (int k = 0; k < NP; ++k) applied[k] = x_tension[k * 64 + lane];
   const float fkx = x_est[0 * 64 + lane], fky = x_est[1 * 64 + lane], fkz = x_est[2 * 64 + lane], fk_res = x_est[3 * 64 + lane],
-              fk_it = x_est[4 * 64 + lane], td_flag = x_est[5 * 64 + lane];
+              fk_it = STEADY ? 4.f : x_est[4 * 64 + lane], td_flag = x_est[5 * 64 + lane];  // (steady launches: fk_iters == 4, every one runs)
+  if (!kOwnIk) {
+    if (kSteadySharedRot) {  // the estimator wave's matrix (same function, same operands: same bits)
+      rot = Rot{x_rot[0 * 64 + lane], x_rot[1 * 64 + lane], x_rot[2 * 64 + lane], x_rot[3 * 64 + lane], x_rot[4 * 64 + lane],
+                x_rot[5 * 64 + lane], x_rot[6 * 64 + lane], x_rot[7 * 64 + lane], x_rot[8 * 64 + lane]};
+    } else {
+      rot = true_state_rot(s.qx, s.qy, s.qz, s.qw);
+    }
+  }
   setforce_limits<NP>(a, qd, applied);
   if (!STEADY && a.dbg && live) write_pid_topic(a.dbg + (size_t)r * 9, dbg_wrote, dbg_wrote, dbg_p, dbg_i, dbg_d, desired[0].x, applied[0].x);
   if (publish && live) {
@@ -908,7 +1004,7 @@ CDPR_DEV void split_controller_wave(const StepArgs& a, float* geo, float gval, u
     w[3] = -w[3];
     w[4] = -w[4];
     w[5] = -w[5];
-    integrate(a, s, w);
+    integrate(a, s, w, rot);
   }
   if (live) {
     store_slot_aux<CDPR_SPLIT_PLAT_AUX>(a.state, st, 0, woff, make_float4(s.px, s.py, s.pz, s.qx));
@@ -931,9 +1027,14 @@ CDPR_DEV void split_kernel_body(const StepArgs& a) {
   __shared__ v2f x_tension[NP][64];    // estimator -> controller: distributed tensions (before the SetForce limits)
   __shared__ float x_est[6][64];       // estimator -> controller: fk x y z, residual, iterations, infeasible flag
   v2f* x_ik = nullptr;                 // estimator -> controller, steady kernel only: the IK rows at the true state (14 KiB at n = 8)
+  float* x_rot = nullptr;              // ... and its rotation matrix, nine rows (2.25 KiB)
   if constexpr (STEADY && CDPR_STEADY_SHARED_IK) {
     __shared__ v2f ik_rows_at_state[kIkRows * NP][64];
     x_ik = &ik_rows_at_state[0][0];
+    if constexpr (kSteadySharedRot) {
+      __shared__ float rot_at_state[9][64];
+      x_rot = &rot_at_state[0][0];
+    }
   }
 
   // which of the two waves estimates: swapped from workgroup to workgroup (bits of the workgroup index chosen by the
@@ -957,10 +1058,10 @@ CDPR_DEV void split_kernel_body(const StepArgs& a) {
   const float4 p0 = load_slot(a.state, st, 0, off), p1 = load_slot(a.state, st, 1, off), p2 = load_slot(a.state, st, 2, off),
                p3 = load_slot(a.state, st, 3, off);
   if (wave == 0) {
-    split_estimator_wave<N, 64, 64, true, STEADY>(a, geo, gval, lane, live, st, off, woff, p0, p1, p3, &x_force[0][0], &x_tension[0][0], &x_est[0][0], x_ik);
+    split_estimator_wave<N, 64, 64, true, STEADY>(a, geo, gval, lane, live, st, off, woff, p0, p1, p3, &x_force[0][0], &x_tension[0][0], &x_est[0][0], x_ik, x_rot);
     return;
   }
-  split_controller_wave<N, PR, STEADY, VEL>(a, geo, gval, lane, r, rr, live, st, off, woff, p0, p1, p2, p3, &x_force[0][0], &x_tension[0][0], &x_est[0][0], x_ik);
+  split_controller_wave<N, PR, STEADY, VEL>(a, geo, gval, lane, r, rr, live, st, off, woff, p0, p1, p2, p3, &x_force[0][0], &x_tension[0][0], &x_est[0][0], x_ik, x_rot);
 }
 template <int N, bool PR = false>
 __global__ __launch_bounds__(128, 2) void cdpr_split_kernel(const StepArgs a) { split_kernel_body<N, PR, false, false>(a); }

@@ -239,6 +239,98 @@ CDPR_DEV Rot quat_to_rot(float x, float y, float z, float w) {
   return r;
 }
 
+#ifndef CDPR_QUAT_PK
+#define CDPR_QUAT_PK 1  // 1 = the role-split kernels hold the quaternion as the pairs (x, y), (z, w) and the rotation matrix as RotPk; 0 = scalars
+#endif
+
+// Halves of a pair as the operand of a packed instruction: the backend folds these shuffles into op_sel / op_sel_hi.
+CDPR_LEAF v2f lo2(v2f v) { return __builtin_shufflevector(v, v, 0, 0); }
+CDPR_LEAF v2f hi2(v2f v) { return __builtin_shufflevector(v, v, 1, 1); }
+CDPR_LEAF v2f swap2(v2f v) { return __builtin_shufflevector(v, v, 1, 0); }
+// The three sums of quat_to_rot_pk and the one product of quat_apply_rotvec_pk whose two lanes differ in SIGN: the backend folds a
+// pair's swizzle into op_sel but not the negation of one half (it emits v_xor_b32 + v_mov_b32 for it), so these four are written as the
+// instruction itself: a plain packed add / fma with its modifiers, nothing else.  Their operands come from packed multiplies, never
+// straight from a transcendental instruction.
+//   (a.lo + b.hi, a.hi - b.lo)
+CDPR_LEAF v2f pk_add_swap_neg_hi(v2f a, v2f b) {
+  v2f r;
+  asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+//   (a.lo - b.hi, a.hi + b.lo)
+CDPR_LEAF v2f pk_add_swap_neg_lo(v2f a, v2f b) {
+  v2f r;
+  asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+//   (a.lo - b.hi, a.lo + b.hi)
+CDPR_LEAF v2f pk_lo_minus_plus_hi(v2f a, v2f b) {
+  v2f r;
+  asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[0,1] neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+//   (a.lo * b.hi + c.lo, -a.hi * b.hi + c.hi)
+CDPR_LEAF v2f pk_fma_hi_neg_hi(v2f a, v2f b, v2f c) {
+  v2f r;
+  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_hi:[1,0,0]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+
+// fma(a, b, c) and fma(-a, b, c) on ONE half of a pair, as the instruction itself.  Written as fmaf on v.x and v.y the SLP vectoriser bundles
+// the two halves' chains into packed fmas whose operands it has to gather from four registers first (in quat_apply_rotvec_pk: 8 plain
+// fmas became 4 packed ones + 11 moves); see hsum.
+CDPR_LEAF float fma_half(float a, float b, float c) {
+  float r;
+  asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+CDPR_LEAF float fnma_half(float a, float b, float c) {
+  float r;
+  asm("v_fma_f32 %0, -%1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+
+// The rotation matrix as pairs, each entry a half that ik_rows broadcasts through op_sel.
+struct RotPk {
+  v2f d;  // (r00, r11)
+  v2f o;  // (r01, r10)
+  v2f c;  // (r02, r12)
+  v2f l;  // (r20, r21)
+  float r22;
+};
+CDPR_DEV Rot unpack_rot(const RotPk& p) { return Rot{p.d.x, p.o.x, p.c.x, p.o.y, p.d.y, p.c.y, p.l.x, p.l.y, p.r22}; }
+
+// quat_to_rot on the quaternion held as A = (x, y), B = (z, w): the same IEEE operations on the same operands.
+//   scalar line (quat_to_rot)          pair form                              lane lo     lane hi
+//   x2 = x + x, y2 = y + y             T = A + A                              x2          y2
+//   z2 = z + z                         U = B + B                              z2          (w + w: unused)
+//   xx = x * x2, yy = y * y2           P1 = A * T                             xx          yy
+//   xz = x * z2, yz = y * z2           P2 = A * U.lo                          xz          yz
+//   wx = w * x2, wy = w * y2           P3 = B.hi * T                          wx          wy
+//   zz = z * z2, wz = w * z2           P4 = B * U.lo                          zz          wz
+//   xy = x * y2                        XY = A * (T.hi, T.lo)                  xy          (y * x2: unused)
+//   r02 = xz + wy, r12 = yz - wx       c = P2 + (P3.hi, -P3.lo)               r02         r12
+//   r20 = xz - wy, r21 = yz + wx       l = P2 + (-P3.hi, P3.lo)               r20         r21
+//   r01 = xy - wz, r10 = xy + wz       o = XY.lo + (-P4.hi, P4.hi)            r01         r10
+//   r00 = 1 - (yy + zz), r11 = 1 - (xx + zz)   d = 1 - ((P1.hi, P1.lo) + P4.lo)   r00     r11
+//   r22 = 1 - (xx + yy)                r22 = 1 - (P1.lo + P1.hi)              (plain)
+// (a - b and a + (-b) are the same operation.)
+CDPR_DEV RotPk quat_to_rot_pk(v2f A, v2f B) {
+  const v2f T = A + A, U = B + B;
+  const v2f P1 = A * T;
+  const v2f P2 = A * lo2(U);
+  const v2f P3 = hi2(B) * T;
+  const v2f P4 = B * lo2(U);
+  const v2f XY = A * swap2(T);
+  RotPk r;
+  r.c = pk_add_swap_neg_hi(P2, P3);
+  r.l = pk_add_swap_neg_lo(P2, P3);
+  r.o = pk_lo_minus_plus_hi(XY, P4);
+  r.d = splat(1.f) - (swap2(P1) + lo2(P4));
+  r.r22 = 1.f - (P1.x + P1.y);
+  return r;
+}
+
 // q <- exp(theta / 2) (x) q, world-frame rotation increment, renormalised.
 CDPR_DEV void quat_apply_rotvec(float& qx, float& qy, float& qz, float& qw, float tx, float ty, float tz) {
   const float a2 = fmaf(tz, tz, fmaf(ty, ty, tx * tx));
@@ -263,6 +355,49 @@ CDPR_DEV void quat_apply_rotvec(float& qx, float& qy, float& qz, float& qw, floa
   qy = ny * inv;
   qz = nz * inv;
   qw = nw * inv;
+}
+
+// quat_apply_rotvec on the quaternion held as A = (qx, qy), B = (qz, qw): the same IEEE operations on the same operands, every chain in
+// its order.  a2, the one v_rsq_f32, __sincosf, the series select: as above, scalar.  The quaternion product's chains (nx, ny) and
+// (nz, nw) run as pairs NA, NB; a term whose two lanes take their q from DIFFERENT pairs is a plain fma on that half of the pair.
+//   scalar line (quat_apply_rotvec)                    pair form                                  lane lo         lane hi
+//   dx = k * tx, dy = k * ty                           D = k * (tx, ty)                           dx              dy
+//   dz = k * tz                                        dz                                         (plain)
+//   cw * qx, cw * qy  (innermost of nx, ny)            NA = cw * A                                cw qx           cw qy
+//   fma(qw, dx, .), fma(qw, dy, .)                     NA = fma(B.hi, D, NA)                      + qw dx         + qw dy
+//   fma(dy, qz, .), fma(dz, qx, .)                     NA.lo, NA.hi: plain                        + dy qz         + dz qx
+//   fma(-dz, qy, .), fma(-dx, qz, .)                   NA.lo, NA.hi: plain                        - dz qy         - dx qz
+//   cw * qz, cw * qw  (innermost of nz, nw)            NB = cw * B                                cw qz           cw qw
+//   fma(qw, dz, .), fma(-dx, qx, .)                    NB.lo, NB.hi: plain                        + qw dz         - dx qx
+//   fma(dx, qy, .), fma(-dy, qy, .)                    NB = fma((D.lo, -D.hi), A.hi, NB)          + dx qy         - dy qy
+//   fma(-dy, qx, .), fma(-dz, qz, .)                   NB.lo, NB.hi: plain                        - dy qx         - dz qz
+//   inv = rsq(nx nx + ny ny + nz nz + nw nw)           the same chain on the halves               (plain)
+//   qx..qw = nx..nw * inv                              A = NA * inv, B = NB * inv                 2 packed
+CDPR_DEV void quat_apply_rotvec_pk(v2f& A, v2f& B, float tx, float ty, float tz) {
+  const float a2 = fmaf(tz, tz, fmaf(ty, ty, tx * tx));
+  const float inv_a = __frsqrt_rn(fmaxf(a2, 1e-30f));
+  float s, c;
+  __sincosf(0.5f * (a2 * inv_a), &s, &c);
+  const bool tiny = a2 < 1e-8f;
+  const float k = tiny ? fmaf(a2, -1.f / 48.f, 0.5f) : s * inv_a;
+  const float cw = tiny ? fmaf(a2, -0.125f, 1.f) : c;
+  const v2f D = splat(k) * (v2f){tx, ty};
+  const float dz = k * tz;
+  v2f NA = splat(cw) * A;
+  NA = fma2(hi2(B), D, NA);
+  NA.x = fma_half(D.y, B.x, NA.x);
+  NA.y = fma_half(dz, A.x, NA.y);
+  NA.x = fnma_half(dz, A.y, NA.x);
+  NA.y = fnma_half(D.x, B.x, NA.y);
+  v2f NB = splat(cw) * B;
+  NB.x = fma_half(B.y, dz, NB.x);
+  NB.y = fnma_half(D.x, A.x, NB.y);
+  NB = pk_fma_hi_neg_hi(D, A, NB);
+  NB.x = fnma_half(D.y, A.x, NB.x);
+  NB.y = fnma_half(dz, B.x, NB.y);
+  const float inv = __frsqrt_rn(fmaf(NB.y, NB.y, fmaf(NB.x, NB.x, fmaf(NA.y, NA.y, NA.x * NA.x))));
+  A = NA * splat(inv);
+  B = NB * splat(inv);
 }
 
 // IK rows of all cable pairs (Joint::Position / GetVelocity restated; geometry statement
@@ -309,6 +444,50 @@ template <int N, bool WANT_L0>
 CDPR_DEV void ik_pairs(const float* lds, float px, float py, float pz, float qx, float qy, float qz, float qw,
                        v2f (&len)[cable_pairs(N)], v2f (&jac)[cable_pairs(N)][6], v2f (&l0)[cable_pairs(N)]) {
   ik_rows<cable_pairs(N), (N & 1) != 0, WANT_L0>(lds, px, py, pz, qx, qy, qz, qw, len, jac, l0);
+}
+
+// ik_rows at a pose whose rotation matrix the caller holds as RotPk: the same statements, every matrix entry a half of a pair broadcast
+// through op_sel instead of a splat scalar.  (A second definition, not a template over both forms: the scalar form's callers keep
+// their code to the instruction.)
+template <int NP, bool ODD, bool WANT_L0>
+CDPR_DEV void ik_rows_pk(const float* lds, float px, float py, float pz, const RotPk& r, v2f (&len)[NP], v2f (&jac)[NP][6], v2f (&l0)[NP]) {
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    const float4 g0 = *reinterpret_cast<const float4*>(lds + k * kGeomFloatsPerPair);
+    const float4 g1 = *reinterpret_cast<const float4*>(lds + k * kGeomFloatsPerPair + 4);
+    const float4 g2 = *reinterpret_cast<const float4*>(lds + k * kGeomFloatsPerPair + 8);
+    const v2f ax = {g0.x, g0.y}, ay = {g0.z, g0.w}, az = {g1.x, g1.y};
+    const v2f bx = {g1.z, g1.w}, by = {g2.x, g2.y}, bz = {g2.z, g2.w};
+    const v2f rbx = fma2(lo2(r.c), bz, fma2(lo2(r.o), by, lo2(r.d) * bx));
+    const v2f rby = fma2(hi2(r.c), bz, fma2(hi2(r.d), by, hi2(r.o) * bx));
+    const v2f rbz = fma2(r.r22, bz, fma2(hi2(r.l), by, lo2(r.l) * bx));
+    const v2f lx = (rbx - ax) + splat(px), ly = (rby - ay) + splat(py), lz = (rbz - az) + splat(pz);
+    const v2f l2 = fma2(lz, lz, fma2(ly, ly, lx * lx));
+    const v2f inv = rsq2(l2);
+    len[k] = l2 * inv;
+    const v2f ux = lx * inv, uy = ly * inv, uz = lz * inv;
+    jac[k][0] = ux;
+    jac[k][1] = uy;
+    jac[k][2] = uz;
+    jac[k][3] = fma2(rby, uz, -(rbz * uy));
+    jac[k][4] = fma2(rbz, ux, -(rbx * uz));
+    jac[k][5] = fma2(rbx, uy, -(rby * ux));
+    if (WANT_L0 || (ODD && k == NP - 1)) {
+      const float4 g3 = *reinterpret_cast<const float4*>(lds + k * kGeomFloatsPerPair + 12);
+      l0[k] = (v2f){g3.x, g3.y};
+      if (ODD && k == NP - 1) {  // odd cable count: the padding cable contributes nothing
+        const v2f mask = {g3.z, g3.w};
+        len[k] *= mask;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) jac[k][c] *= mask;
+      }
+    }
+  }
+}
+template <int N, bool WANT_L0>
+CDPR_DEV void ik_pairs_pk(const float* lds, float px, float py, float pz, const RotPk& r, v2f (&len)[cable_pairs(N)],
+                          v2f (&jac)[cable_pairs(N)][6], v2f (&l0)[cable_pairs(N)]) {
+  ik_rows_pk<cable_pairs(N), (N & 1) != 0, WANT_L0>(lds, px, py, pz, r, len, jac, l0);
 }
 
 // g[c] = sum over cables of jac[.][c] * v[.]  (J^T v), pairs interleaved so the chains are independent
@@ -514,8 +693,8 @@ struct Platform {
 // World step (Gazebo/ODE restated): semi-implicit Euler on the free platform
 // under the wrench w (force, torque about the platform origin, world frame).
 CDPR_DEV void integrate_pose(const StepArgs& a, Platform& s);
-CDPR_DEV void integrate_velocity(const StepArgs& a, Platform& s, const float (&w)[6]) {
-  const Rot r = quat_to_rot(s.qx, s.qy, s.qz, s.qw);
+// (r: the rotation matrix of s.q, for a caller that holds it already)
+CDPR_DEV void integrate_velocity(const StepArgs& a, Platform& s, const float (&w)[6], const Rot& r) {
   s.vx = fmaf(a.dt_inv_mass, w[0], s.vx);
   s.vy = fmaf(a.dt_inv_mass, w[1], s.vy);
   s.vz = fmaf(a.dt_inv_mass, w[2], s.vz);
@@ -539,6 +718,9 @@ CDPR_DEV void integrate_velocity(const StepArgs& a, Platform& s, const float (&w
   s.wy = fmaf(a.dt, fmaf(r.r12, abz, fmaf(r.r11, aby, r.r10 * abx)), s.wy);
   s.wz = fmaf(a.dt, fmaf(r.r22, abz, fmaf(r.r21, aby, r.r20 * abx)), s.wz);
 }
+CDPR_DEV void integrate_velocity(const StepArgs& a, Platform& s, const float (&w)[6]) {
+  integrate_velocity(a, s, w, quat_to_rot(s.qx, s.qy, s.qz, s.qw));
+}
 
 // second half of the world step: p+ = p + dt v+, q+ = normalize(q + dt/2 [w+, 0] (x) q)
 CDPR_DEV void integrate_pose(const StepArgs& a, Platform& s) {
@@ -559,6 +741,10 @@ CDPR_DEV void integrate_pose(const StepArgs& a, Platform& s) {
 
 CDPR_DEV void integrate(const StepArgs& a, Platform& s, const float (&w)[6]) {
   integrate_velocity(a, s, w);
+  integrate_pose(a, s);
+}
+CDPR_DEV void integrate(const StepArgs& a, Platform& s, const float (&w)[6], const Rot& r) {
+  integrate_velocity(a, s, w, r);
   integrate_pose(a, s);
 }
 

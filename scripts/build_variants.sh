@@ -23,14 +23,20 @@ flags_of() {
     expect_fence) echo "-DCDPR_EXPECT_STEADY -DCDPR_HYP_STEP_FENCE" ;;
     descbuf)      echo "-DCDPR_DESC_PER_BUFFER" ;;
     noslp)        echo "-fno-slp-vectorize" ;;                      # round 6 A/B: every unit without LLVM's SLP vectorizer (the shipped build: k_pair only)                  # round 2's experiment: one buffer descriptor per buffer in store_slot
+    # the role-split kernels' switches, each alone (tests/test_gpu_quat_stages.py, scripts/headline_ab.py): the scalar quaternion stages;
+    # the controller wave forming the true state's rotation matrix itself; no pin
+    quat_pk0)    echo "-DCDPR_QUAT_PK=0" ;;
+    shared_rot0) echo "-DCDPR_STEADY_SHARED_ROT=0" ;;
+    pin0)        echo "-DCDPR_EST_PIN_FACTOR=0" ;;                  # the estimator wave's factor not pinned in front of barrier #1
     *) echo "unknown variant $1" >&2; exit 2 ;;
   esac
 }
 
-# variants whose flags only reach the general controller kernels recompile those units and link the shipped build's other objects
+# variants whose flags only reach some kernels recompile those units and link the shipped build's other objects
 units_of() {
   case "$1" in
     expect*) echo "k_gen_one k_gen_split k_gen_step k_gen_roll k_gen_step32 k_gen_roll32" ;;
+    quat_pk0|shared_rot0|pin0) echo "k_onestep k_gen_split" ;;   # the units that hold split_estimator_wave / split_controller_wave
     *) echo "" ;;
   esac
 }
