@@ -23,7 +23,8 @@ box W (yaw up to pi) some of their poses are close to singular: the normal matri
 (fp64, from the oracle's structure matrix) of up to 6e6 at n = 7 and 1.6e8 at n = 6 among 55 draws, against at most 1.3e4 for the eight-cable
 model.  A float32 solve loses kappa * 2^-24 of its solution there whatever kernel runs it: with such a draw in the batch (kappa = 6e6, n = 7)
 the efforts were 5.1e-2 N from the oracle at step 1, with bits EQUAL to the scalar one-wave kernel's.  TOL was stated for the four- and
-eight-cable models (tests/parity.py; the suite's other n = 6, 7 comparisons start within 0.05 rad of the spawn pose), so start_state draws from
+eight-cable models (tests/parity.py; the suite's other n = 6, 7 comparisons start within 0.05 rad of the spawn pose), so start_state
+(tests/quat_stage_poses.py, shared with tests/test_gpu_model_constants.py) draws from
 the box until it has enough poses with kappa <= KAPPA_MAX = 1.5e4, just above the eight-cable model's largest; the bound is a property of the
 models, not of the engine.  No draw of the n = 8 cells is rejected; the named poses are fixed and are not filtered (kappa <= 1e4).
 
@@ -43,6 +44,7 @@ from scipy.spatial.transform import Rotation
 
 import workspace_poses as wp
 from parity import NAMES, ROUTING_OVERRIDES, TOL, assert_within, observed, worst_errors
+from quat_stage_poses import KAPPA_MAX, TURNING, start_state
 
 pytestmark = pytest.mark.gpu
 
@@ -53,44 +55,6 @@ SPLIT, ONE_WAVE = "cdpr_split_kernel<%d, false>", "cdpr_step_kernel<"
 OVERRIDES = ROUTING_OVERRIDES + ("CDPR_SPLIT_STEADY", "CDPR_NO_GRAPH", "CDPR_LIB")
 CELLS = [(n, mode, batch) for n in (8, 7, 6) for mode in ("velocity", "position") for batch in (65, 64)]
 SWITCH_LIBS = {"CDPR_QUAT_PK=0": "quat_pk0", "CDPR_STEADY_SHARED_ROT=0": "shared_rot0", "CDPR_EST_PIN_FACTOR=0": "pin0"}
-KAPPA_MAX = 1.5e4  # largest condition number of J^T J a drawn start pose may have (the module's docstring)
-REST, TURNING = 0, 1
-TURN_RATE = 200.0  # rad/s: 0.2 rad in the 1 ms of world step 0
-
-
-_start = {}
-
-
-def td_condition(st, pose7):
-    """Condition number of J^T J at a pose (fp64, the oracle's structure matrix)."""
-    import oracle
-
-    jac = oracle.ik(st, np.asarray(pose7, dtype=np.float64))[3]
-    return float(np.linalg.cond(jac.T @ jac))
-
-
-def start_state(pkg, n, batch):
-    """(pose7, twist6) float32 of the module's docstring, and the largest kappa of the batch."""
-    if (n, batch) not in _start:
-        model = wp.cell_model(pkg, n)
-        st = pkg.Config(model=model, batch=1, stages=3).to_struct()
-        rng = np.random.default_rng(1000 * n + batch)
-        pose = np.tile(np.asarray(model.home_pose(), dtype=np.float64), (batch, 1))
-        box, drawn = [], 0
-        while len(box) < batch - 10:
-            for p in wp.box_poses(model, batch - 10, rng, "W"):
-                drawn += 1
-                if len(box) < batch - 10 and td_condition(st, p.astype(np.float32)) <= KAPPA_MAX:
-                    box.append(p)
-            assert drawn <= 20 * batch, "box W of this model holds hardly any well-conditioned pose"
-        pose[2:batch - 8] = box
-        axes = np.vstack([np.eye(3), np.ones((1, 3)) / np.sqrt(3.0)])
-        pose[batch - 8:, 3:] = Rotation.from_rotvec(np.concatenate([0.3 * axes, -0.3 * axes])).as_quat()
-        twist = np.zeros((batch, 6))
-        twist[TURNING, 3:] = TURN_RATE / np.sqrt(3.0)
-        pose = pose.astype(np.float32)
-        _start[(n, batch)] = (pose, twist.astype(np.float32), max(td_condition(st, p) for p in pose))
-    return _start[(n, batch)]
 
 
 def commands(batch, n, seed):

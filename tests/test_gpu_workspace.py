@@ -47,12 +47,11 @@ import numpy as np
 import pytest
 
 import workspace_poses as wp
-from parity import FULL_SIZE_SLICES, TOL, TOL64, check_slice, clean_env_fixture, observed, state_of, worst_errors
+from parity import FULL_SIZE_SLICES, TOL, TOL64, check_slice, clean_env_fixture
 
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-FIRST, NOT_STEADY = 1, 8  # CDPR_PLAN_* (include/cdpr.h)
 WORST = {}
 RAN = {}  # cell -> kernel names its launches ran on
 
@@ -177,107 +176,11 @@ def test_solve_td_over_the_edge_box(pkg, oracle, n):
 
 
 # ---- c. the closed-loop matrix over W ------------------------------------------------------------------------------------------
-def oracle_jacobians(oracle, s, poses):
-    return np.array([oracle.ik(s, p)[3] for p in poses])
-
-
 @pytest.mark.parametrize("cell", list(wp.CELLS))
 def test_closed_loop_cell_over_the_wide_box(pkg, oracle, monkeypatch, cell):
+    """The cell body is workspace_poses.closed_loop_cell (shared with tests/test_gpu_model_constants.py)."""
     cfg, env, seed = wp.cell_config(pkg, cell)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    B, n, f64, stages = cfg.batch, cfg.n_cables, cfg.precision == 64, cfg.stages
-    s = cfg.to_struct()
-    tol = TOL64 if f64 else TOL
-    rng = np.random.default_rng(seed)
-    pose = wp.start_poses(cfg.model, B, rng)
-    cmds = wp.script_commands(rng, B, n)
-    rows, twins = wp.twin_rows(B)
-    pkg.plan_kernel(cfg, 1)
-    # a: one step per launch; b: fused (10 per launch); c: the trajectory record
-    engs = [pkg.Engine(cfg, 0) for _ in range(3)]
-    a, b, c = engs
-    ora = oracle.OracleSim(cfg.to_struct(), oracle.DERIV_EXACT)
-    for e in engs:
-        e.set_platform_state_f64(pose7=pose.astype(np.float64)) if f64 else e.set_platform_state(pose7=pose)
-    ora.set_platform_state(pose7=pose.astype(np.float64))
-    ran = RAN.setdefault(cell, set())
-    used = {}
-    failures = []
-    for kind, k in wp.SCRIPT:
-        where = f"{cell}, {kind}"
-        cmd = wp.segment_command(kind, cmds, ora, used)
-        if cmd is not None:
-            for sim in (a, b, c, ora):
-                getattr(sim, wp.SETTER[kind])(cmd)
-        a.update(k)
-        b.update(k, 10)
-        rec = c.update_record(k, 10)
-        ora.update(k)
-        # what ran = what was planned (as test_cable_count_matrix)
-        flags = (FIRST | NOT_STEADY) if kind == "hold" else NOT_STEADY if kind == "force" else 0
-        last = k - 10 * ((k - 1) // 10)
-        assert a.kernel_name == pkg.plan_kernel(cfg, 1), where
-        planned = pkg.plan_kernel(cfg, last, flags)
-        if kind == "hold" and pkg.plan_kernel(cfg, 10).startswith(("cdpr_gen_split", "cdpr_gen_lean")):
-            planned = pkg.plan_kernel(cfg, 1, NOT_STEADY)  # (these handles run a fused update as one-step launches: the last one does not start at world step 0)
-        assert b.kernel_name == planned == c.kernel_name, where
-        ran.update((a.kernel_name, b.kernel_name))
-        # the oracle
-        got = observed(a, f64)
-        for name, (err, robot, _) in worst_errors(got, observed(ora), where, f64=f64).items():
-            note(cell, name, err)
-            if err > tol[name]:
-                failures.append(f"{where}: {name} differs from the oracle by {err:.3e} (tolerance {tol[name]:.1e}, robot {robot})")
-        # launch forms
-        sa = state_of(a, f64)
-        for e, form in ((b, "fused"), (c, "recorded")):
-            for x, y in zip(sa, state_of(e, f64)):
-                assert np.array_equal(x, y), f"{where}: {form} launches differ from one-step launches"
-        for j, key in enumerate(("position", "velocity", "effort", "pose", "twist")):
-            assert np.array_equal(rec[key][-1], sa[2 + j]), f"{where}: the record's last step is not the published one ({key})"
-        # a robot and its twin started from the negated quaternion
-        gp, gt, gq, gqd, ge = got
-        for name, x in (("q", gq), ("qd", gqd), ("effort", ge), ("twist", gt), ("position", gp[:, :3])):
-            assert np.array_equal(x[rows], x[twins]), f"{where}: {name} of a robot and of its -q twin differ"
-        assert np.array_equal(gp[rows, 3:], -gp[twins, 3:]), f"{where}: published quaternions of twins are not exact negatives"
-        if stages & 1:
-            fp, fr, fi = a.fk_state()
-            op, orr, oi = ora.fk_state()
-            err = float(np.abs(fp - op).max())
-            note(cell, "fk estimate", err)
-            assert np.array_equal(fi, oi), f"{where}: FK iteration counts"
-            if err > 1e-5:
-                failures.append(f"{where}: FK estimate differs from the oracle's by {err:.3e} (robot {int(np.abs(fp - op).max(axis=1).argmax())})")
-        if stages & 2:
-            tt, tf = a.td_state()
-            ot, of = ora.td_state()
-            err = float(np.abs(tt - ot).max())
-            note(cell, "tension", err)
-            if err > TOL["eff"]:
-                failures.append(f"{where}: tensions differ by {err:.3e}")
-            lo, hi = float(s.td_f_min), float(s.td_f_max)
-            near = wp.near_bound(ot, lo, hi, 2e-2)  # (a clamped value sits on its bound)
-            differ = tf != of
-            note(cell, "flags differ (share)", differ.mean())
-            assert not differ[~near].any(), f"{where}: infeasibility flags differ away from the bounds"
-            assert differ.mean() <= 0.01, f"{where}: flags differ on {differ.sum()} robots"
-            if kind == "force":
-                # the commanded forces are known: the unclamped tensions follow from the oracle's Jacobian at its estimate
-                at = ora.fk_state()[0] if stages & 1 else ora.platform_state()[0]
-                jac = oracle_jacobians(oracle, s, at)
-                wd = -np.einsum("bna,bn->ba", jac, cmd.astype(np.float64))
-                unc = wp.unclamped_tensions(jac, wd, lo, hi)
-                assert np.abs(np.clip(unc, lo, hi) - ot).max() < 1e-9, where
-                near5 = wp.near_bound(unc, lo, hi, 5e-3)
-                note(cell, "near a bound in force mode (share)", near5.mean())
-                assert near5.mean() <= 0.01, where
-                assert np.array_equal(tf[~near5], of[~near5]), f"{where}: flags differ on robots farther than 5e-3 N from a bound"
-                assert (of != 0).any(), where
-    assert not failures, "\n".join(failures)
-    for e in engs:
-        e.close()
-    ora.close()
+    wp.closed_loop_cell(pkg, oracle, monkeypatch, cfg, env, seed, TOL64 if cfg.precision == 64 else TOL, RAN, WORST, cell)
 
 
 # ---- d. the headline launch from W ---------------------------------------------------------------------------------------------

@@ -19,27 +19,6 @@ from parity import clean_env_fixture
 clean_env = clean_env_fixture()
 
 
-def run_script(oracle, cfg, pose, cmds, targets=None):
-    """The script on the oracle from `pose`; returns the observables after every segment, the position targets used, and the
-    travel-limit masks.  `targets`: position targets of an earlier run (twin runs share their commands)."""
-    ora = oracle.OracleSim(cfg.to_struct(), oracle.DERIV_EXACT)
-    ora.set_platform_state(pose7=pose)
-    used, out, tg, limits, force = {}, [], None, [], None
-    for kind, k in wp.SCRIPT:
-        cmd = wp.segment_command(kind, cmds, ora, used)
-        if kind == "position":
-            cmd = tg = cmd if targets is None else targets
-        if cmd is not None:
-            getattr(ora, wp.SETTER[kind])(cmd)
-        ora.update(k)
-        out.append(ora.platform_state() + ora.joint_states())
-        limits.append(ora.limit_state())
-        if kind == "force" and cfg.stages & 2:  # the pose the tension distribution saw, its tensions and flags
-            force = (ora.fk_state()[0] if cfg.stages & 1 else ora.platform_state()[0],) + ora.td_state()
-    ora.close()
-    return out, tg, limits, force
-
-
 @pytest.mark.parametrize("cell", list(wp.CELLS))
 def test_oracle_sensitivity_to_one_rounding_of_the_start_pose(pkg, oracle, clean_env, cell):
     cfg, _, seed = wp.cell_config(pkg, cell)
@@ -49,8 +28,8 @@ def test_oracle_sensitivity_to_one_rounding_of_the_start_pose(pkg, oracle, clean
     cmds = wp.script_commands(rng, B, n)
     twin = np.nextafter(pose, np.where(np.random.default_rng(seed + 1).random(pose.shape) < 0.5, -np.inf, np.inf).astype(np.float32))
     assert twin.dtype == np.float32 and (twin != pose).all()
-    a, targets, limits, force = run_script(oracle, cfg, pose.astype(np.float64), cmds)
-    b, _, _, _ = run_script(oracle, cfg, twin.astype(np.float64), cmds, targets)
+    a, targets, limits, force = wp.oracle_script(oracle, cfg, pose.astype(np.float64), cmds)
+    b, _, _, _ = wp.oracle_script(oracle, cfg, twin.astype(np.float64), cmds, targets)
     worst = dict.fromkeys(("pose", "twist", "q", "qd", "eff"), 0.0)
     for sa, sb in zip(a, b):
         for name, x, y in zip(worst, sa, sb):

@@ -138,6 +138,29 @@ def near_bound(t, f_min, f_max, margin):
     return ((np.abs(t - f_min) < margin) | (np.abs(t - f_max) < margin)).any(axis=1)
 
 
+def oracle_script(oracle, cfg, pose, cmds, targets=None):
+    """The script on the oracle alone from `pose` (tests/test_workspace_inputs.py, tests/test_model_constant_inputs.py); returns the
+    observables after every segment, the position targets used, the travel-limit masks and, with the tension distribution on, (the
+    pose it saw, its tensions, its flags) of the Force segment.  `targets`: position targets of an earlier run (twin runs share
+    their commands)."""
+    ora = oracle.OracleSim(cfg.to_struct(), oracle.DERIV_EXACT)
+    ora.set_platform_state(pose7=pose)
+    used, out, tg, limits, force = {}, [], None, [], None
+    for kind, k in SCRIPT:
+        cmd = segment_command(kind, cmds, ora, used)
+        if kind == "position":
+            cmd = tg = cmd if targets is None else targets
+        if cmd is not None:
+            getattr(ora, SETTER[kind])(cmd)
+        ora.update(k)
+        out.append(ora.platform_state() + ora.joint_states())
+        limits.append(ora.limit_state())
+        if kind == "force" and cfg.stages & 2:  # the pose the tension distribution saw, its tensions and flags
+            force = (ora.fk_state()[0] if cfg.stages & 1 else ora.platform_state()[0],) + ora.td_state()
+    ora.close()
+    return out, tg, limits, force
+
+
 # ---- the cells of the closed-loop matrix (tests/test_gpu_workspace.py, section c) ---------------------------------------------
 # name: (cables, Config keywords beyond model / batch, environment switches, batch, seed).  Models: 4 = cube_model, 8 =
 # eight_cable_model, 12 = twelve_cable_model, else the first n anchors of twelve_cable_model (as tests/test_gpu_cable_counts.py).
@@ -220,6 +243,120 @@ def cell_config(pkg, name, batch=None):
         kw["mapping"] = {"robot": pkg._abi.MAP_LANE_PER_ROBOT, "pair": pkg._abi.MAP_LANE_PAIR, "cable": pkg._abi.MAP_LANE_PER_CABLE}[mapping]
     model = cell_model(pkg, n, **kw.pop("model_kw", {}))
     return pkg.Config(model=model, batch=batch or B, **kw), env, seed
+
+
+# ---- the body of a closed-loop cell (tests/test_gpu_workspace.py, section c; tests/test_gpu_model_constants.py, section a) ------
+FIRST, NOT_STEADY = 1, 8  # CDPR_PLAN_* (include/cdpr.h)
+
+
+def oracle_jacobians(oracle, s, poses):
+    return np.array([oracle.ik(s, p)[3] for p in poses])
+
+
+def closed_loop_cell(pkg, oracle, monkeypatch, cfg, env, seed, tol, ran, worst, label):
+    """The script on three engines (one step per launch, fused, recorded) and the oracle from start_poses, under the environment
+    switches `env`: the oracle after every segment at `tol` (a dictionary over parity.NAMES), one-step = fused = recorded bit for
+    bit, kernel_name = plan_kernel, FK iteration counts and estimates, TD tensions and flags with the near-bound rule, the
+    Force-mode tension reconstruction, (q, -q) twins.  ran[label] collects the kernel names, worst[(label, quantity)] the largest
+    error seen.  pytest rewrites asserts only in test modules, so every assert here carries its message."""
+    from parity import TOL, observed, state_of, worst_errors
+
+    def note(name, err):
+        worst[(label, name)] = max(worst.get((label, name), 0.0), float(err))
+
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    B, n, f64, stages = cfg.batch, cfg.n_cables, cfg.precision == 64, cfg.stages
+    s = cfg.to_struct()
+    rng = np.random.default_rng(seed)
+    pose = start_poses(cfg.model, B, rng)
+    cmds = script_commands(rng, B, n)
+    rows, twins = twin_rows(B)
+    pkg.plan_kernel(cfg, 1)
+    # a: one step per launch; b: fused (10 per launch); c: the trajectory record
+    engs = [pkg.Engine(cfg, 0) for _ in range(3)]
+    a, b, c = engs
+    ora = oracle.OracleSim(cfg.to_struct(), oracle.DERIV_EXACT)
+    for e in engs:
+        e.set_platform_state_f64(pose7=pose.astype(np.float64)) if f64 else e.set_platform_state(pose7=pose)
+    ora.set_platform_state(pose7=pose.astype(np.float64))
+    names = ran.setdefault(label, set())
+    used = {}
+    failures = []
+    for kind, k in SCRIPT:
+        where = f"{label}, {kind}"
+        cmd = segment_command(kind, cmds, ora, used)
+        if cmd is not None:
+            for sim in (a, b, c, ora):
+                getattr(sim, SETTER[kind])(cmd)
+        a.update(k)
+        b.update(k, 10)
+        rec = c.update_record(k, 10)
+        ora.update(k)
+        # what ran = what was planned (as test_cable_count_matrix)
+        flags = (FIRST | NOT_STEADY) if kind == "hold" else NOT_STEADY if kind == "force" else 0
+        last = k - 10 * ((k - 1) // 10)
+        assert a.kernel_name == pkg.plan_kernel(cfg, 1), (where, a.kernel_name)
+        planned = pkg.plan_kernel(cfg, last, flags)
+        if kind == "hold" and pkg.plan_kernel(cfg, 10).startswith(("cdpr_gen_split", "cdpr_gen_lean")):
+            planned = pkg.plan_kernel(cfg, 1, NOT_STEADY)  # (these handles run a fused update as one-step launches: the last one does not start at world step 0)
+        assert b.kernel_name == planned == c.kernel_name, (where, b.kernel_name, planned, c.kernel_name)
+        names.update((a.kernel_name, b.kernel_name))
+        # the oracle
+        got = observed(a, f64)
+        for name, (err, robot, _) in worst_errors(got, observed(ora), where, f64=f64).items():
+            note(name, err)
+            if err > tol[name]:
+                failures.append(f"{where}: {name} differs from the oracle by {err:.3e} (tolerance {tol[name]:.1e}, robot {robot})")
+        # launch forms
+        sa = state_of(a, f64)
+        for e, form in ((b, "fused"), (c, "recorded")):
+            for x, y in zip(sa, state_of(e, f64)):
+                assert np.array_equal(x, y), f"{where}: {form} launches differ from one-step launches"
+        for j, key in enumerate(("position", "velocity", "effort", "pose", "twist")):
+            assert np.array_equal(rec[key][-1], sa[2 + j]), f"{where}: the record's last step is not the published one ({key})"
+        # a robot and its twin started from the negated quaternion
+        gp, gt, gq, gqd, ge = got
+        for name, x in (("q", gq), ("qd", gqd), ("effort", ge), ("twist", gt), ("position", gp[:, :3])):
+            assert np.array_equal(x[rows], x[twins]), f"{where}: {name} of a robot and of its -q twin differ"
+        assert np.array_equal(gp[rows, 3:], -gp[twins, 3:]), f"{where}: published quaternions of twins are not exact negatives"
+        if stages & 1:
+            fp, fr, fi = a.fk_state()
+            op, orr, oi = ora.fk_state()
+            err = float(np.abs(fp - op).max())
+            note("fk estimate", err)
+            assert np.array_equal(fi, oi), f"{where}: FK iteration counts"
+            if err > 1e-5:
+                failures.append(f"{where}: FK estimate differs from the oracle's by {err:.3e} (robot {int(np.abs(fp - op).max(axis=1).argmax())})")
+        if stages & 2:
+            tt, tf = a.td_state()
+            ot, of = ora.td_state()
+            err = float(np.abs(tt - ot).max())
+            note("tension", err)
+            if err > TOL["eff"]:
+                failures.append(f"{where}: tensions differ by {err:.3e}")
+            lo, hi = float(s.td_f_min), float(s.td_f_max)
+            near = near_bound(ot, lo, hi, 2e-2)  # (a clamped value sits on its bound)
+            differ = tf != of
+            note("flags differ (share)", differ.mean())
+            assert not differ[~near].any(), f"{where}: infeasibility flags differ away from the bounds"
+            assert differ.mean() <= 0.01, f"{where}: flags differ on {differ.sum()} robots"
+            if kind == "force":
+                # the commanded forces are known: the unclamped tensions follow from the oracle's Jacobian at its estimate
+                at = ora.fk_state()[0] if stages & 1 else ora.platform_state()[0]
+                jac = oracle_jacobians(oracle, s, at)
+                wd = -np.einsum("bna,bn->ba", jac, cmd.astype(np.float64))
+                unc = unclamped_tensions(jac, wd, lo, hi)
+                assert np.abs(np.clip(unc, lo, hi) - ot).max() < 1e-9, where
+                near5 = near_bound(unc, lo, hi, 5e-3)
+                note("near a bound in force mode (share)", near5.mean())
+                assert near5.mean() <= 0.01, (where, float(near5.mean()))
+                assert np.array_equal(tf[~near5], of[~near5]), f"{where}: flags differ on robots farther than 5e-3 N from a bound"
+                assert (of != 0).any(), where
+    assert not failures, "\n".join(failures)
+    for e in engs:
+        e.close()
+    ora.close()
 
 
 # ---- the one-shot solvers over E (tests/test_gpu_workspace.py, section b) ------------------------------------------------------
