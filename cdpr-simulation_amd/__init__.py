@@ -8,7 +8,7 @@ thousands of independent robots per GPU.  Host code is Python over a ctypes C-AB
 """
 from . import _abi, stimulus
 from .config import Config, DoneRule, FilterParameters, Model, PidParameters, cube_model, eight_cable_model, twelve_cable_model
-from ._abi import EnvSpec, MppiSpec, ResampleSpec
+from ._abi import CemSpec, EnvSpec, MppiSpec, ResampleSpec
 from .engine import CdprError, Engine, derivative_weights, observation_width, plan_kernel
 from .model_io import load_launch, load_sdf, load_yaml
 from .messages import Header, JointState, Joy, KeyValue, PlatformState, Pose, Twist, WireStates
@@ -17,6 +17,6 @@ from .sharding import ShardedEngine, shard_range
 
 __all__ = [
     "Config", "DoneRule", "FilterParameters", "Model", "PidParameters", "cube_model", "eight_cable_model", "twelve_cable_model",
-    "load_launch", "load_sdf", "load_yaml", "Engine", "CdprError", "derivative_weights", "plan_kernel", "EnvSpec", "ResampleSpec", "MppiSpec", "observation_width", "CdprGazeboPlugin", "TopicBus", "ShardedEngine", "shard_range",
+    "load_launch", "load_sdf", "load_yaml", "Engine", "CdprError", "derivative_weights", "plan_kernel", "EnvSpec", "ResampleSpec", "MppiSpec", "CemSpec", "observation_width", "CdprGazeboPlugin", "TopicBus", "ShardedEngine", "shard_range",
     "Header", "JointState", "Joy", "KeyValue", "PlatformState", "Pose", "Twist", "WireStates", "stimulus", "_abi",
 ]  # fmt: skip

@@ -201,3 +201,43 @@ class MppiSpec(C.Structure):
         s = MppiSpec.from_buffer_copy(self)
         s.robot_offset = (self.robot_offset + int(robot_offset)) & 0xFFFFFFFF
         return s
+
+
+CEM_NOMINAL_FIRST, CEM_CLAMP, CEM_SHIFT = 1, 2, 4  # cdpr_cem_spec_t.flags: the bits of their MPPI namesakes
+CEM_STATUS = 4  # cdpr_cem_update_device's d_status: [robots updated, robots degenerate, bad costs, robots short of K usable costs]
+
+
+class CemSpec(C.Structure):
+    """cdpr_cem_spec_t: what Engine.cem_sample[_device] and Engine.cem_update[_device] compute.  samples S and horizon H shape the command
+    batch float[B][H][S][n]; the elites are the K best samples of a robot; alpha in (0, 1] blends the fit into the old plans (1: the fit
+    itself), sigma' is clamped to [sigma_min, sigma_max] (inf: no upper clamp); cmd_min / cmd_max bound the commands under CEM_CLAMP;
+    (seed_lo, seed_hi) is the Philox key and robot_offset the global index of the handle's robot 0 (a shard of a larger batch).
+    struct_size is filled in."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("samples", C.c_uint32),
+        ("horizon", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("elites", C.c_uint32),
+        ("alpha", C.c_float),
+        ("sigma_min", C.c_float),
+        ("sigma_max", C.c_float),
+        ("cmd_min", C.c_float),
+        ("cmd_max", C.c_float),
+        ("seed_lo", C.c_uint32),
+        ("seed_hi", C.c_uint32),
+        ("robot_offset", C.c_uint32),
+        ("reserved", C.c_uint32 * 3),
+    ]
+
+    def __init__(self, samples=1, horizon=1, flags=0, elites=1, alpha=1.0, sigma_min=0.0, sigma_max=float("inf"), cmd_min=0.0, cmd_max=0.0,
+                 seed=0, robot_offset=0):
+        super().__init__(C.sizeof(CemSpec), int(samples), int(horizon), int(flags), int(elites), float(alpha), float(sigma_min), float(sigma_max),
+                         float(cmd_min), float(cmd_max), int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF, int(robot_offset) & 0xFFFFFFFF)
+
+    def with_offset(self, robot_offset):
+        """a copy whose robot 0 has the global index robot_offset more (modulo 2^32): the spec of a shard"""
+        s = CemSpec.from_buffer_copy(self)
+        s.robot_offset = (self.robot_offset + int(robot_offset)) & 0xFFFFFFFF
+        return s

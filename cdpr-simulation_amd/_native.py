@@ -20,6 +20,7 @@ EXPORTS = [
     "cdpr_env_spec_size", "cdpr_observation_width", "cdpr_observe_device", "cdpr_env_evaluate_device",
     "cdpr_copy_robots", "cdpr_copy_robots_device", "cdpr_resample_spec_size", "cdpr_resample_map_device", "cdpr_resample_device",
     "cdpr_mppi_spec_size", "cdpr_mppi_sample_device", "cdpr_mppi_update_device",
+    "cdpr_cem_spec_size", "cdpr_cem_sample_device", "cdpr_cem_update_device",
     "cdpr_set_velocity_command", "cdpr_set_position_command", "cdpr_set_velocity_command_device",
     "cdpr_set_position_command_device", "cdpr_bind_velocity_command_device", "cdpr_bind_position_command_device",
     "cdpr_set_velocity_command_masked", "cdpr_set_position_command_masked", "cdpr_set_force_command", "cdpr_set_force_command_device",
@@ -94,6 +95,11 @@ def lib():
         L.cdpr_mppi_spec_size.restype = C.c_size_t
         L.cdpr_mppi_sample_device.argtypes = [H, C.POINTER(_abi.MppiSpec), C.c_uint32, C.c_void_p, C.c_void_p]
         L.cdpr_mppi_update_device.argtypes = [H, C.POINTER(_abi.MppiSpec)] + [C.c_void_p] * 7
+    # ... and CEM beside it: the sampler with a sigma plan and the refit of both plans to the elites
+    if hasattr(L, "cdpr_cem_spec_size"):
+        L.cdpr_cem_spec_size.restype = C.c_size_t
+        L.cdpr_cem_sample_device.argtypes = [H, C.POINTER(_abi.CemSpec), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cdpr_cem_update_device.argtypes = [H, C.POINTER(_abi.CemSpec)] + [C.c_void_p] * 8
     for name in ("cdpr_set_velocity_command", "cdpr_set_position_command", "cdpr_set_force_command"):
         getattr(L, name).argtypes = [H, fp, C.c_size_t]
     for name in ("cdpr_set_velocity_command_device", "cdpr_set_position_command_device", "cdpr_bind_velocity_command_device",
@@ -160,5 +166,7 @@ def lib():
         raise ImportError("cdpr_resample_spec_t layout mismatch between include/cdpr.h and _abi.py")
     if hasattr(L, "cdpr_mppi_spec_size") and L.cdpr_mppi_spec_size() != C.sizeof(_abi.MppiSpec):
         raise ImportError("cdpr_mppi_spec_t layout mismatch between include/cdpr.h and _abi.py")
+    if hasattr(L, "cdpr_cem_spec_size") and L.cdpr_cem_spec_size() != C.sizeof(_abi.CemSpec):
+        raise ImportError("cdpr_cem_spec_t layout mismatch between include/cdpr.h and _abi.py")
     _lib = L
     return L

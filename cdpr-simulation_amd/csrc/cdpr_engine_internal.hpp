@@ -8,7 +8,8 @@
 // general paths, schedules), cdpr_engine_f64.hip (precision = 64: set-up, its path of the chain), cdpr_engine_rollout.hip (cdpr_rollout_velocity*), cdpr_engine_solvers.hip (cdpr_solve_ik / fk / td), cdpr_engine_reset.hip
 // (cdpr_reset_robots*), cdpr_engine_copy.hip (cdpr_copy_robots*), cdpr_engine_done.hip (cdpr_evaluate_done*, cdpr_reset_done_device, cdpr_get_episode_start), cdpr_engine_env.hip (cdpr_observe_device,
 // cdpr_env_evaluate_device, cdpr_observation_width), cdpr_engine_resample.hip (cdpr_resample_map_device, cdpr_resample_device),
-// cdpr_engine_mppi.hip (cdpr_mppi_sample_device, cdpr_mppi_update_device).  Not installed, not part of the C-ABI (include/cdpr.h is).
+// cdpr_engine_mppi.hip (cdpr_mppi_sample_device, cdpr_mppi_update_device), cdpr_engine_cem.hip (cdpr_cem_sample_device,
+// cdpr_cem_update_device).  Not installed, not part of the C-ABI (include/cdpr.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -8,9 +8,6 @@
 
 namespace cdpr_host {
 
-constexpr uint64_t kMppiMaxElems = 1ull << 34;  // E = H * S * n: a group index is one Philox counter word
-constexpr uint64_t kMppiMaxTraj = 1ull << 30;   // B * S: the rollout's own limit
-
 // what both calls refuse of a spec; E becomes H * S * n
 static int mppi_checks(cdpr_engine* h, const cdpr_mppi_spec_t* spec, bool update, uint64_t& E, const char* what) {
   const char* bad = nullptr;
@@ -60,21 +57,11 @@ int cdpr_mppi_sample_device(cdpr_handle_t h, const cdpr_mppi_spec_t* spec, uint3
   if (!d_commands) return refuse_null(h, what, "command buffer");
   if (set_device(h) != CDPR_OK) return CDPR_ERR_DEVICE;
   MppiSampleArgs a{};
-  a.nominal = d_nominal, a.commands = d_commands, a.elems = E;
-  a.batch = h->batch, a.samples = spec->samples, a.horizon = spec->horizon, a.n = h->n;
-  a.row = (uint64_t)spec->samples * h->n;
-  a.inv_n = 1.0f / (float)h->n, a.inv_samples = 1.0f / (float)spec->samples;
+  a.nominal = d_nominal, a.commands = d_commands;
+  const dim3 grid = mppi_sample_geometry(a, h->batch, spec->samples, spec->horizon, h->n);
   a.flags = spec->flags, a.sigma = spec->sigma, a.lo = spec->cmd_min, a.hi = spec->cmd_max;
   a.key0 = spec->seed_lo, a.key1 = spec->seed_hi, a.iteration = iteration, a.robot_offset = spec->robot_offset;
-  const bool vec = E % 4u == 0u && reinterpret_cast<uintptr_t>(d_commands) % 16u == 0u;
-  const uint64_t groups = (E + 3u) / 4u;  // per robot
-  uint32_t k = 0u;
-  while (k < 8u && (1ull << k) < groups) ++k;
-  a.lane_shift = k;
-  const uint64_t robot_blocks = ((uint64_t)h->batch + (kMppiBlock >> k) - 1u) / (kMppiBlock >> k);
-  const uint32_t gy = (uint32_t)std::min<uint64_t>(robot_blocks, 32768u);
-  const dim3 grid((uint32_t)((groups + (1ull << k) - 1u) >> k), gy, (uint32_t)((robot_blocks + gy - 1u) / gy));
-  hipLaunchKernelGGL(mppi_sample_kernel_entry(vec), grid, dim3(kMppiBlock), 0, h->stream, a);
+  hipLaunchKernelGGL(mppi_sample_kernel_entry(mppi_sample_vec(E, d_commands)), grid, dim3(kMppiBlock), 0, h->stream, a);
   HIP_TRY(h, hipGetLastError());
   return CDPR_OK;
 }

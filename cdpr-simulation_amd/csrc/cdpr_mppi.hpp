@@ -40,6 +40,7 @@ struct MppiSampleArgs {
   float sigma, lo, hi;
   float inv_n, inv_samples;  // 1 / n, 1 / S rounded to float
   uint32_t key0, key1, iteration, robot_offset;
+  const float* sigma_plan;  // float[B][H][n]: the kPlan instantiations (cdpr_cem_sample_device) take sigma from here, entry by entry
 };
 
 struct MppiUpdateArgs {
@@ -77,7 +78,9 @@ CDPR_DEV void box_muller(uint32_t x, uint32_t y, float& z0, float& z1) {
   z0 = r * c, z1 = r * s;
 }
 
-template <bool kVec>  // kVec: E % 4 == 0 and the buffer is 16-byte aligned - one 16-byte store per group
+// kVec: E % 4 == 0 and the buffer is 16-byte aligned - one 16-byte store per group.  kPlan: sigma is a plan float[B][H][n] beside the
+// nominal one and read the same way (CEM: cdpr_cem.hpp); the streams, the element order and everything else are the same
+template <bool kVec, bool kPlan = false>
 __global__ __launch_bounds__(kMppiBlock) void cdpr_mppi_sample_kernel(const MppiSampleArgs a) {
   const uint32_t k = a.lane_shift;
   const uint32_t sub = threadIdx.x >> k, lane = threadIdx.x & ((1u << k) - 1u);
@@ -118,6 +121,7 @@ __global__ __launch_bounds__(kMppiBlock) void cdpr_mppi_sample_kernel(const Mppi
     s = y - dt * a.samples, t += dt;
   }
   const float* u = a.nominal + ((size_t)b * a.horizon + t) * a.n;
+  const float* sg = kPlan ? a.sigma_plan + ((size_t)b * a.horizon + t) * a.n : nullptr;
   const bool clamp = (a.flags & CDPR_MPPI_CLAMP) != 0u, first = (a.flags & CDPR_MPPI_NOMINAL_FIRST) != 0u;
   float v[4];
   bool in[4];
@@ -125,12 +129,17 @@ __global__ __launch_bounds__(kMppiBlock) void cdpr_mppi_sample_kernel(const Mppi
   for (int q = 0; q < 4; ++q) {
     in[q] = e0 + (uint64_t)q < a.elems;
     const float nom = in[q] ? u[i] : 0.0f;
-    float c = (first && s == 0u) ? nom : fmaf(a.sigma, z[q], nom);
+    float sigma = a.sigma;
+    if constexpr (kPlan) sigma = in[q] ? sg[i] : 0.0f;
+    float c = (first && s == 0u) ? nom : fmaf(sigma, z[q], nom);
     if (clamp) c = fminf(fmaxf(c, a.lo), a.hi);
     v[q] = c;
     if (++i == a.n) {
       i = 0u;
-      if (++s == a.samples) s = 0u, u += a.n;  // (the next horizon step's row)
+      if (++s == a.samples) {  // (the next horizon step's row)
+        s = 0u, u += a.n;
+        if constexpr (kPlan) sg += a.n;
+      }
     }
   }
   float* out = a.commands + (size_t)b * a.elems + e0;
@@ -279,5 +288,24 @@ using MppiUpdateKernel = void (*)(const MppiUpdateArgs);
 MppiUpdateKernel mppi_update_kernel_entry(uint32_t n);  // k_mppi.hip: nullptr outside 1 .. 12
 using MppiSampleKernel = void (*)(const MppiSampleArgs);
 MppiSampleKernel mppi_sample_kernel_entry(bool vec);    // k_mppi.hip
+
+constexpr uint64_t kMppiMaxElems = 1ull << 34;  // E = H * S * n: a group index is one Philox counter word
+constexpr uint64_t kMppiMaxTraj = 1ull << 30;   // B * S: the rollout's own limit
+
+// the sampler's launch (host): fills the shape, the reciprocals and lane_shift of `a` from (B, S, H, n) - E = H * S * n within
+// kMppiMaxElems - and returns the grid; what is sampled around what (nominal, sigma or sigma_plan, flags, bounds, key) is the caller's
+inline dim3 mppi_sample_geometry(MppiSampleArgs& a, uint32_t batch, uint32_t samples, uint32_t horizon, uint32_t n) {
+  a.batch = batch, a.samples = samples, a.horizon = horizon, a.n = n;
+  a.row = (uint64_t)samples * n, a.elems = (uint64_t)horizon * a.row;
+  a.inv_n = 1.0f / (float)n, a.inv_samples = 1.0f / (float)samples;
+  const uint64_t groups = (a.elems + 3u) / 4u;  // per robot
+  uint32_t k = 0u;
+  while (k < 8u && (1ull << k) < groups) ++k;
+  a.lane_shift = k;
+  const uint64_t robot_blocks = ((uint64_t)batch + (kMppiBlock >> k) - 1u) / (kMppiBlock >> k);
+  const uint32_t gy = (uint32_t)(robot_blocks < 32768u ? robot_blocks : 32768u);
+  return dim3((uint32_t)((groups + (1ull << k) - 1u) >> k), gy, (uint32_t)((robot_blocks + gy - 1u) / gy));
+}
+inline bool mppi_sample_vec(uint64_t elems, const float* commands) { return elems % 4u == 0u && reinterpret_cast<uintptr_t>(commands) % 16u == 0u; }
 
 }  // namespace cdpr

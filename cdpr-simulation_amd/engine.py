@@ -222,6 +222,61 @@ class Engine:
 
         return self._with_scratch([c.nbytes, v.nbytes, u.nbytes, 4 * self.B * self.n, c.nbytes, 4 * self.B, 4 * _abi.MPPI_STATUS], body)
 
+    # -- CEM around the rollout: the command batch from a mean and a sigma plan, both refitted to the best samples, on the device
+    def cem_sample_device(self, spec: _abi.CemSpec, iteration: int, d_mean: int, d_sigma: int, d_commands: int) -> None:
+        """The command batch float[B][H][S][n] rollout_velocity_device reads, from the mean plan and the sigma plan float[B][H][n]
+        (cdpr_cem_sample_device): mppi_sample_device's normals, each scaled by its own sigma entry, clamped under CEM_CLAMP, sample 0
+        the mean itself under CEM_NOMINAL_FIRST.  Device buffers; queued on the engine's stream, nothing copied or waited for."""
+        vp = lambda x: C.c_void_p(x) if x else None  # noqa: E731
+        self._check(lib().cdpr_cem_sample_device(self._h, C.byref(spec), int(iteration) & 0xFFFFFFFF, vp(d_mean), vp(d_sigma), vp(d_commands)))
+
+    def cem_update_device(self, spec: _abi.CemSpec, d_cost: int, d_commands: int, d_mean: int, d_sigma: int, d_action: int = 0, d_elite: int = 0,
+                          d_best: int = 0, d_status: int = 0) -> None:
+        """The rollout's costs float[B][S] turned into the next plans (cdpr_cem_update_device): every robot's spec.elites best samples
+        are picked, d_mean and d_sigma float[B][H][n] become the elites' mean and standard deviation blended by spec.alpha into the old
+        plans (moved one step on under CEM_SHIFT), d_action float[B][n] the new mean's first row - what set_velocity_command_device
+        takes; d_elite float[B][S] (1 for an elite), d_best int32[B], d_status uint32[_abi.CEM_STATUS]; 0 = not wanted.  Queued on the
+        engine's stream, nothing copied or waited for."""
+        vp = lambda x: C.c_void_p(x) if x else None  # noqa: E731
+        self._check(lib().cdpr_cem_update_device(self._h, C.byref(spec), vp(d_cost), vp(d_commands), vp(d_mean), vp(d_sigma), vp(d_action),
+                                                 vp(d_elite), vp(d_best), vp(d_status)))
+
+    def cem_sample(self, mean, sigma, spec: _abi.CemSpec, iteration: int) -> np.ndarray:
+        """commands float32[B, H, S, n] on the host: the mean and sigma plans [B, H, n] go up, cem_sample_device runs into a scratch
+        buffer, the batch comes down."""
+        H, S = int(spec.horizon), int(spec.samples)
+        m = np.ascontiguousarray(mean, dtype=np.float32).reshape(self.B, H, self.n)
+        g = np.ascontiguousarray(sigma, dtype=np.float32).reshape(self.B, H, self.n)
+
+        def body(ptrs):
+            self.device_upload_into(ptrs[0], m)
+            self.device_upload_into(ptrs[1], g)
+            self.cem_sample_device(spec, iteration, ptrs[0], ptrs[1], ptrs[2])
+            return self.device_download(ptrs[2], (self.B, H, S, self.n), np.float32)
+
+        return self._with_scratch([m.nbytes, g.nbytes, 4 * self.B * H * S * self.n], body)
+
+    def cem_update(self, cost, commands, mean, sigma, spec: _abi.CemSpec):
+        """(mean float32[B, H, n], sigma float32[B, H, n], action float32[B, n], elite float32[B, S], best int32[B], status
+        uint32[_abi.CEM_STATUS]) on the host: cost [B, S], commands [B, H, S, n] and both plans go up, cem_update_device runs on scratch
+        buffers, the results come down."""
+        H, S = int(spec.horizon), int(spec.samples)
+        c = np.ascontiguousarray(cost, dtype=np.float32).reshape(self.B, S)
+        v = np.ascontiguousarray(commands, dtype=np.float32).reshape(self.B, H, S, self.n)
+        m = np.ascontiguousarray(mean, dtype=np.float32).reshape(self.B, H, self.n)
+        g = np.ascontiguousarray(sigma, dtype=np.float32).reshape(self.B, H, self.n)
+
+        def body(ptrs):
+            d_c, d_v, d_m, d_g, d_action, d_elite, d_best, d_status = ptrs
+            for d, a in ((d_c, c), (d_v, v), (d_m, m), (d_g, g)):
+                self.device_upload_into(d, a)
+            self.cem_update_device(spec, d_c, d_v, d_m, d_g, d_action, d_elite, d_best, d_status)
+            return (self.device_download(d_m, (self.B, H, self.n), np.float32), self.device_download(d_g, (self.B, H, self.n), np.float32),
+                    self.device_download(d_action, (self.B, self.n), np.float32), self.device_download(d_elite, (self.B, S), np.float32),
+                    self.device_download(d_best, self.B, np.int32), self.device_download(d_status, _abi.CEM_STATUS, np.uint32))
+
+        return self._with_scratch([c.nbytes, v.nbytes, m.nbytes, g.nbytes, 4 * self.B * self.n, c.nbytes, 4 * self.B, 4 * _abi.CEM_STATUS], body)
+
     # -- done rules: who should be put back, decided on the device
     @staticmethod
     def _rule(rule):

@@ -133,6 +133,28 @@ class ShardedEngine:
         parts = [e.mppi_update(c[lo:hi], v[lo:hi], u[lo:hi], spec) for e, (lo, hi) in zip(self.engines, self.spans)]
         return tuple(np.concatenate([p[k] for p in parts]) for k in range(4)) + (np.sum([p[4] for p in parts], axis=0, dtype=np.uint32),)
 
+    def cem_sample(self, mean, sigma, spec, iteration):
+        """Engine.cem_sample over the shards: both plans split by shard_range, every shard's spec with robot_offset moved on by its
+        first robot, so the batch is to the bit what one engine of the whole batch writes."""
+        import numpy as np
+
+        m = np.asarray(mean, dtype=np.float32).reshape(self.B, int(spec.horizon), self.n)
+        g = np.asarray(sigma, dtype=np.float32).reshape(self.B, int(spec.horizon), self.n)
+        return np.concatenate([e.cem_sample(m[lo:hi], g[lo:hi], spec.with_offset(lo), iteration) for e, (lo, hi) in zip(self.engines, self.spans)])
+
+    def cem_update(self, cost, commands, mean, sigma, spec):
+        """Engine.cem_update over the shards (the update is per robot): rows split by shard_range, mean, sigma, action, elite and best
+        concatenated in shard order, status summed."""
+        import numpy as np
+
+        H, S = int(spec.horizon), int(spec.samples)
+        c = np.asarray(cost, dtype=np.float32).reshape(self.B, S)
+        v = np.asarray(commands, dtype=np.float32).reshape(self.B, H, S, self.n)
+        m = np.asarray(mean, dtype=np.float32).reshape(self.B, H, self.n)
+        g = np.asarray(sigma, dtype=np.float32).reshape(self.B, H, self.n)
+        parts = [e.cem_update(c[lo:hi], v[lo:hi], m[lo:hi], g[lo:hi], spec) for e, (lo, hi) in zip(self.engines, self.spans)]
+        return tuple(np.concatenate([p[k] for p in parts]) for k in range(5)) + (np.sum([p[5] for p in parts], axis=0, dtype=np.uint32),)
+
     def evaluate_done(self, rule):
         """Engine.evaluate_done over the shards: masks and reasons concatenated in shard_range order, counts summed."""
         import numpy as np

@@ -40,7 +40,7 @@ extern "C" {
  * after 8 as new exports only: no struct or call that existed changed, so the number stays 8.  A caller discovers the feature by those
  * symbols and checks its cdpr_env_spec_t against cdpr_env_spec_size().  So did the fork (cdpr_copy_robots*) and the resampler
  * (cdpr_resample_spec_t, cdpr_resample_spec_size, cdpr_resample_map_device, cdpr_resample_device) and MPPI (cdpr_mppi_spec_t, cdpr_mppi_spec_size, cdpr_mppi_sample_device,
- * cdpr_mppi_update_device). */
+ * cdpr_mppi_update_device) and CEM (cdpr_cem_spec_t, cdpr_cem_spec_size, cdpr_cem_sample_device, cdpr_cem_update_device). */
 #define CDPR_ABI_VERSION 8u   /* 8 = 7 + cdpr_done_rule_t, cdpr_evaluate_done, cdpr_evaluate_done_device, cdpr_reset_done_device, cdpr_get_episode_start, cdpr_done_rule_size; 7 = 6 + cdpr_reset_robots, cdpr_reset_robots_device; 6 = 5 + cdpr_plan_kernel, cdpr_kernel_name, CDPR_MAX_CABLES 8 -> 12 (cdpr_config_t's anchor arrays grow); 5 = 4 + cdpr_update_scheduled_kind, cdpr_device_pci_bus_id, cdpr_decode_observables_f64 */
 #define CDPR_MAX_CABLES 12u         /* PLG.h:20 fixes 4 (kCableCount); cube.yaml:21-29 is a free-length `points` list: the engine takes 1..12
                                       (9..12: uniform-mode fp32 handles on the lane-per-robot kernels, FK and TD included; see cdpr_create) */
@@ -363,6 +363,72 @@ int cdpr_mppi_sample_device(cdpr_handle_t h, const cdpr_mppi_spec_t *spec, uint3
 int cdpr_mppi_update_device(cdpr_handle_t h, const cdpr_mppi_spec_t *spec, const float *d_cost /*[B][S]*/,
                             const float *d_commands, float *d_nominal /*in/out*/, float *d_action /*[B][n] or NULL*/,
                             float *d_weights /*[B][S] or NULL*/, float *d_ess /*[B] or NULL*/, uint32_t *d_status /*[3] or NULL*/);
+
+/* CEM on the device: the cross-entropy method in MPPI's place around cdpr_rollout_velocity_device.  cdpr_cem_sample_device writes the
+ * command batch float[B][H][S][n] from a mean plan and a sigma plan, float[B][H][n] each (a standard deviation per horizon step and
+ * cable); cdpr_cem_update_device picks every robot's K best samples by the rollout's costs float[B][S] and refits both plans to them.
+ * No temperature: only the order of the costs counts.  Neither reads robot state or touches a step kernel; the handle supplies B, n and
+ * the stream.  New exports after ABI 8, no struct changes.  tests/cem_oracle.py restates the definition in numpy.
+ *
+ * Sample.  cdpr_mppi_sample_device's definition word for word - the same Philox4x32-10 counter (e >> 2, robot_offset + b, iteration, 0)
+ * under the key (seed_lo, seed_hi), the same Box-Muller, the same element order e = (t * S + s) * n + i, the same clamp, the same
+ * CDPR_CEM_NOMINAL_FIRST (sample 0 is the clamped mean), only d_commands[0, B * E) written - with one change: the command is
+ *   v = fmaf(sigma[b][t][i], z, mean[b][t][i]).
+ * A sigma entry is used as it is: 0 gives the mean to the bit, a NaN a NaN in front of the clamp.  The streams being the same, a sigma
+ * plan filled with one value gives bit for bit the batch cdpr_mppi_sample_device writes for that spec.sigma under the same key,
+ * iteration and offset.
+ *
+ * Update, per robot.  A cost is usable iff it is finite; the others are counted BAD.  The usable costs are ordered by value, -0 equal
+ * to +0, equal values by sample index, lower first.  With M usable costs the elites are the first K' = min(K, M) of that order
+ * (K = spec.elites).  M = 0: the robot is DEGENERATE and counted - both plans stay (moved one row on under CDPR_CEM_SHIFT), d_elite is 0,
+ * d_best is -1, d_action the old mean's first row.  0 < M < K: the robot is counted SHORT (and updated).  The fit, for every (t, i) over
+ * the elites' commands V[t][s][i]:
+ *   m = (sum v) / K',   d = v - m (one float subtraction against the float m as computed),   var = (sum d * d) / K',   f = sqrtf(var)
+ * (the population variance in two passes; K' as a float).  Sums are float in a fixed order: S <= 4096: lane l of 64 adds the elites
+ * of rank l, l + 64, .. (ranks by ascending sample index) in that order, d * d by fmaf; S > 4096: lane l adds the elites among the
+ * samples l, l + 64, .. in that order; then a xor butterfly over the 64 lanes (distances 32, 16, .. 1) either way.  The same inputs
+ * give the same bits on every run; against the definition in double the results agree within the bounds tests/cem_oracle.py derives.
+ * The commands of a sample that is no elite are not read: a NaN behind one does not reach a plan.  An elite's NaN does.
+ * Smoothing against the old plans:
+ *   mean' = fmaf(alpha, m - mean, mean),   sigma' = fminf(fmaxf(fmaf(alpha, f - sigma, sigma), sigma_min), sigma_max);
+ * alpha == 1 selects m and f themselves (selected, not multiplied: a NaN in the old plan is then harmless; sigma' is still clamped).
+ * d_action[b][i] = mean'[0][i].  d_elite[b][s] = 1.0f for an elite, else 0.0f.  d_best[b] = the first sample of the order.  The plans
+ * written are mean' and sigma'; with CDPR_CEM_SHIFT out[t] = plan'[t + 1], the last row repeated.  In place: every row of a robot's
+ * d_mean and d_sigma is read before it is written, also where under CDPR_CEM_SHIFT another row's blend is stored over it.
+ * d_action float[B][n], d_elite float[B][S], d_best int32[B], d_status uint32[4] = [robots updated, robots degenerate, bad costs, robots
+ * short] (zeroed on the stream in front of the kernel): each may be NULL.  All device buffers; they must stay valid until the stream
+ * has passed the call.
+ *
+ * Both calls: any handle - uniform or per-robot, every kernel family, both precisions, 1 .. 12 cables.  Stream-ordered behind
+ * everything queued; they copy nothing and wait for nothing.  Not step launches: cdpr_kernel_name, cdpr_plan_kernel and the launch
+ * counter do not see them.  Both calls check the whole spec.
+ * CEM refusals (a refused call queues nothing): CDPR_ERR_INVALID for a NULL handle, a NULL spec, a NULL required buffer (sample: d_mean,
+ * d_sigma, d_commands; update: d_cost, d_commands, d_mean, d_sigma), struct_size != sizeof(cdpr_cem_spec_t), an unknown flag bit,
+ * a reserved word != 0, samples == 0, horizon == 0, elites == 0, elites > samples, an alpha that is not in (0, 1] or not finite,
+ * a sigma_min that is negative or not finite or greater than sigma_max, a sigma_max that is NaN (+inf is allowed: no upper clamp),
+ * CDPR_CEM_CLAMP with bounds that are not finite or with cmd_min > cmd_max;
+ * CDPR_ERR_UNSUPPORTED for E > 2^34, B * S > 2^30 (the rollout's own limit). */
+#define CDPR_CEM_NOMINAL_FIRST 1u    /* sample 0 of every robot is the (clamped) mean itself              */
+#define CDPR_CEM_CLAMP         2u    /* commands clamped to [cmd_min, cmd_max] (finite, cmd_min <= cmd_max) */
+#define CDPR_CEM_SHIFT         4u    /* update: both plans move one step towards now (receding horizon)   */
+
+typedef struct cdpr_cem_spec {
+  uint32_t struct_size, samples /*S*/, horizon /*H*/, flags;
+  uint32_t elites;                 /* K: 1 .. S                                       */
+  float alpha;                     /* smoothing, (0, 1]; 1 = the fit itself           */
+  float sigma_min, sigma_max;      /* sigma' clamped to [sigma_min, sigma_max]        */
+  float cmd_min, cmd_max;
+  uint32_t seed_lo, seed_hi;       /* Philox key                                      */
+  uint32_t robot_offset;           /* global index of the handle's robot 0 (shards)   */
+  uint32_t reserved[3];            /* 0                                               */
+} cdpr_cem_spec_t;
+
+size_t cdpr_cem_spec_size(void);                     /* sizeof(cdpr_cem_spec_t) as compiled */
+int cdpr_cem_sample_device(cdpr_handle_t h, const cdpr_cem_spec_t *spec, uint32_t iteration, const float *d_mean /*[B][H][n]*/,
+                           const float *d_sigma /*[B][H][n]*/, float *d_commands /*[B][H][S][n]*/);
+int cdpr_cem_update_device(cdpr_handle_t h, const cdpr_cem_spec_t *spec, const float *d_cost /*[B][S]*/, const float *d_commands,
+                           float *d_mean /*in/out*/, float *d_sigma /*in/out*/, float *d_action /*[B][n] or NULL*/,
+                           float *d_elite /*[B][S] or NULL*/, int32_t *d_best /*[B] or NULL*/, uint32_t *d_status /*[4] or NULL*/);
 
 /* Done rules: which robots a loop should put back, decided on the device.  cdpr_reset_robots_device takes a "done" mask that lives
  * on the GPU; these calls compute it there, from the state the handle already holds, so that a Monte-Carlo sweep, an RL-style
